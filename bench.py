@@ -8,6 +8,12 @@ Multi-GPU (torchrun): one process per GPU, each rank owns its own batch of 512 g
 (graph-sharded, weak scaling; the forward has no data-path collective).  Timing: barrier +
 device sync on both sides of exactly K steps; the max over ranks is reported.
 
+A plain run (``bench.py --gpus N --steps K --warmup W``) sets up, warms up, times the K steps and
+prints the line.  ``--dump-outputs DIR`` also writes what the last timed step computed as
+``DIR/<name>.npy``.  Every measurement that takes runs of its own (the CPU baselines, the isolated
+leg behind roofline.isolated / readout_isolated / step_account, the 1M-node edge-cut leg) runs
+under ``--full`` only.
+
 Extra objects on the JSON line:
   roofline      dominant kernel (most time in the warm-up), on its binding roof:
                 algorithmic FLOPs (mfma, peak fp32 MFMA 157.3 TFLOP/s) or bytes (hbm, 8 TB/s)
@@ -15,11 +21,14 @@ Extra objects on the JSON line:
                 around that kernel's launches in the timed region; traffic = HBM bytes per
                 launch from the committed rocprofv3 PMC summary (profiles/), or null.
                 warmup_kernels: every kernel kind, timed during the warm-up.
-  cpu_baseline  the dense-padded oracle (oracle/dense_forward.py, float32 numpy, the TF op
+                --full adds isolated, readout_isolated and step_account (sub-batch 0 alone on the
+                chip, three forwards after the timed region).
+  cpu_baseline  (--full) the dense-padded oracle (oracle/dense_forward.py, float32 numpy, the TF op
                 sequence incl. padded work) on a bounded sample of the same workload, rank 0, N=1,
                 one process per CPU this process may use (CPU model and count on the line).
-  cpu_baseline_cxx  the second CPU line: the C++/OpenMP float32 restatement
+  cpu_baseline_cxx  (--full) the second CPU line: the C++/OpenMP float32 restatement
                 (oracle/cpu_forward.cpp) on the same sample and CPUs.
+  edge_cut_1m   (--full) the 1M-node / 10M-edge graph in the same ranks, after the main measurement.
 """
 
 import argparse
@@ -65,13 +74,21 @@ def parse():
                     help="forward: the rank's graphs as this many sub-batches, one engine / HIP stream each, "
                          "launched back to back in every step (their kernels co-run); 0 = auto: 4 for graphs "
                          "of fewer than 1000 paths or models of 3+ MPs per iteration (Q-size), else 2")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU baseline sample budget")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-timing", action="store_true", help="skip per-kernel HIP event timing")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baselines, the isolated leg "
+                         "(sub-batch 0 alone on the chip, after the timed region) and the edge-cut leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32; "
+                         "at most 64 MB in all, a fixed seeded sample of a larger output; _rank<r> suffix at N > 1)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="with --full: CPU baseline sample budget")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-timing", action="store_true",
+                    help="skip per-kernel HIP event timing (and with it --full's isolated leg)")
     ap.add_argument("--no-edge-cut", action="store_true",
-                    help="skip the edge-cut leg (the 1M-node / 10M-edge graph of BASELINE configs[4] split across "
-                         "the same ranks, RCCL halo all-to-all per MP; at N=1 the whole graph on one GPU), which "
-                         "otherwise runs after the main measurement and is reported under 'edge_cut_1m'")
+                    help="with --full or --dry-run: skip the edge-cut leg (the 1M-node / 10M-edge graph of BASELINE "
+                         "configs[4] split across the same ranks, RCCL halo all-to-all per MP; at N=1 the whole "
+                         "graph on one GPU), which otherwise runs after the main measurement and is reported under "
+                         "'edge_cut_1m'")
     ap.add_argument("--edge-cut-nodes", type=int, default=1_000_000, help="edge-cut leg: synthetic graph size")
     ap.add_argument("--edge-cut-steps", type=int, default=0, help="edge-cut leg: timed forwards (0: --steps)")
     ap.add_argument("--dry-run", action="store_true",
@@ -230,6 +247,38 @@ def _reduce(dist, vals, op, device=None):
     t = torch.tensor([float(v) for v in vals], dtype=torch.float64, device=device)
     dist.all_reduce(t, op=dist.ReduceOp.MAX if op == "max" else dist.ReduceOp.SUM)
     return t.cpu().tolist()
+
+
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: all files of all ranks together
+DUMP_SEED = 20261015
+
+
+def read_predictions(batch):
+    """The predictions the batch's last forward left on the device (no new launch)."""
+    import ctypes as C
+
+    import numpy as np
+    from ignnition_amd.engine import check, lib
+    out = np.empty((batch.predictions, batch.output_units), np.float32)
+    check(lib.ign_batch_read_predictions(batch.engine.handle, batch.handle, out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def dump_outputs(path, arrays, rank=0, world=1, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every array of ``arrays`` as ``path/<name>.npy`` in float32 (``_rank<r>``
+    after the name at N > 1).  Beyond the byte limit each array keeps a fixed sample of its
+    elements in their order (the same indices in every run: seeded by the array's size only)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    limit = limit // max(world, 1)
+    for name, a in arrays.items():
+        if total > limit:
+            keep = max(1, int(a.size * (limit / total)))
+            rng = np.random.Generator(np.random.PCG64([DUMP_SEED, a.size]))
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, name + ("" if world == 1 else "_rank%d" % rank) + ".npy"), a)
 
 
 def edge_cut_key(nodes: int) -> str:
@@ -429,7 +478,9 @@ def main():
     if args.dry_run:
         return dry_run(args, dist, rank, world, mi, graphs, synthetic)
     cpu = cpu_cxx = None
-    if world == 1 and not args.no_cpu and not args.train:
+    dump_batches = []   # --dump-outputs: the batches whose predictions the step leaves on the device
+    train_out = {}      # --dump-outputs: the training step's device tensors (gradients)
+    if args.full and world == 1 and not args.no_cpu and not args.train:
         # before anything touches the GPU: the baseline's worker processes are forked
         if synthetic:
             # bounded sample: 25k-node graphs from the same generator (same degree law and locality)
@@ -478,12 +529,14 @@ def main():
                 it_box[0] += 1
             edges = tr.batches[0].edges_per_forward
             gru_steps = tr.batches[0].gru_steps_per_forward
+            dump_batches += tr.batches
             cleanup.append(tr.close)
         else:
             fw = partition.EdgeCutForward(eng, [part], comm)
             step = lambda: fw.forward(to_host=False)
             edges = fw.edges_per_forward
             gru_steps = fw.batches[0].gru_steps_per_forward
+            dump_batches += fw.batches
     elif args.train and args.fresh_batches:
         # the real input pipeline: write the rank's graphs as a tar.gz dataset in the reference
         # layout, then every step reads a new shuffled batch through the native reader
@@ -538,9 +591,11 @@ def main():
         edges = sb.edges_per_forward
         gru_steps = sb.gru_steps_per_forward
         batches += sb.parts
+        dump_batches += sb.parts
     else:
         batch = Batch(eng, graphs)
         batches.append(batch)
+        dump_batches.append(batch)
         step = lambda: batch.forward(to_host=False)
         edges = batch.edges_per_forward
         gru_steps = batch.gru_steps_per_forward
@@ -554,6 +609,7 @@ def main():
             grads = torch.zeros(eng.n_params, dtype=torch.float32, device=y.device)
             m_state, v_state = torch.zeros_like(grads), torch.zeros_like(grads)
             it_box = [0]
+            train_out["grads"] = grads
 
             def step():   # model_fn TRAIN (GM:712-818): one optimizer step on the rank's batch
                 batch.forward_train(to_host=False)
@@ -581,8 +637,20 @@ def main():
     barrier_sync()
     dt = time.perf_counter() - t0
     stats = stats_all()
+    if args.dump_outputs:
+        # what the last timed step left: the predictions in graph order (a training step: before its
+        # update), and after a training step its gradients and the updated parameters
+        outs = {}
+        if dump_batches:
+            outs["predictions"] = np.concatenate([read_predictions(b) for b in dump_batches])
+        if args.train:
+            if "grads" in train_out:
+                outs["grads"] = train_out["grads"].detach().cpu().numpy()
+            prm_out = engines[0].get_params()
+            outs["params"] = np.concatenate([prm_out[name].reshape(-1) for name, _, _ in engines[0].layout])
+        dump_outputs(args.dump_outputs, outs, rank, world)
     isolated = isolated_all = None
-    if len(subs) > 1 and not args.no_timing and not args.train:
+    if args.full and len(subs) > 1 and not args.no_timing and not args.train:
         # isolated leg, after the timed region: sub-batch 0 alone on the chip, its dominant kernel's
         # and the readout's launches timed (in the timed region the sub-batches' kernels co-run, so
         # there a launch's duration is its share of a chip it does not have to itself)
@@ -604,7 +672,7 @@ def main():
     total_edges = total_edges_step * args.steps
     value = total_edges / dt
     edge_cut = None
-    if not (synthetic or args.train or args.no_edge_cut):
+    if args.full and not (synthetic or args.train or args.no_edge_cut):
         # BASELINE configs[4] in the same ranks: the 1M-node graph edge-cut over
         # RCCL at N>1, whole on one GPU at N=1; the main line's value stays the RouteNet metric
         edge_cut = edge_cut_leg(args, dist, rank, world, device if world > 1 else 0, backend)

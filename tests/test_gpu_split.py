@@ -66,7 +66,7 @@ def test_split_batch_replicas_follow_parameter_updates():
 
 
 def test_bench_line_with_sub_batch_streams():
-    """bench.py's default step (two sub-batch streams) on a small batch: one JSON line whose
+    """bench.py --full's default step (two sub-batch streams) on a small batch: one JSON line whose
     roofline carries the timed region's figure and the isolated one; --streams 1 has no isolated leg."""
     import json
     import os
@@ -76,7 +76,7 @@ def test_bench_line_with_sub_batch_streams():
     lines = {}
     for streams in (2, 1):
         r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--graphs", "16", "--steps", "2",
-                            "--warmup", "1", "--no-cpu", "--streams", str(streams)],
+                            "--warmup", "1", "--full", "--no-cpu", "--streams", str(streams)],
                            capture_output=True, text=True, timeout=300, cwd=repo)
         assert r.returncode == 0, r.stderr[-2000:]
         out = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
@@ -89,3 +89,29 @@ def test_bench_line_with_sub_batch_streams():
     iso = two["roofline"]["isolated"]
     assert iso["launches"] > 0 and 0 < iso["frac"] and "note" in two["roofline"]
     assert "isolated" not in one["roofline"]
+
+
+def test_bench_plain_run_dumps_last_step_predictions(tmp_path):
+    """A plain bench.py run: the timed steps only (no CPU baseline, isolated or edge-cut leg), and
+    --dump-outputs writes the last step's predictions, bitwise those of one Batch over the same
+    seeded graphs and parameters."""
+    import json
+    import os
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--graphs", "16", "--steps", "2",
+                        "--warmup", "1", "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=300, cwd=repo)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(out) == 1
+    line = out[0]
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["cpu_baseline"] is None and line["cpu_baseline_cxx"] is None
+    assert not any(k.startswith("edge_cut") for k in line)
+    assert "isolated" not in (line["roofline"] or {}) and "step_account" not in (line["roofline"] or {})
+    assert os.listdir(tmp_path / "out") == ["predictions.npy"]
+    got = np.load(tmp_path / "out" / "predictions.npy")
+    eng, _, graphs, _ = _engine("routenet", "synth50", 16)
+    assert got.dtype == np.float32 and np.array_equal(got, Batch(eng, graphs).forward())
