@@ -545,7 +545,8 @@ int ign_plan_create(const ign_plan_desc* d, int32_t device, ign_plan** out) {
   for (size_t l = 0; l < p->dense.size(); ++l) {
     DenseP& dp = p->dense[l];
     dp.off_w = off; p->tensors.push_back({3, (int)l, off, dp.in, dp.out}); off = align(off + (int64_t)dp.in * dp.out);
-    dp.off_b = off; p->tensors.push_back({4, (int)l, off, 1, dp.out}); off = align(off + dp.out);
+    // use_bias false: Keras' Dense owns no bias variable, so the layout has none either
+    if (dp.use_bias) { dp.off_b = off; p->tensors.push_back({4, (int)l, off, 1, dp.out}); off = align(off + dp.out); }
   }
   p->n_params = off;
   int64_t pk = 0;

@@ -209,7 +209,7 @@ struct Lowered {
     for (auto& l : dense) {
       const std::string pre = "readout_model_" + std::to_string(predict_counter) + "/" + l.name;
       s.push_back({pre + "/kernel", {fan, l.d.units}});
-      s.push_back({pre + "/bias", {l.d.units}});
+      if (l.d.use_bias) s.push_back({pre + "/bias", {l.d.units}});
       fan = l.d.units;
     }
     return s;

@@ -335,7 +335,9 @@ class MPPlan:
         fan_in = sum(self.ro_widths[i] for i in self.readout_inputs)
         for li, (name, units, _, use_bias, _) in enumerate(self.dense):
             pre = "readout_model_%d/%s" % (self.predict_counter, name or ("layer_%d" % li))
-            specs += [(pre + "/kernel", (fan_in, units)), (pre + "/bias", (units,))]
+            specs.append((pre + "/kernel", (fan_in, units)))
+            if use_bias:
+                specs.append((pre + "/bias", (units,)))
             fan_in = units
         return specs
 
@@ -478,6 +480,13 @@ class Engine:
                                   n, cols, C.c_void_p(dst.data_ptr())))
 
     def close(self):
+        # ign_batch_destroy reads its plan (stream, block cache): while a batch of this engine is
+        # open, the plan stays, and the last batch's close() destroys it.  (The collector finalises
+        # an engine and its batches in no particular order when they die in one reference cycle,
+        # e.g. in the traceback of a failed test.)
+        if getattr(self, "_open_batches", 0) > 0:
+            self._close_pending = True
+            return
         for r in getattr(self, "_replicas", []):
             r.close()
         self._replicas = []
@@ -610,6 +619,7 @@ class Batch:
         h = C.c_void_p()
         check(lib.ign_batch_create(engine.handle, C.byref(desc), C.byref(h)))
         self.handle = h
+        engine._open_batches = getattr(engine, "_open_batches", 0) + 1
         _LIVE_BATCHES.add(self)
         info = _lib.BatchInfo()
         check(lib.ign_batch_info(h, C.byref(info)))
@@ -741,6 +751,10 @@ class Batch:
         if h:
             lib.ign_batch_destroy(h)
             self.handle = None
+            eng = self.engine
+            eng._open_batches -= 1
+            if eng._open_batches == 0 and getattr(eng, "_close_pending", False):
+                eng.close()
 
     def __del__(self):
         self.close()

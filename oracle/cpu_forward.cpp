@@ -481,10 +481,11 @@ int ign_oracle_forward(const ign_plan_desc* p, const ign_batch_desc* d, const fl
   int in = 0;
   for (int i = 0; i < p->num_readout_inputs; ++i) in += p->entities[p->readout_inputs[i]].hidden_dim;
   for (int l = 0; l < p->num_dense; ++l) {
-    if (k + 2 > n_params) return err(IGN_ERR_INVALID, "too few parameter tensors");
-    m.dense.push_back({in, p->dense[l].units, p->dense[l].activation, params[k], params[k + 1]});
+    const int nt = p->dense[l].use_bias ? 2 : 1;   // a Dense without bias owns a kernel only
+    if (k + nt > n_params) return err(IGN_ERR_INVALID, "too few parameter tensors");
+    m.dense.push_back({in, p->dense[l].units, p->dense[l].activation, params[k], nt == 2 ? params[k + 1] : nullptr});
     in = p->dense[l].units;
-    k += 2;
+    k += nt;
   }
   if (k != n_params) return err(IGN_ERR_INVALID, "parameter tensor count does not match the plan");
   const int G = d->num_graphs, E = p->num_entities, A = p->num_adjacencies, I = p->num_interleave;

@@ -46,6 +46,21 @@ def test_examples_match_dense_oracle(kind, topo, n):
     _check(desc, dims, graphs)
 
 
+@pytest.mark.parametrize("case", ["nobias_hidden", "nobias_out", "mixed", "four_layer", "odd_widths", "out3", "sigmoid_out"])
+def test_predict_networks_match_dense_oracle(case):
+    """Predict networks of other shapes (tests/predict_cases.py): a Dense with use_bias false owns no
+    bias tensor in the plan's parameter list, and neither restatement adds one."""
+    from tests.predict_cases import PREDICT_CASES, forward_case, layer_name
+    desc, dims, plan, graphs, _, prm, ref = forward_case(case, 32)
+    names = [n for n, _ in plan.param_specs()]
+    for i, (_, _, extra) in enumerate(PREDICT_CASES[case]):
+        pre = "readout_model_0/%s/" % layer_name(i)
+        assert pre + "kernel" in names and ((pre + "bias") in names) == extra.get("use_bias", True)
+    assert sorted(names) == sorted(prm)
+    _close(cpu_oracle.cpu_forward(plan, graphs, prm, 2, float64=True), ref, TOL64)
+    _close(cpu_oracle.cpu_forward(plan, graphs, prm, 2), ref, TOL32)
+
+
 @pytest.mark.parametrize("threads", [1, 3])
 def test_one_large_graph_parallel_over_destinations(threads):
     desc, dims, mi, graphs, _ = workloads.make_synthetic_inputs(n_nodes=2000, iterations=3, window=64)

@@ -45,16 +45,24 @@ def _engine_grads(desc, dims, graphs, labels, prm, eng=None):
     return eng, b, pred, loss, named, grads
 
 
-def _check(desc, dims, graphs, labels, prm):
-    eng, b, pred, loss, g, _ = _engine_grads(desc, dims, graphs, labels, prm)
-    o_loss, o_reg, o_g, o_pred = TorchOracle(desc, dims, prm).loss_and_grads(graphs, labels)
+def _check_grads(desc, dims, graphs, labels, prm, oracle=None):
+    """Loss, l2 term, predictions and every gradient tensor of a fresh engine against torch autograd of
+    the float64 restatement (``oracle``: its loss_and_grads result, where the caller has it already)."""
+    eng, b, pred, loss, g, grads = _engine_grads(desc, dims, graphs, labels, prm)
+    o_loss, o_reg, o_g, o_pred = oracle or TorchOracle(desc, dims, prm).loss_and_grads(graphs, labels)
     np.testing.assert_allclose(pred.reshape(-1), o_pred, rtol=1e-4, atol=1e-4)
     assert loss == pytest.approx(o_loss, rel=1e-5)
     assert eng.l2_loss() == pytest.approx(o_reg, rel=1e-5)
+    rel = {name: np.linalg.norm(g[name].astype(np.float64) - og) / max(np.linalg.norm(og), 1e-30) for name, og in o_g.items()}
+    print("worst gradient tensor vs float64 autograd: %s, relative L2 %.3g" % max((v, k) for k, v in rel.items())[::-1])
     for name, og in o_g.items():
         err = np.linalg.norm(g[name].astype(np.float64) - og)
         assert err <= GTOL * np.linalg.norm(og) + 1e-7, "%s: rel err %.3g" % (name, err / max(np.linalg.norm(og), 1e-30))
-    return eng, b
+    return eng, b, grads
+
+
+def _check(desc, dims, graphs, labels, prm):
+    return _check_grads(desc, dims, graphs, labels, prm)[:2]
 
 
 @pytest.mark.parametrize("kind,n", [("routenet", 1), ("routenet", 3), ("qsize", 2)])
@@ -531,3 +539,94 @@ def test_gpu_transposed_csrs_equal_host(monkeypatch, kind, topo, n):
     g_host = _engine_grads(desc, dims, graphs, labels, prm)[5].cpu().numpy()
     assert np.abs(g_host).sum() > 0
     np.testing.assert_array_equal(g_gpu, g_host)
+
+
+# ---------------------------------------------------------------------------------------------
+# predict networks beyond 256-selu-256-selu-1 (tests/predict_cases.py)
+from tests.predict_cases import PREDICT_CASES, forward_case  # noqa: E402
+
+_ORACLE_GRADS = {}
+
+
+def _predict_case(case, hidden=32):
+    """forward_case's inputs and torch autograd of the float64 restatement (once per case), checked not
+    to be degenerate: predictions that vary, every gradient tensor non-zero.  out3's labels [P][3] come
+    from a fixed RNG (the loss is the mean over the flat [P * 3] predictions, GM:716-753)."""
+    desc, dims, plan, graphs, labels, prm, ref = forward_case(case, hidden)
+    if case == "out3":
+        rng = np.random.default_rng(5)
+        labels = [rng.normal(size=(int(np.asarray(g["num_path"])), 3)).astype(np.float32) for g in graphs]
+    if (case, hidden) not in _ORACLE_GRADS:
+        _ORACLE_GRADS[case, hidden] = TorchOracle(desc, dims, prm).loss_and_grads(graphs, labels)
+    o = _ORACLE_GRADS[case, hidden]
+    assert np.ptp(o[3]) > 1e-3
+    if case == "relu_out":
+        assert (o[3] > 0).mean() >= 0.25
+    assert set(o[2]) == set(prm)
+    for name, og in o[2].items():
+        assert np.linalg.norm(og) > 0, name
+    return desc, dims, graphs, labels, prm, o
+
+
+def _again(eng, b, labels):
+    """A second forward and backward of the same batch: the flat gradient."""
+    y = torch.tensor(np.concatenate([np.asarray(l, np.float32).reshape(-1) for l in labels]), device="cuda")
+    dpred = torch.empty_like(y)
+    grads = torch.zeros(eng.n_params, dtype=torch.float32, device="cuda")
+    b.forward_train(to_host=False)
+    eng.mse_loss(b.predictions_ptr(), y, dpred)
+    b.backward(dpred, grads)
+    torch.cuda.synchronize()
+    return grads
+
+
+@pytest.mark.parametrize("case", sorted(PREDICT_CASES))
+def test_gradients_predict_networks(case):
+    """Every predict-network case at hidden 32, default switches: the training forward's kernel per
+    layer (readout_h16<SAVE>, dense_h16, dense_fwd_kernel, the dot kernel, dense_generic) and the
+    backward's (act_bwd on the output activation, the on-the-fly output rows, dense_h16_t, row_gemm_t,
+    row_gemm_t_generic, bias gradients present or not) against float64 autograd; a second forward and
+    backward of the same batch gives the same bits."""
+    desc, dims, graphs, labels, prm, o = _predict_case(case)
+    eng, b, grads = _check_grads(desc, dims, graphs, labels, prm, oracle=o)
+    assert torch.equal(_again(eng, b, labels), grads)
+    b.close()
+    eng.close()
+
+
+@pytest.mark.parametrize("case", ["relu", "tanh", "sigmoid", "linear", "selu", "sigmoid_out"])
+def test_gradients_predict_switches(monkeypatch, case):
+    """The fused activation cases under each training-readout switch, one at a time on a fresh engine:
+    readout_h32's SAVE form (IGN_READOUT_VARIANT=5), the per-layer forward (IGN_TRAIN_FUSED_READOUT=0),
+    the split-bf16 and f32-MFMA Dense kernels (IGN_TRAIN_DENSE_H16=0, IGN_TRAIN_DENSE_BF=0) and
+    row_outer_t (IGN_FUSE_OUTER_BWD=0).  Each within GTOL of float64 autograd per tensor, and variant 5
+    within GTOL of the default (variant 4) per tensor."""
+    desc, dims, graphs, labels, prm, o = _predict_case(case)
+    eng, b, base = _check_grads(desc, dims, graphs, labels, prm, oracle=o)
+    b.close()
+    eng.close()
+    g4 = base.cpu().numpy().astype(np.float64)
+    for switch, v in (("IGN_READOUT_VARIANT", "5"), ("IGN_TRAIN_FUSED_READOUT", "0"), ("IGN_TRAIN_DENSE_H16", "0"),
+                      ("IGN_TRAIN_DENSE_BF", "0"), ("IGN_FUSE_OUTER_BWD", "0")):
+        with monkeypatch.context() as m:
+            m.setenv(switch, v)
+            print("%s=%s" % (switch, v))
+            eng, b, grads = _check_grads(desc, dims, graphs, labels, prm, oracle=o)
+            if switch == "IGN_READOUT_VARIANT":
+                g5 = grads.cpu().numpy().astype(np.float64)
+                for name, shape, off in eng.layout:
+                    n = int(np.prod(shape))
+                    ref = np.linalg.norm(g4[off:off + n])
+                    assert np.linalg.norm(g5[off:off + n] - g4[off:off + n]) <= GTOL * ref + 1e-7, name
+            b.close()
+            eng.close()
+
+
+@pytest.mark.parametrize("hidden", [16, 64])
+def test_gradients_predict_selu_hidden_sizes(hidden):
+    """The DIN = 64 SAVE form of readout_h16 and, at hidden 16 (no fused readout kernel with saves),
+    the per-layer Dense kernels, on the 364-row batch."""
+    desc, dims, graphs, labels, prm, o = _predict_case("selu", hidden)
+    eng, b, _ = _check_grads(desc, dims, graphs, labels, prm, oracle=o)
+    b.close()
+    eng.close()

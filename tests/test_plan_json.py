@@ -12,6 +12,7 @@ import pytest
 from ignnition_amd import _lib, model_examples, workloads
 from ignnition_amd.engine import MPPlan
 from ignnition_amd.json_operations import Model_information
+from tests.predict_cases import PREDICT_CASES, SATURATED, predict_model
 from tests.readout_cases import READOUT_CASES
 
 ROUTENET_DIMS = workloads.model("routenet")[1]
@@ -33,6 +34,10 @@ def _cases():
                                                                 activation="selu"), ROUTENET_DIMS)
     for name, (ops, pin, nets) in READOUT_CASES.items():
         c["readout_" + name] = (model_examples.routenet_readout(ops, pin, nets), ROUTENET_DIMS)
+    # predict networks: use_bias false, the four activation strings and "None", 1 to 4 layers, odd widths
+    for name in PREDICT_CASES:
+        if name not in SATURATED:   # (the same descriptions as relu / selu / tanh / sigmoid)
+            c["predict_" + name] = (predict_model(name), ROUTENET_DIMS)
     return c
 
 
@@ -128,6 +133,21 @@ def test_unsupported_models_rejected_like_python():
     d["readout"] = [{"type": "product", "type_product": "dot_product", "input": ["path", "path"], "output_name": "p"}] \
         + d["readout"]
     _rejected(d, ROUTENET_DIMS, -2, "tensordot")
+
+
+@pytest.mark.parametrize("layer", [0, 2])
+@pytest.mark.parametrize("act", ["gelu", "SELU", "softmax"])
+def test_unknown_predict_activation_rejected(layer, act):
+    """An activation name outside _lib.ACT in the predict network: UnsupportedModel from the Python
+    lowering, IGN_ERR_UNSUPPORTED naming the activation from the C++ one (no silent linear layer)."""
+    from ignnition_amd.engine import UnsupportedModel
+    assert act not in _lib.ACT
+    d = predict_model("selu")
+    net = [n for n in d["neural_networks"] if n["nn_name"] == "readout_model"][0]
+    net["nn_architecture"][layer]["activation"] = act
+    with pytest.raises(UnsupportedModel, match="activation %r not supported" % act):
+        MPPlan.from_model_info(Model_information(copy.deepcopy(d), ROUTENET_DIMS))
+    _rejected(d, ROUTENET_DIMS, -2, "activation '%s' not supported" % act)
 
 
 def test_reference_validation_errors():
