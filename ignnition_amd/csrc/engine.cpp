@@ -35,6 +35,7 @@
 #include "kernels.h"
 
 #include "engine_internal.h"
+#include "batch_lower.h"
 #include "train_kernels.h"
 
 namespace ign {
@@ -213,47 +214,6 @@ int dev_alloc(ign_batch* b, float** out, int64_t n) {
 }
 
 int act_ok(int a) { return a >= IGN_ACT_LINEAR && a <= IGN_ACT_TANH; }
-
-// Destination processing order: one global stable sort by message count, descending (tiles of
-// equal length; the longest sequences start first).  Measured faster than per-graph orders with
-// XCD-aware tiles for both the ordered and the sum updates (profiles/r02/seq_experiments).  A
-// counting sort (counts are small): O(n), the same order as std::stable_sort.
-// f(lo, hi) over [0, n) in contiguous chunks on up to IGN_BUILD_THREADS threads (default 2: a
-// training loop already runs several builders), at least min_per items each; the caller's thread
-// takes the first chunk
-template <class F>
-void parallel_ranges(int64_t n, int64_t min_per, F&& f) {
-  static const int T = [] {
-    const char* v = std::getenv("IGN_BUILD_THREADS");
-    return v && *v ? std::max(1, std::atoi(v)) : 2;
-  }();
-  const int nt = (int)std::min<int64_t>(T, std::max<int64_t>(1, n / std::max<int64_t>(1, min_per)));
-  if (nt <= 1) {
-    f(0, n);
-    return;
-  }
-  std::vector<std::thread> th;
-  th.reserve(nt - 1);
-  for (int t = 1; t < nt; ++t) th.emplace_back([&f, n, nt, t] { f(n * t / nt, n * (t + 1) / nt); });
-  f(0, n / nt);
-  for (auto& x : th) x.join();
-}
-
-void sort_order(hvec<int32_t>& order, const hvec<int64_t>& cnt) {
-  const int64_t n = (int64_t)order.size();
-  int64_t mx = 0;
-  for (int32_t r : order) mx = std::max(mx, cnt[r]);
-  if (mx > (int64_t)16 * n + 4096) {
-    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return cnt[x] > cnt[y]; });
-    return;
-  }
-  hvec<int64_t> start(mx + 2, 0);   // bucket c holds count mx - c (descending)
-  for (int32_t r : order) start[mx - cnt[r] + 1]++;
-  for (int64_t c = 0; c <= mx; ++c) start[c + 1] += start[c];
-  hvec<int32_t> out(n);
-  for (int32_t r : order) out[start[mx - cnt[r]]++] = r;
-  order.swap(out);
-}
 
 // Per-launch algorithmic cost: one GRU application = 2*3H*(DIN+H) + 14H flops.
 double gru_flops(int din, int H) { return 2.0 * 3 * H * (din + H) + 14.0 * H; }
@@ -767,309 +727,117 @@ static bool resident_plan_shape(const ign_plan* p, ResShape* sh) {
   return true;
 }
 
-// dynamic LDS of one graph in a form: union-row states and projected table always; the sum MPs' CSR
-// rows unless CL is off; the path states and step codes in the all-LDS form
-static size_t resident_lds_bytes(int64_t paths, int64_t urows, int64_t msgs, int64_t codes, int form) {
-  const size_t order = (size_t)((urows + 1) & ~int64_t(1)) * sizeof(uint16_t);   // the row order, padded
-  size_t b = (size_t)(urows * kResidentStateStride + (urows + 1) * kResidentTableStride) * sizeof(float) +
-             (size_t)(urows + 1) * sizeof(int32_t) + order;
-  if (form != IGN_RES_PATH_CSR_GLOBAL) b += (size_t)msgs * sizeof(uint16_t);
-  if (form == IGN_RES_ALL_LDS) b += (size_t)paths * kResidentStateStride * sizeof(float) + (size_t)codes * sizeof(uint16_t);
-  return b;
-}
+// ---------------------------------------------------------------------------------------------
+// ign_batch_create's per-MP steps: batch_lower.cpp builds an MP's host tables, these upload them (in
+// a fixed order: the pool hands out its blocks by it) and keep the host copies train.cpp reads.
 
-// a sum MP's destinations with at least this many messages take the segmented sum (sum_seg_kernel,
-// one wave per destination); the others the lane walk of the GRU-step kernel (IGN_SUM_WINDOW=2: every
-// destination segmented).  Per destination, so a graph's rows take the same order alone and in any batch.
-// IGN_SUM_WINDOW=0, the lane walk's A/B switch, refuses a batch with a destination of >= 64 messages
-// (ign_batch_create): a float32 chain that long leaves the fp32 class -- Q-size synth50's nodes as
-// lane walks landed at 4.3x IEEE float32's error (all of them) and 1.8x (those below 128), DESIGN.md §4
-constexpr int64_t kSegMinMessages = 64;
-static int64_t seg_min_messages(const ign_plan* p) { return p->sum_window == 2 ? 0 : kSegMinMessages; }
-
-// per-graph tables of the resident forward, K graphs per workgroup; leaves b->resident false where it
-// does not apply
-static int resident_batch_k(ign_plan* p, ign_batch* b, int K) {
-  ResShape sh;
-  if (!resident_plan_shape(p, &sh)) return IGN_OK;
-  const int path = sh.path, S = sh.n_src;
-  const MPB& ma = b->mp[0];
-  if (b->halo[path] || ma.n_multi || (int)ma.src_off.size() != S) return IGN_OK;
-  for (int s = 0; s < S; ++s)
-    if (b->halo[sh.src_ent[s]]) return IGN_OK;
-  // a workgroup's "graph" is a group of K consecutive graphs of the batch (round 6, IGN_RES_GROUP):
-  // their disjoint union is one graph to the kernel (concatenated local rows, one tile counter, one
-  // set of union-row tiles), so small graphs fill the 16 waves -- GEANT2's 35 path tiles and 5
-  // union-row tiles per graph leave most waves idle in phase A's tail and in phase B.  Every row is
-  // computed as before (tiles of paths sorted by length across the group: the scale caveat above)
-  const int G = (b->G + K - 1) / K;
-  std::vector<int64_t> po_g(G + 1), so_g[kResidentMaxSrc];
-  for (int k = 0; k <= G; ++k) po_g[k] = b->row_off[path][std::min(k * K, b->G)];
-  for (int s = 0; s < S; ++s) {
-    so_g[s].resize(G + 1);
-    for (int k = 0; k <= G; ++k) so_g[s][k] = b->row_off[sh.src_ent[s]][std::min(k * K, b->G)];
-  }
-  const auto& po = po_g;
-  const std::vector<int64_t>* so[kResidentMaxSrc] = {&so_g[0], S > 1 ? &so_g[1] : nullptr};
-  auto Ls = [&](int s, int g) -> int64_t { return s < S ? (*so[s])[g + 1] - (*so[s])[g] : 0; };
-  // union rows: per graph, source entity 0's rows, then entity 1's
-  std::vector<int64_t> uo(G + 1, 0);
-  for (int g = 0; g < G; ++g) {
-    uo[g + 1] = uo[g] + Ls(0, g) + Ls(1, g);
-    if (po[g + 1] - po[g] > 65535 || uo[g + 1] - uo[g] > 65535) return IGN_OK;   // local rows are 16-bit
-    if ((Ls(0, g) + 15) / 16 + (Ls(1, g) + 15) / 16 > kResidentMaxTiles) return IGN_OK;   // B2/B3: two tiles per wave
-  }
-  // the graph of every row (rows are graph-contiguous)
-  auto graph_of = [&](const std::vector<int64_t>& off, int64_t r) {
-    return (int)(std::upper_bound(off.begin(), off.end(), r) - off.begin()) - 1;
-  };
-  auto urow = [&](int s, int g, int64_t row) { return uo[g] + (s ? Ls(0, g) : 0) + (row - (*so[s])[g]); };
-  // the sum MPs: each graph's CSR by local union row, its messages in the MP's order (local path rows)
-  hvec<int32_t> lmsg_ptr((size_t)(uo[G] + G), 0), lmsg_off(G + 1, 0);
-  std::vector<int64_t> nmsg(G, 0);
-  for (int s = 0; s < S; ++s) {
-    const MPB& ms = b->mp[sh.sum_mp[s]];
-    for (int64_t q = 0; q < (int64_t)ms.h_order.size(); ++q) {
-      const int64_t row = ms.h_order[q];
-      const int g = graph_of(*so[s], row);
-      const int32_t cnt = ms.h_msg_ptr[q + 1] - ms.h_msg_ptr[q];
-      lmsg_ptr[urow(s, g, row) + g + 1] = cnt;   // counts, prefix-summed below
-      nmsg[g] += cnt;
-    }
-  }
-  const int64_t seg_min = seg_min_messages(p);
-  hvec<uint16_t> lorder(std::max<int64_t>(uo[G], 1));
-  hvec<int32_t> lnseg(G, 0);
-  int64_t seg_rows = 0;
-  for (int g = 0; g < G; ++g) {
-    lmsg_off[g + 1] = lmsg_off[g] + (int32_t)nmsg[g];
-    int32_t* cp = lmsg_ptr.data() + uo[g] + g;
-    const int64_t U = uo[g + 1] - uo[g];
-    // its local rows by message count, descending (stable): the rows of >= seg_min messages first
-    // (the segmented sums), then the lane walks, long chains first
-    std::vector<int32_t> ord(U);
-    std::iota(ord.begin(), ord.end(), 0);
-    std::stable_sort(ord.begin(), ord.end(), [&](int32_t x, int32_t y) { return cp[x + 1] > cp[y + 1]; });
-    for (int64_t r = 0; r < U; ++r) {
-      lorder[uo[g] + r] = (uint16_t)ord[r];
-      if (cp[ord[r] + 1] >= seg_min) lnseg[g]++;
-    }
-    seg_rows += lnseg[g];
-    for (int64_t r = 0; r < U; ++r) cp[r + 1] += cp[r];
-  }
-  hvec<uint16_t> lmsg_src(std::max<int32_t>(lmsg_off[G], 1));
-  for (int s = 0; s < S; ++s) {
-    const MPB& ms = b->mp[sh.sum_mp[s]];
-    for (int64_t q = 0; q < (int64_t)ms.h_order.size(); ++q) {
-      const int64_t row = ms.h_order[q];
-      const int g = graph_of(*so[s], row);
-      int32_t pos = lmsg_off[g] + lmsg_ptr[urow(s, g, row) + g];
-      for (int32_t m = ms.h_msg_ptr[q]; m < ms.h_msg_ptr[q + 1]; ++m) {
-        const int64_t pr = (int64_t)(ms.h_msg_src[m] & IGN_ROW_MASK) - po[g];
-        if ((ms.h_msg_src[m] >> IGN_SLOT_SHIFT) != 0 || pr < 0 || pr >= po[g + 1] - po[g]) return IGN_OK;
-        lmsg_src[pos++] = (uint16_t)pr;
-      }
-    }
-  }
-  // ordered MP: each graph's positions in the batch's length-sorted order (stable, so still sorted
-  // by length, descending), padded to whole tiles; their step codes as local union rows (U_g: the
-  // hole), then max_len + 8 hole codes (the tile loop reads codes past a row's end)
-  // (positions by graph: a counting sort keyed by a row -> graph table, the batch order kept)
-  const int64_t ND = (int64_t)ma.h_order.size();
-  hvec<int32_t> pstart(G + 1, 0), plist(std::max<int64_t>(ND, 1));
-  {
-    hvec<int32_t> gid(std::max<int64_t>(po[G], 1));
-    for (int g = 0; g < G; ++g)
-      for (int64_t r = po[g]; r < po[g + 1]; ++r) gid[r] = g;
-    for (int64_t i = 0; i < ND; ++i) pstart[gid[ma.h_order[i]] + 1]++;
-    for (int g = 0; g < G; ++g) pstart[g + 1] += pstart[g];
-    hvec<int32_t> fill(pstart.begin(), pstart.end() - 1);
-    for (int64_t i = 0; i < ND; ++i) plist[fill[gid[ma.h_order[i]]]++] = (int32_t)i;
-  }
-  // two passes over the graphs, the second on IGN_BUILD_THREADS threads (the tables are ~10^7
-  // entries for 512 synth50 graphs, ~20 ms on one builder thread): each graph's sizes, their
-  // prefix sums, then every graph fills its own ranges
-  std::vector<int64_t> npad(G), ncode(G), maxl_g(G, 0);
-  hvec<int32_t> ptile_off(G + 1, 0), lcode_off(G + 1, 0);
-  double tile_steps = 0;
-  for (int g = 0; g < G; ++g) {
-    const int64_t n = pstart[g + 1] - pstart[g];
-    npad[g] = (n + 15) / 16 * 16;
-    int64_t codes = 0, maxl = 0;
-    for (int64_t k = pstart[g]; k < pstart[g + 1]; ++k) {
-      const int32_t len = ma.h_len[plist[k]];
-      codes += len;
-      maxl = std::max<int64_t>(maxl, len);
-    }
-    for (int64_t k = pstart[g]; k < pstart[g + 1]; k += 16) tile_steps += ma.h_len[plist[k]];   // a tile's first row is its longest
-    maxl_g[g] = maxl;
-    ncode[g] = codes + maxl + 8;
-    ptile_off[g + 1] = ptile_off[g] + (int32_t)npad[g];
-    if ((int64_t)lcode_off[g] + ncode[g] >= INT32_MAX) return IGN_OK;
-    lcode_off[g + 1] = lcode_off[g] + (int32_t)ncode[g];
-  }
-  hvec<int32_t> hdr((size_t)4 * ptile_off[G]), hsb((size_t)ptile_off[G]);
-  hvec<uint16_t> lcode((size_t)lcode_off[G]);
-  std::atomic<bool> foreign{false};   // a code of another graph's row or a multi-message row: not resident
-  parallel_ranges(G, 16, [&](int64_t g0, int64_t g1) {
-    for (int64_t g = g0; g < g1 && !foreign.load(std::memory_order_relaxed); ++g) {
-      const int64_t U = uo[g + 1] - uo[g];
-      int32_t* h = hdr.data() + (size_t)4 * ptile_off[g];
-      int32_t* hs = hsb.data() + ptile_off[g];
-      uint16_t* lc = lcode.data() + lcode_off[g];
-      int32_t c = 0;   // the graph's next local code
-      for (int64_t k = pstart[g]; k < pstart[g + 1]; ++k) {
-        const int64_t i = plist[k];
-        const int32_t len = ma.h_len[i], sp = ma.h_step_ptr[i];
-        *h++ = (int32_t)(ma.h_order[i] - po[g]);
-        *h++ = len;
-        *hs++ = sp + (int32_t)i;   // the training forward's hs_save rows of position i
-        *h++ = c;
-        const int32_t c_first = c;
-        for (int32_t t = 0; t < len; ++t) {
-          const uint32_t cd = ma.h_step_code[sp + t];
-          uint16_t code = (uint16_t)U;   // the zero row: a hole
-          if (cd < (uint32_t)ma.zero_row) {
-            const int s = S > 1 && (int64_t)cd >= ma.src_off[1] ? 1 : 0;
-            const int64_t lr = (int64_t)cd - ma.src_off[s] - (*so[s])[g];
-            if (lr < 0 || lr >= Ls(s, (int)g)) { foreign = true; return; }
-            code = (uint16_t)((s ? Ls(0, (int)g) : 0) + lr);
-          } else if (cd != (uint32_t)ma.zero_row) {
-            foreign = true;   // a multi-message row (n_multi == 0: unreachable)
-            return;
-          }
-          lc[c++] = code;
-        }
-        *h++ = len > 0 ? lc[c_first] : (int32_t)U;
-      }
-      const int32_t pad = c;
-      for (int64_t q = 0; q < maxl_g[g] + 8; ++q) lc[c++] = (uint16_t)U;
-      for (int64_t k = pstart[g + 1] - pstart[g]; k < npad[g]; ++k) {   // padding: row -1, length 0, hole codes, hs_save's pad row (unwritten)
-        *hs++ = (int32_t)(ma.n_steps + ND);
-        *h++ = -1;
-        *h++ = 0;
-        *h++ = pad;
-        *h++ = (int32_t)U;
-      }
-    }
-  });
-  if (foreign) return IGN_OK;
-  size_t lds[3] = {0, 0, 0};
-  for (int g = 0; g < G; ++g)
-    for (int f = 0; f < 3; ++f)
-      lds[f] = std::max(lds[f], resident_lds_bytes(po[g + 1] - po[g], uo[g + 1] - uo[g], nmsg[g], ncode[g], f));
-  // the workgroups' graphs, longest first (round 6): a launch of more graphs than CUs -- or the second
-  // of two sub-batch launches, whose workgroups take the CUs the first one frees -- is a list
-  // schedule in workgroup order, so longest-first is LPT.  The estimate, in cycles of one workgroup:
-  // phase A's tile-steps over 4 SIMDs at ~1 300 cycles each, phase B's messages at ~6
-  hvec<int32_t> gorder(G);
-  {
-    std::vector<double> cost(G, 0.0);
-    for (int g = 0; g < G; ++g) {
-      double ts = 0;
-      for (int64_t k = pstart[g]; k < pstart[g + 1]; k += 16) ts += ma.h_len[plist[k]];
-      cost[g] = ts * 325.0 + (double)nmsg[g] * 6.0;
-    }
-    std::iota(gorder.begin(), gorder.end(), 0);
-    std::stable_sort(gorder.begin(), gorder.end(), [&](int32_t x, int32_t y) { return cost[x] > cost[y]; });
-  }
-  // every state in LDS where the largest graph's fit, else the path states in global memory, else
-  // also the sum MPs' CSR
-  int form = IGN_RES_ALL_LDS;
-  if (lds[0] > kResidentMaxDynLds || p->resident_path_global) {
-    if (!p->resident_pg) return IGN_OK;
-    form = lds[1] <= kResidentMaxDynLds ? IGN_RES_PATH_GLOBAL : IGN_RES_PATH_CSR_GLOBAL;
-    if (lds[form] > kResidentMaxDynLds) return IGN_OK;
-  }
-  // the training forward's form: path states in global memory always (their versions)
-  b->res_train_form = lds[1] <= kResidentMaxDynLds ? IGN_RES_PATH_GLOBAL : IGN_RES_PATH_CSR_GLOBAL;
-  b->res_train_lds = lds[b->res_train_form];
-  HIP_TRY(resident_prepare_device());
-  std::vector<int64_t> pov(po.begin(), po.end());
+// message networks: per-edge rows and parameters (GM:440-475)
+static int upload_message_nets(ign_batch* b, const MPP& mp, size_t mi, const BatchShape& sh, MPB& mb) {
   int rc;
-  for (int s = 0; s < S; ++s) {
-    std::vector<int64_t> sov(so[s]->begin(), so[s]->end());
-    if ((rc = dev_upload(b, &b->d_res_src_off[s], sov))) return rc;
+  for (int s = 0; s < (int)mp.src.size(); ++s) {
+    const MsgNN& nn = mp.nn[s];
+    if (nn.layers.empty()) continue;
+    const int a = mp.src[s].adjacency;
+    hvec<int32_t> es, ed;
+    if ((rc = lower_edge_rows(mp, mi, s, sh, &es, &ed))) return rc;
+    const int64_t ne = (int64_t)es.size();
+    mb.n_edges[s] = ne;
+    if ((rc = dev_upload(b, &mb.d_edge_src[s], es)) || (rc = dev_upload(b, &mb.d_edge_dst[s], ed))) return rc;
+    if (std::find(nn.inputs.begin(), nn.inputs.end(), (int)IGN_MSG_EDGE_PARAMS) != nn.inputs.end()) {
+      hvec<float> prm(sh.d->adj_params[a], sh.d->adj_params[a] + ne * nn.param_dim);
+      if ((rc = dev_upload(b, &mb.d_edge_params[s], prm))) return rc;
+    }
+    if ((rc = dev_alloc(b, &mb.d_msg_in[s], ne * nn.din_pad))) return rc;
+    HIP_TRY(hipMemsetAsync(mb.d_msg_in[s], 0, ne * nn.din_pad * sizeof(float), upload_stream()));   // zero padding columns
+    for (auto& dp : nn.layers) {
+      float* f = nullptr;
+      if ((rc = dev_alloc(b, &f, ne * dp.out))) return rc;
+      mb.d_msg_layer[s].push_back(f);
+    }
   }
-  if ((rc = dev_upload(b, &b->d_res_path_off, pov)) || (rc = dev_upload(b, &b->d_res_urow_off, uo)) ||
-      (rc = dev_upload(b, &b->d_res_ptile_off, ptile_off)) || (rc = dev_upload(b, &b->d_res_hdr, hdr)) ||
-      (rc = dev_upload(b, &b->d_res_lmsg_off, lmsg_off)) || (rc = dev_upload(b, &b->d_res_lmsg_ptr, lmsg_ptr)) ||
-      (rc = dev_upload(b, &b->d_res_lmsg_src, lmsg_src)) || (rc = dev_upload(b, &b->d_res_lorder, lorder)) ||
-      (rc = dev_upload(b, &b->d_res_lnseg, lnseg)) || (rc = dev_upload(b, &b->d_res_lcode_off, lcode_off)) ||
-      (rc = dev_upload(b, &b->d_res_hsb, hsb)) || (rc = dev_upload(b, &b->d_res_gorder, gorder)) ||
-      (rc = dev_upload(b, &b->d_res_lcode, lcode)))
-    return rc;
-  b->res_lds = lds[form];
-  b->res_form = form;
-  b->res_graphs = G;
-  // the cost model of one launch (ign_batch_resident_info)
-  ign_resident_info_t& ri = b->res_info;
-  ri = ign_resident_info_t{};
-  ri.active = 1;
-  ri.form = form;
-  ri.lds_bytes = (int64_t)lds[form];
-  ri.tile_steps = (int64_t)(tile_steps * p->T);
-  ri.seg_rows = seg_rows;
-  ri.messages = lmsg_off[G];
-  double utiles = 0;
-  for (int g = 0; g < G; ++g) utiles += (double)((Ls(0, g) + 15) / 16 + (Ls(1, g) + 15) / 16);
-  ri.union_tiles = (int64_t)utiles;
-  // compulsory: the features, tile headers, step codes and the sum CSR read once, the final states
-  // written once
-  const int64_t P = b->rows[path], Urows = uo[G];
-  double feat = 4.0 * P * p->ents[path].feature_total;
-  for (int s = 0; s < S; ++s) feat += 4.0 * b->rows[sh.src_ent[s]] * p->ents[sh.src_ent[s]].feature_total;
-  ri.bytes_compulsory = feat + 4.0 * hdr.size() + 2.0 * (double)lcode.size() + 4.0 * lmsg_ptr.size() +
-                        2.0 * lmsg_src.size() + 4.0 * 32 * (P + Urows);
-  // global-path forms: every iteration moves each path row once in and out of the ordered update and
-  // once per message into the sums (rows of 128 B) and reads the step codes again; the CSR-global
-  // form also reads the message rows every iteration
-  if (form != IGN_RES_ALL_LDS)
-    ri.bytes_roundtrip = p->T * (128.0 * (2.0 * P + (double)lmsg_src.size()) + 2.0 * (double)lcode.size());
-  if (form == IGN_RES_PATH_CSR_GLOBAL) ri.bytes_roundtrip += p->T * 2.0 * (double)lmsg_src.size();
-  // B_stage of every MP (MPB::bytes), T times
-  double stage = ma.bytes, mflops = ma.flops;
-  for (int s = 0; s < S; ++s) {
-    stage += b->mp[sh.sum_mp[s]].bytes;
-    mflops += b->mp[sh.sum_mp[s]].flops;
-  }
-  ri.bytes_stage = p->T * stage;
-  // the MPs' FLOPs per iteration plus the ordered MP's input projection of every union row
-  ri.flops = p->T * (mflops + 2.0 * Urows * 32 * 96);
-  // the matrix pipe: phase A's split-fp16 h.U (3 products x 3 gates x 2 tiles per tile-step), the
-  // split-bf16 GRU step (2 x 36 per tile), the projection (3 gates x 2 x 6, T - 1 times), all
-  // 16x16x32; iteration 0's projection on f32 MFMA (3 gates x 2 tiles x 8 k-steps per union tile;
-  // the projection's tiles straddle the entities, ceil(U / 16) per graph)
-  double ptiles = 0;
-  for (int g = 0; g < G; ++g) ptiles += (double)((uo[g + 1] - uo[g] + 15) / 16);
-  ri.mfma_bf16 = (p->T * (tile_steps * 18.0 + utiles * 72.0) + (p->T - 1) * utiles * 36.0) * kMfmaBf16Flops;
-  ri.mfma_f32 = ptiles * 48.0 * kMfmaF32Flops;
-  ri.workgroups = G;
-  ri.graphs_per_workgroup = K;
-  b->resident = true;
   return IGN_OK;
 }
 
-// ---------------------------------------------------------------------------------------------
-// ign_batch_create's message lists for one (graph, source) of a plain MP (no interleave, attention or
-// axis-2 concat), T the desc's index type: false when an index is out of range (the caller's checked
-// loop then reports the first one)
-extern "C++" template <class T>
-static bool plain_messages(const T* __restrict as, const T* __restrict ad, const T* __restrict aq, int64_t n,
-                           int64_t nsrc, int64_t ndst, int64_t rd, int64_t rs, int64_t slot_off, uint32_t sb, bool net,
-                           int64_t e0, hvec<int32_t>& mdst, hvec<int32_t>& mpos, hvec<uint32_t>& mcode,
-                           int64_t* __restrict fl) {
-  bool bad = false;
-  for (int64_t k = 0; k < n; ++k) {
-    const int64_t si = as[k], di = ad[k];
-    bad |= (uint64_t)si >= (uint64_t)nsrc || (uint64_t)di >= (uint64_t)ndst;
-    const int64_t dc = bad ? 0 : di;   // (no store outside the graph's flen range before the report)
-    mdst.push_back((int32_t)(rd + dc));
-    mpos.push_back((int32_t)(slot_off + (int64_t)aq[k]));
-    mcode.push_back(sb | (uint32_t)(net ? e0 + k : rs + si));
-    fl[dc] += 1;
+static int build_ordered_mp(ign_batch* b, const MPP& mp, int H, const BatchShape& sh, const MsgLists& ml, BuildMarks& bm,
+                            MPB& mb) {
+  OrderedTables t;
+  int rc = lower_ordered(mp, H, sh, ml, bm, &t);
+  if (rc) return rc;
+  mb.src_off = std::move(t.src_off);
+  mb.src_rows = std::move(t.src_rows);
+  mb.zero_row = t.zero_row;
+  mb.n_multi = t.n_multi;
+  mb.wave_steps = t.wave_steps;
+  mb.n_steps = t.n_steps;
+  mb.n_msgs = t.n_msgs;
+  mb.flops = t.flops;
+  mb.bytes = t.bytes;
+  if ((rc = dev_upload(b, &mb.d_seq_hdr, t.hdr)) || (rc = dev_upload(b, &mb.d_order, t.order)) ||
+      (rc = dev_upload(b, &mb.d_len, t.len)) || (rc = dev_upload(b, &mb.d_step_ptr, t.step_ptr)) ||
+      (rc = dev_upload(b, &mb.d_step_code, t.step_code)) || (rc = dev_upload(b, &mb.d_multi_ptr, t.multi_ptr)) ||
+      (rc = dev_upload(b, &mb.d_multi_rows, t.multi_rows)))
+    return rc;
+  mb.h_order = std::move(t.order);
+  mb.h_len = std::move(t.len);
+  mb.h_step_ptr = std::move(t.step_ptr);
+  mb.h_step_code = std::move(t.step_code);
+  mb.h_multi_ptr = std::move(t.multi_ptr);
+  mb.h_multi_rows = std::move(t.multi_rows);
+  const int64_t tfloats = (mb.zero_row + 1 + mb.n_multi) * 3LL * H;
+  if ((rc = dev_alloc(b, &mb.d_table, tfloats))) return rc;
+  HIP_TRY(hipMemsetAsync(mb.d_table, 0, (tfloats + 256) * sizeof(float), upload_stream()));   // zero row stays zero
+  b->gru_steps += mb.n_steps * b->plan->T;
+  bm.mark("uploads");
+  return IGN_OK;
+}
+
+static int build_sum_mp(ign_batch* b, const MPP& mp, size_t mi, int H, const BatchShape& sh, const MsgLists& ml,
+                        BuildMarks& bm, MPB& mb) {
+  const int64_t ND = mb.n_dst;
+  const int DIN = mp.din;
+  int rc;
+  SumCsr csr;
+  lower_sum_csr(mp, sh, ml, bm, &csr);
+  mb.n_interior = csr.n_interior;
+  if (mp.aggr == IGN_AGGR_ATTENTION) {
+    AttnTables at;
+    lower_attention(mp, sh, ml, csr, &at);
+    mb.n_groups = at.n_groups;
+    mb.n_cells = at.n_cells;
+    if ((rc = dev_upload(b, &mb.d_group_ptr, at.group_ptr)) || (rc = dev_upload(b, &mb.d_group_empty, at.group_empty)) ||
+        (rc = dev_upload(b, &mb.d_cell_dst, at.cell_dst)) || (rc = dev_upload(b, &mb.d_cell_ptr, at.cell_ptr)) ||
+        (rc = dev_upload(b, &mb.d_cell_msgs, at.cell_msgs)))
+      return rc;
+    if ((rc = dev_alloc(b, &mb.d_msg_w, (int64_t)ml.mdst.size())) || (rc = dev_alloc(b, &mb.d_ecell, mb.n_cells)) ||
+        (rc = dev_alloc(b, &mb.d_s_dst, ND)))
+      return rc;
+    for (int s = 0; s < (int)mp.src.size(); ++s)
+      if ((rc = dev_alloc(b, &mb.d_s_src[s], source_rows(mp, s, sh)))) return rc;
   }
-  return !bad;
+  bm.mark("csr");
+  SumAgg ag;
+  if ((rc = lower_sum_agg(mp, mi, b->plan->sum_window, sh, ml, csr, &ag))) return rc;
+  mb.n_win_wg = ag.n_win_wg;
+  mb.sum_seg = ag.seg;
+  mb.n_seg = ag.n_seg;
+  if (ag.window && ((rc = dev_upload(b, &mb.d_win_wg, ag.wg)) || (rc = dev_upload(b, &mb.d_win_dst, ag.wdst)) ||
+                    (rc = dev_upload(b, &mb.d_win_ptr, ag.wptr)) || (rc = dev_upload(b, &mb.d_win_src, ag.wsrc))))
+    return rc;
+  if ((ag.window || ag.seg) &&
+      ((rc = dev_upload(b, &mb.d_id_ptr, ag.id_ptr)) || (rc = dev_upload(b, &mb.d_id_src, ag.id_src)) ||
+       (rc = dev_alloc(b, &mb.d_xsum, std::max<int64_t>(ND, 1) * DIN))))
+    return rc;
+  mb.n_msgs = (int64_t)csr.msrc.size();
+  if ((rc = dev_upload(b, &mb.d_order, csr.order)) || (rc = dev_upload(b, &mb.d_msg_ptr, csr.ptr)) ||
+      (rc = dev_upload(b, &mb.d_msg_src, csr.msrc)))
+    return rc;
+  mb.h_order = std::move(csr.order);
+  mb.h_msg_ptr = std::move(csr.ptr);
+  mb.h_msg_src = std::move(csr.msrc);
+  mb.flops = (double)ND * gru_flops(DIN, H) + (double)mb.n_msgs * DIN;
+  mb.bytes = (double)mb.n_msgs * (4.0 * DIN + 4) + (double)ND * (8.0 * H + 8);
+  b->gru_steps += ND * b->plan->T;
+  return IGN_OK;
 }
 
 int ign_batch_create(ign_plan* p, const ign_batch_desc* d, ign_batch** out) {
@@ -1085,53 +853,11 @@ int ign_batch_create(ign_plan* p, const ign_batch_desc* d, ign_batch** out) {
   b->plan = p;
   b->pool = p->pool;
   b->G = G;
-  b->rows.assign(E, 0);
-  b->row_off.assign(E, std::vector<int64_t>(G + 1, 0));
-  for (int e = 0; e < E; ++e) {
-    for (int g = 0; g < G; ++g) {
-      int64_t n = d->num_nodes[(int64_t)g * E + e];
-      if (n < 0) return fail(IGN_ERR_INVALID, "graph %d: negative num_ for entity %d", g, e);
-      b->row_off[e][g + 1] = b->row_off[e][g] + n;
-    }
-    b->rows[e] = b->row_off[e][G];
-  }
-  b->halo.assign(E, 0);
-  if (d->halo_rows) {
-    // a partition holds only its own destinations: the attention softmax normalises over all of the
-    // graph's destinations per position (AUX:327-336), and the sorted updates pad per graph
-    // (GM:477-543).  Sum / convolution MPs, with or without message networks, are destination-local.
-    for (auto& mp : p->mps)
-      if (mp.aggr == IGN_AGGR_ATTENTION || mp.sorted)
-        return fail(IGN_ERR_UNSUPPORTED, "edge-cut partitions support sum and convolution MPs only (attention "
-                    "normalises over the whole graph, AUX:327-336; ordered updates pad per graph, GM:477-543)");
-    for (int e = 0; e < E; ++e) {
-      if (d->halo_rows[e] < 0) return fail(IGN_ERR_INVALID, "entity %d: negative halo_rows", e);
-      b->halo[e] = d->halo_rows[e];
-      if (b->halo[e] && G != 1) return fail(IGN_ERR_INVALID, "halo rows need num_graphs == 1 (one partition)");
-    }
-  }
-  for (int e = 0; e < E; ++e)
-    if (b->rows[e] + b->halo[e] >= (int64_t)IGN_ROW_MASK) return fail(IGN_ERR_UNSUPPORTED, "entity %d: too many rows", e);
-  // edge offsets per adjacency
-  std::vector<hvec<int64_t>> eoff(p->n_adj, hvec<int64_t>(G + 1, 0));
-  for (int a = 0; a < p->n_adj; ++a)
-    for (int g = 0; g < G; ++g) {
-      int64_t n = d->adj_edges[(int64_t)g * p->n_adj + a];
-      if (n < 0) return fail(IGN_ERR_INVALID, "negative edge count");
-      eoff[a][g + 1] = eoff[a][g] + n;
-    }
-  std::vector<IdxArr> asrc(p->n_adj), adst(p->n_adj), aseq(p->n_adj), ilx(p->n_il);   // ABI 13: int32 or int64
-  if (d->index_bytes != 0 && d->index_bytes != 4 && d->index_bytes != 8)
-    return fail(IGN_ERR_INVALID, "index_bytes %d (0 / 8: int64 index arrays, 4: int32)", (int)d->index_bytes);
-  for (int a = 0; a < p->n_adj; ++a) {
-    asrc[a] = IdxArr(d->adj_src[a], d->index_bytes);
-    adst[a] = IdxArr(d->adj_dst[a], d->index_bytes);
-    aseq[a] = IdxArr(d->adj_seq[a], d->index_bytes);
-  }
-  for (int i = 0; i < p->n_il; ++i) ilx[i] = IdxArr(d->interleave_idx[i], d->index_bytes);
-  std::vector<hvec<int64_t>> ioff(p->n_il, hvec<int64_t>(G + 1, 0));
-  for (int i = 0; i < p->n_il; ++i)
-    for (int g = 0; g < G; ++g) ioff[i][g + 1] = ioff[i][g] + d->interleave_len[(int64_t)g * p->n_il + i];
+  BatchShape sh;
+  if ((rc = lower_batch_shape(E, p->n_adj, p->n_il, p->mps, d, &sh))) return rc;
+  b->rows = sh.rows;
+  b->halo = sh.halo;
+  b->row_off = sh.row_off;
 
   // features + state buffers
   b->d_feat.assign(E, nullptr);
@@ -1152,7 +878,8 @@ int ign_batch_create(ign_plan* p, const ign_batch_desc* d, ign_batch** out) {
     }
   }
 
-  // per-MP CSR / step tables
+  // per-MP CSR / step tables: each MP is lowered on the host (batch_lower.cpp), then uploaded, so
+  // its staged copies run under the next MP's host work
   static const bool build_prof = env_flag("IGN_BUILD_PROF", false);
   std::vector<double> t_mp;   // IGN_BUILD_PROF: the time up to the end of each MP's tables
   const double t_mp0 = build_prof ? now_ms() : 0.0;
@@ -1160,471 +887,18 @@ int ign_batch_create(ign_plan* p, const ign_batch_desc* d, ign_batch** out) {
   for (size_t mi = 0; mi < p->mps.size(); ++mi) {
     if (build_prof && mi > 0) t_mp.push_back(now_ms());
     const MPP& mp = p->mps[mi];
-    const int S = (int)mp.src.size();
-    const int dst = mp.dst;
-    const int64_t ND = b->rows[dst];
     MPB mb;
     mb.sorted = mp.sorted;
-    mb.n_dst = ND;
-    // messages: (dst row, position, code), in source order then edge order
-    hvec<int32_t> mdst;   // rows < IGN_ROW_MASK
-    hvec<int32_t> mpos;   // < total_slots (checked)
-    hvec<uint32_t> mcode;
-    int64_t tot = 0;
-    for (int s = 0; s < S; ++s) tot += eoff[mp.src[s].adjacency][G];
-    mdst.reserve(tot);
-    mpos.reserve(tot);
-    mcode.reserve(tot);
-    hvec<int64_t> flen(ND, 0);
-    for (int g = 0; g < G; ++g) {
-      int64_t slot_off = 0;  // sum of Lmax of previous sources in this graph (GM:533)
-      hvec<int64_t> ilflat;
-      if (mp.aggr == IGN_AGGR_INTERLEAVE) {
-        // tf.stack([indices_a, indices_b]) then reshape [-1,1] (GM:518, AUX:433)
-        int64_t len0 = -1;
-        for (int s = 0; s < S; ++s) {
-          int il = mp.src[s].interleave;
-          int64_t n = ioff[il][g + 1] - ioff[il][g];
-          if (len0 >= 0 && n != len0)
-            return fail(IGN_ERR_INVALID, "graph %d: interleave index lists have different lengths (%lld vs %lld;"
-                        " tf.stack fails, GM:518)", g, (long long)len0, (long long)n);
-          len0 = n;
-          for (int64_t k = ioff[il][g]; k < ioff[il][g + 1]; ++k) ilflat.push_back(ilx[il][k]);
-        }
-      }
-      int64_t total_slots = 0;
-      hvec<int64_t> lmax(S, 0);
-      for (int s = 0; s < S; ++s) {
-        const int a = mp.src[s].adjacency;
-        const int64_t e0 = eoff[a][g], e1 = eoff[a][g + 1];
-        if (e1 == e0)
-          return fail(IGN_ERR_INVALID, "graph %d: adjacency slot %d has no edges (the reference's scatter_nd shape"
-                      " max(seq)+1 is undefined, GM:484-490)", g, a);
-        int64_t mx = -1;
-        for (int64_t k = e0; k < e1; ++k) {
-          int64_t sq = aseq[a][k];
-          if (sq < 0) return fail(IGN_ERR_INVALID, "graph %d: negative seq value", g);
-          mx = std::max(mx, sq);
-        }
-        lmax[s] = mx + 1;
-        total_slots += lmax[s];
-      }
-      if (total_slots >= INT32_MAX) return fail(IGN_ERR_UNSUPPORTED, "graph %d: sequences too long", g);
-      if (mp.feature_concat) {   // tf.concat on axis 2 needs every source's [N, Lmax] to match
-        for (int s = 1; s < S; ++s)
-          if (lmax[s] != lmax[0])
-            return fail(IGN_ERR_INVALID, "graph %d: concat on axis 2 of sequences of length %lld and %lld "
-                        "(ConcatOp dimension mismatch, GM:503)", g, (long long)lmax[0], (long long)lmax[s]);
-        total_slots = lmax[0];
-      }
-      if (mp.aggr == IGN_AGGR_INTERLEAVE && (int64_t)ilflat.size() != total_slots)
-        return fail(IGN_ERR_INVALID, "graph %d: interleave indices cover %lld slots but the messages need %lld"
-                    " (scatter_nd shape mismatch, AUX:435)", g, (long long)ilflat.size(), (long long)total_slots);
-      for (int s = 0; s < S; ++s) {
-        const int a = mp.src[s].adjacency;
-        const int se = mp.src[s].entity;
-        const int64_t e0 = eoff[a][g], e1 = eoff[a][g + 1];
-        const int64_t nsrc = b->row_off[se][g + 1] - b->row_off[se][g] + b->halo[se];   // halo: G == 1
-        const int64_t ndst = b->row_off[dst][g + 1] - b->row_off[dst][g];
-        // attention: comb_seq of source s > 0 is seq + that source's own in-degree (GM:539-540)
-        hvec<int64_t> lens_s;
-        if (mp.aggr == IGN_AGGR_ATTENTION && s > 0) {
-          lens_s.assign(ndst, 0);
-          for (int64_t k = e0; k < e1; ++k) {
-            const int64_t di = adst[a][k];
-            if (di >= 0 && di < ndst) lens_s[di]++;
-          }
-        }
-        if (mp.aggr != IGN_AGGR_INTERLEAVE && mp.aggr != IGN_AGGR_ATTENTION && !mp.feature_concat) {
-          // the common case (sum, ordered, convolution; no axis-2 concat): the loop below without its
-          // per-message branches on the MP's kind, whose fields it reloaded on every message (the
-          // stores may alias them), reading the desc's own index width.  An index out of range
-          // reruns the checked loop, which reports the first one.
-          const int64_t rd = b->row_off[dst][g], rs = b->row_off[se][g];
-          const uint32_t sb = (uint32_t)s << IGN_SLOT_SHIFT;
-          const bool net = !mp.nn[s].layers.empty();
-          const bool ok = d->index_bytes == 4
-              ? plain_messages(static_cast<const int32_t*>(asrc[a].p) + e0, static_cast<const int32_t*>(adst[a].p) + e0,
-                               static_cast<const int32_t*>(aseq[a].p) + e0, e1 - e0, nsrc, ndst, rd, rs, slot_off, sb,
-                               net, e0, mdst, mpos, mcode, flen.data() + rd)
-              : plain_messages(d->adj_src[a] + e0, d->adj_dst[a] + e0, d->adj_seq[a] + e0, e1 - e0, nsrc, ndst, rd, rs,
-                               slot_off, sb, net, e0, mdst, mpos, mcode, flen.data() + rd);
-          if (ok) {
-            slot_off += lmax[s];
-            continue;
-          }
-        }
-        for (int64_t k = e0; k < e1; ++k) {
-          int64_t si = asrc[a][k], di = adst[a][k], sq = aseq[a][k];
-          if (si < 0 || si >= nsrc) return fail(IGN_ERR_INVALID, "graph %d: src index %lld out of range [0,%lld)", g, (long long)si, (long long)nsrc);
-          if (di < 0 || di >= ndst) return fail(IGN_ERR_INVALID, "graph %d: dst index %lld out of range [0,%lld)", g, (long long)di, (long long)ndst);
-          int64_t pos = slot_off + sq;
-          if (mp.aggr == IGN_AGGR_INTERLEAVE) {
-            pos = ilflat[pos];
-            if (pos < 0 || pos >= total_slots)
-              return fail(IGN_ERR_INVALID, "graph %d: interleave index %lld outside [0,%lld) (scatter_nd, AUX:435)",
-                          g, (long long)pos, (long long)total_slots);
-          }
-          if (mp.aggr == IGN_AGGR_ATTENTION) pos = sq + (s > 0 ? lens_s[di] : 0);
-          if (mp.feature_concat) pos = sq;   // all sources share the positions (axis-2 concat)
-          int64_t drow = b->row_off[dst][g] + di;
-          mdst.push_back(drow);
-          mpos.push_back(pos);
-          // a message network's messages live per edge: the code addresses the edge (GM:440-475)
-          const int64_t mrow = mp.nn[s].layers.empty() ? b->row_off[se][g] + si : k;
-          mcode.push_back(((uint32_t)s << IGN_SLOT_SHIFT) | (uint32_t)mrow);
-          // final_len = sum of lens over sources (GM:505/519/543); axis-2 concat keeps the first
-          // source's lens (GM:503-505)
-          if (!mp.feature_concat || s == 0) flen[drow] += 1;
-        }
-        slot_off += lmax[s];
-      }
-      if (mp.sorted) {
-        // gather_nd(outputs, [d, final_len-1]) needs final_len <= sum of Lmax (AUX:793-795)
-        int64_t max_flen = 0;
-        for (int64_t r = b->row_off[dst][g]; r < b->row_off[dst][g + 1]; ++r) {
-          if (flen[r] > total_slots)
-            return fail(IGN_ERR_INVALID, "graph %d: destination row %lld has final_len %lld > %lld padded slots"
-                        " (gather_nd out of range, AUX:793-795)", g, (long long)(r - b->row_off[dst][g]),
-                        (long long)flen[r], (long long)total_slots);
-          max_flen = std::max(max_flen, flen[r]);
-        }
-        // RNN(mask=tf.sequence_mask(final_len)) (AUX:785-790): the mask is max(final_len) wide, and
-        // K.rnn unstacks it into a TensorList that its while loop reads at every one of the
-        // total_slots time steps -> InvalidArgument at step max(final_len) when that is narrower
-        // ("masked-RNN time length")
-        if (b->row_off[dst][g + 1] > b->row_off[dst][g] && max_flen < total_slots)
-          return fail(IGN_ERR_INVALID, "graph %d: sequence_mask(final_len) is %lld steps wide but the padded "
-                      "sequence has %lld (K.rnn reads the mask TensorList past its end, AUX:785-790)", g,
-                      (long long)max_flen, (long long)total_slots);
-      }
-    }
-    for (int s = 0; s < S; ++s) {   // message networks: per-edge rows and parameters (GM:440-475)
-      const MsgNN& nn = mp.nn[s];
-      if (nn.layers.empty()) continue;
-      const int a = mp.src[s].adjacency, se = mp.src[s].entity;
-      const int64_t ne = eoff[a][G];
-      if (ne >= (int64_t)IGN_ROW_MASK) return fail(IGN_ERR_UNSUPPORTED, "too many edges for a message network");
-      hvec<int32_t> es(ne), ed(ne);
-      for (int g = 0; g < G; ++g)
-        for (int64_t k = eoff[a][g]; k < eoff[a][g + 1]; ++k) {
-          es[k] = (int32_t)(b->row_off[se][g] + asrc[a][k]);
-          ed[k] = (int32_t)(b->row_off[dst][g] + adst[a][k]);
-        }
-      mb.n_edges[s] = ne;
-      if ((rc = dev_upload(b.get(), &mb.d_edge_src[s], es)) || (rc = dev_upload(b.get(), &mb.d_edge_dst[s], ed))) return rc;
-      if (std::find(nn.inputs.begin(), nn.inputs.end(), (int)IGN_MSG_EDGE_PARAMS) != nn.inputs.end()) {
-        if (!d->adj_params || !d->adj_params[a])
-          return fail(IGN_ERR_INVALID, "message network of mp %zu reads edge_params but params_<adj> is missing", mi);
-        hvec<float> prm(d->adj_params[a], d->adj_params[a] + ne * nn.param_dim);
-        if ((rc = dev_upload(b.get(), &mb.d_edge_params[s], prm))) return rc;
-      }
-      if ((rc = dev_alloc(b.get(), &mb.d_msg_in[s], ne * nn.din_pad))) return rc;
-      HIP_TRY(hipMemsetAsync(mb.d_msg_in[s], 0, ne * nn.din_pad * sizeof(float), upload_stream()));   // zero padding columns
-      for (auto& dp : nn.layers) {
-        float* f = nullptr;
-        if ((rc = dev_alloc(b.get(), &f, ne * dp.out))) return rc;
-        mb.d_msg_layer[s].push_back(f);
-      }
-    }
+    mb.n_dst = b->rows[mp.dst];
+    MsgLists ml;
+    if ((rc = lower_messages(mp, sh, &ml)) || (rc = upload_message_nets(b.get(), mp, mi, sh, mb))) return rc;
     bm.mark("messages");
-    mb.edges = tot;
-    b->edges_per_forward += tot * p->T;
-    const CellP& cp = p->cells[mp.cell];
-    const int H = cp.H, DIN = mp.din;
-
-    hvec<int32_t> order(ND);
-    std::iota(order.begin(), order.end(), 0);
-    if (mp.sorted) {
-      for (int64_t r = 0; r < ND; ++r)
-        if (flen[r] == 0)   // AUX:793-795: gather_nd(outputs, [d, final_len-1]) with -1
-          return fail(IGN_ERR_INVALID, "destination row %lld receives no message: the reference's sorted update"
-                      " gathers position -1 (AUX:793-795)", (long long)r);
-      sort_order(order, flen);
-      bm.mark("sort");
-      // combined projected table: source s occupies rows [src_off[s], src_off[s] + rows_s)
-      int64_t trow = 0;
-      for (int s = 0; s < S; ++s) {
-        mb.src_off.push_back(trow);
-        const int se = mp.src[s].entity;
-        const int64_t rows_s = mp.nn[s].layers.empty() ? b->rows[se] + b->halo[se] : eoff[mp.src[s].adjacency][G];
-        mb.src_rows.push_back(rows_s);
-        trow += rows_s;
-      }
-      mb.zero_row = trow;
-      auto table_row = [&](uint32_t code) -> int64_t {
-        return mb.src_off[code >> IGN_SLOT_SHIFT] + (code & IGN_ROW_MASK);
-      };
-      // Step t of the destination at sorted position i is slot step_ptr[i] + t.  A slot holds its
-      // message's table row, the zero row (a hole), or a pre-summed "multi" row when several
-      // messages share the position (scatter_nd adds them); messages at positions >= final_len
-      // are dropped (the masked RNN never reads them).  Multi rows are numbered in slot order and
-      // list their messages in message order.  maxL + 8 trailing zero-row slots: the kernels read
-      // codes past a row's end unconditionally.
-      hvec<int32_t> len(ND), step_ptr(ND), multi_ptr(1, 0);
-      hvec<int32_t> where(ND);
-      int64_t steps = 0, maxL = 0;
-      for (int64_t i = 0; i < ND; ++i) {
-        const int64_t r = order[i];
-        where[r] = (int32_t)i;
-        len[i] = (int32_t)flen[r];
-        step_ptr[i] = (int32_t)steps;
-        maxL = std::max(maxL, flen[r]);
-        steps += flen[r];
-      }
-      if (steps >= INT32_MAX) return fail(IGN_ERR_UNSUPPORTED, "MP too large");
-      hvec<uint32_t> scode((size_t)(steps + maxL + 8), (uint32_t)mb.zero_row);
-      hvec<int32_t> slot_of(mdst.size(), -1), scount(steps, 0);
-      int64_t n_msgs = 0;
-      for (size_t k = 0; k < mdst.size(); ++k) {
-        const int64_t r = mdst[k];
-        if (mpos[k] >= flen[r]) continue;
-        const int64_t slot = step_ptr[where[r]] + mpos[k];
-        slot_of[k] = (int32_t)slot;
-        if (++scount[slot] == 1) scode[slot] = (uint32_t)table_row(mcode[k]);
-        ++n_msgs;
-      }
-      hvec<uint32_t> multi_rows;
-      hvec<int32_t> multi_of(steps, -1);
-      for (int64_t slot = 0; slot < steps; ++slot)
-        if (scount[slot] > 1) {
-          multi_of[slot] = (int32_t)mb.n_multi;
-          scode[slot] = (uint32_t)(mb.zero_row + 1 + mb.n_multi);
-          multi_ptr.push_back(multi_ptr.back() + scount[slot]);
-          mb.n_multi++;
-        }
-      if (mb.n_multi) {
-        multi_rows.resize(multi_ptr.back());
-        hvec<int32_t> fill(multi_ptr.begin(), multi_ptr.end() - 1);
-        for (size_t k = 0; k < mdst.size(); ++k)
-          if (slot_of[k] >= 0 && multi_of[slot_of[k]] >= 0)
-            multi_rows[fill[multi_of[slot_of[k]]]++] = (uint32_t)table_row(mcode[k]);
-      }
-      bm.mark("slots");
-      for (int64_t i = 0; i < ND; i += 16) mb.wave_steps += len[i];   // sorted: a tile's first row is its longest
-      {   // the ordered update's tile headers: one 16-B load per position, no dependent code load
-        const int64_t NDp = (ND + 15) / 16 * 16;
-        hvec<int32_t> hdr((size_t)(4 * NDp));
-        for (int64_t i = 0; i < NDp; ++i) {
-          const bool v = i < ND;
-          hdr[4 * i] = v ? order[i] : 0;
-          hdr[4 * i + 1] = v ? len[i] : 0;
-          hdr[4 * i + 2] = v ? step_ptr[i] : (int32_t)steps;
-          hdr[4 * i + 3] = (int32_t)scode[v ? step_ptr[i] : steps];
-        }
-        if ((rc = dev_upload(b.get(), &mb.d_seq_hdr, hdr))) return rc;
-      }
-      bm.mark("headers");
-      if (mb.zero_row + 1 + mb.n_multi >= (int64_t)UINT32_MAX) return fail(IGN_ERR_UNSUPPORTED, "MP too large");
-      mb.n_steps = steps;
-      mb.n_msgs = n_msgs;
-      if ((rc = dev_upload(b.get(), &mb.d_order, order))) return rc;
-      if ((rc = dev_upload(b.get(), &mb.d_len, len))) return rc;
-      if ((rc = dev_upload(b.get(), &mb.d_step_ptr, step_ptr))) return rc;
-      if ((rc = dev_upload(b.get(), &mb.d_step_code, scode))) return rc;
-      if ((rc = dev_upload(b.get(), &mb.d_multi_ptr, multi_ptr))) return rc;
-      if ((rc = dev_upload(b.get(), &mb.d_multi_rows, multi_rows))) return rc;
-      mb.h_order = std::move(order);
-      mb.h_len = std::move(len);
-      mb.h_step_ptr = std::move(step_ptr);
-      mb.h_step_code = std::move(scode);
-      mb.h_multi_ptr = std::move(multi_ptr);
-      mb.h_multi_rows = std::move(multi_rows);
-      const int64_t tfloats = (mb.zero_row + 1 + mb.n_multi) * 3LL * H;
-      if ((rc = dev_alloc(b.get(), &mb.d_table, tfloats))) return rc;
-      HIP_TRY(hipMemsetAsync(mb.d_table, 0, (tfloats + 256) * sizeof(float), upload_stream()));   // zero row stays zero
-      // per launch of the recurrence: h.U + gates per step; one projected row (3H floats) per step
-      // FLOPs executed (fp32-equivalent): h.U + gates per step (x.W is hoisted into project);
-      // bytes per SURVEY §8d, B_stage = E (4 + 4H) + 2 N_d 4H + 4 (N_d + 1): one message row and
-      // code per step, the state read and written once per destination
-      mb.flops = (double)steps * (2.0 * H * 3 * H + 14.0 * H);
-      mb.bytes = (double)steps * (4.0 * H + 4) + (double)ND * 8.0 * H + 4.0 * (ND + 1);
-      b->gru_steps += steps * p->T;
-      bm.mark("uploads");
-    } else {
-      sort_order(order, flen);
-      // edge-cut partitions: destinations reading a halo row go last (they wait for the exchange)
-      // (a message network's codes address edges, and its per-edge pass reads every source row
-      // before any destination runs: no interior destinations then)
-      bool nets = false;
-      for (auto& nn : mp.nn) nets = nets || !nn.layers.empty();
-      bool halo = false;
-      for (auto& sd : mp.src) halo = halo || b->halo[sd.entity] > 0;
-      hvec<char> bnd(ND, nets && halo ? 1 : 0);
-      for (size_t k = 0; k < mdst.size() && !nets; ++k) {
-        const uint32_t c = mcode[k];
-        const int se = mp.src[c >> IGN_SLOT_SHIFT].entity;
-        if ((int64_t)(c & IGN_ROW_MASK) >= b->rows[se]) bnd[mdst[k]] = 1;
-      }
-      std::stable_partition(order.begin(), order.end(), [&](int32_t r) { return !bnd[r]; });
-      bm.mark("sort");
-      mb.n_interior = std::count(bnd.begin(), bnd.end(), 0);
-      hvec<int32_t> where(ND);
-      for (int64_t i = 0; i < ND; ++i) where[order[i]] = (int32_t)i;
-      hvec<int32_t> ptr(ND + 1, 0);
-      for (size_t k = 0; k < mdst.size(); ++k) ptr[where[mdst[k]] + 1]++;
-      for (int64_t i = 0; i < ND; ++i) ptr[i + 1] += ptr[i];
-      hvec<uint32_t> msrc(mdst.size());
-      hvec<int32_t> csr_pos(mp.aggr == IGN_AGGR_ATTENTION ? mdst.size() : 0);   // message -> CSR slot
-      {
-        hvec<int32_t> fill(ptr.begin(), ptr.end() - 1);
-        for (size_t k = 0; k < mdst.size(); ++k) {
-          const int32_t q = fill[where[mdst[k]]]++;
-          if (!csr_pos.empty()) csr_pos[k] = q;
-          msrc[q] = mcode[k];
-        }
-      }
-      if (mp.aggr == IGN_AGGR_ATTENTION) {
-        // dense (destination, position) cells of the scatter_nd (AUX:327-331); duplicates share one
-        // cell.  Groups = (graph, position): the softmax runs over a graph's destinations (AUX:336)
-        hvec<int> gof(ND);
-        for (int g = 0; g < G; ++g)
-          for (int64_t r = b->row_off[dst][g]; r < b->row_off[dst][g + 1]; ++r) gof[r] = g;
-        hvec<int64_t> key(mdst.size());
-        hvec<int64_t> gmax(G, 0);
-        for (size_t k = 0; k < mdst.size(); ++k) gmax[gof[mdst[k]]] = std::max<int64_t>(gmax[gof[mdst[k]]], mpos[k] + 1);
-        hvec<int64_t> gbase(G + 1, 0);   // group index base per graph
-        for (int g = 0; g < G; ++g) gbase[g + 1] = gbase[g] + gmax[g];
-        hvec<size_t> ord(mdst.size());
-        std::iota(ord.begin(), ord.end(), 0);
-        std::stable_sort(ord.begin(), ord.end(), [&](size_t x, size_t y) {
-          const int64_t gx = gbase[gof[mdst[x]]] + mpos[x], gy = gbase[gof[mdst[y]]] + mpos[y];
-          return gx != gy ? gx < gy : mdst[x] < mdst[y];
-        });
-        hvec<int32_t> group_ptr(gbase[G] + 1, 0), group_empty(gbase[G], 0), cell_dst, cell_ptr(1, 0), cell_msgs;
-        for (size_t q = 0; q < ord.size();) {
-          const size_t k = ord[q];
-          const int64_t grp = gbase[gof[mdst[k]]] + mpos[k];
-          size_t q2 = q;
-          while (q2 < ord.size() && mdst[ord[q2]] == mdst[k] && mpos[ord[q2]] == mpos[k]) cell_msgs.push_back(csr_pos[ord[q2++]]);
-          cell_dst.push_back((int32_t)mdst[k]);
-          cell_ptr.push_back((int32_t)cell_msgs.size());
-          group_ptr[grp + 1]++;
-          q = q2;
-        }
-        for (int64_t q = 0; q < gbase[G]; ++q) group_ptr[q + 1] += group_ptr[q];
-        for (int g = 0; g < G; ++g)
-          for (int64_t pq = 0; pq < gmax[g]; ++pq) {
-            const int64_t grp = gbase[g] + pq;
-            group_empty[grp] = (int32_t)((b->row_off[dst][g + 1] - b->row_off[dst][g]) - (group_ptr[grp + 1] - group_ptr[grp]));
-          }
-        mb.n_groups = gbase[G];
-        mb.n_cells = (int64_t)cell_dst.size();
-        if ((rc = dev_upload(b.get(), &mb.d_group_ptr, group_ptr)) || (rc = dev_upload(b.get(), &mb.d_group_empty, group_empty)) ||
-            (rc = dev_upload(b.get(), &mb.d_cell_dst, cell_dst)) || (rc = dev_upload(b.get(), &mb.d_cell_ptr, cell_ptr)) ||
-            (rc = dev_upload(b.get(), &mb.d_cell_msgs, cell_msgs)))
-          return rc;
-        if ((rc = dev_alloc(b.get(), &mb.d_msg_w, (int64_t)mdst.size())) || (rc = dev_alloc(b.get(), &mb.d_ecell, mb.n_cells)) ||
-            (rc = dev_alloc(b.get(), &mb.d_s_dst, ND)))
-          return rc;
-        for (int s = 0; s < S; ++s) {
-          const int se = mp.src[s].entity;
-          const int64_t rows_s = mp.nn[s].layers.empty() ? b->rows[se] + b->halo[se] : eoff[mp.src[s].adjacency][G];
-          if ((rc = dev_alloc(b.get(), &mb.d_s_src[s], rows_s))) return rc;
-        }
-      }
-      // windowed sum: one workgroup per (graph, chunk of <= 256 destinations by message count), the
-      // destination's source rows ascending (a fixed summation order), LDS windows over the graph's
-      // source rows; the GRU step then reads x through an identity CSR over the same order
-      // (small graphs only: a workgroup walks all of its graph's windows, at most 4 of them)
-      int64_t max_src_rows = 0;
-      if (S == 1)
-        for (int g = 0; g < G; ++g)
-          max_src_rows = std::max(max_src_rows, b->row_off[mp.src[0].entity][g + 1] - b->row_off[mp.src[0].entity][g]);
-      const int64_t win_rows = DIN == 16 ? 2400 : DIN == 32 ? 1200 : 600;   // sum_win_kernel's windows
-      // IGN_SUM_WINDOW: -1 auto, 0 off below 128 messages (one lane group per destination walks its
-      // messages in the GRU-step kernel), 1 windowed, 2 segmented for every destination.  Auto takes the segmented
-      // sum (one wave per destination) for the destinations whose lane walk would be a long dependent
-      // chain: >= 64 messages (seg_min_messages; Q-size's path -> node update, ~140 per node: 4.36-4.39
-      // ms/step against 5.19 windowed and 5.51 lane-walk in round 4).  The rule reads each
-      // destination's own in-degree, a property of its graph, so a graph's predictions stay bitwise
-      // the same alone and in any batch (the two kernels add a destination's messages in different
-      // orders), and the graph-resident forward takes the same order per row (resident.hip B1).
-      bm.mark("csr");
-      const bool window = p->sum_window == 1;
-      int64_t n_seg = 0;   // order is sorted by message count, descending: the segmented rows lead
-      if (p->sum_window == 0 && ND > 0 && ptr[1] - ptr[0] >= kSegMinMessages)   // (order: by count, descending)
-        return fail(IGN_ERR_UNSUPPORTED, "IGN_SUM_WINDOW=0 (every sum a lane walk): mp %d has a destination of %lld "
-                    "messages; a float32 chain of >= %lld terms leaves the fp32 class, so this switch is for batches "
-                    "below that", (int)mi, (long long)(ptr[1] - ptr[0]), (long long)kSegMinMessages);
-      if (!window && !halo)
-        while (n_seg < ND && ptr[n_seg + 1] - ptr[n_seg] >= seg_min_messages(p)) ++n_seg;
-      const bool seg = n_seg > 0;
-      if (window && mp.aggr == IGN_AGGR_SUM && S == 1 && mp.nn[0].layers.empty() &&
-          b->halo[mp.src[0].entity] == 0 && (DIN == 16 || DIN == 32 || DIN == 64) && max_src_rows <= 4 * win_rows) {
-        const int se = mp.src[0].entity;
-        hvec<int64_t> dstart(ND + 1, 0);
-        for (size_t k = 0; k < mdst.size(); ++k) dstart[mdst[k] + 1]++;
-        for (int64_t r = 0; r < ND; ++r) dstart[r + 1] += dstart[r];
-        hvec<int32_t> rows_by(mdst.size());
-        {
-          hvec<int64_t> fill(dstart.begin(), dstart.end() - 1);
-          for (size_t k = 0; k < mdst.size(); ++k) rows_by[fill[mdst[k]]++] = (int32_t)(mcode[k] & IGN_ROW_MASK);
-        }
-        for (int64_t r = 0; r < ND; ++r) std::sort(rows_by.begin() + dstart[r], rows_by.begin() + dstart[r + 1]);
-        hvec<int64_t> wg;
-        hvec<int32_t> wdst, wptr(1, 0), wsrc;
-        wdst.reserve(ND);
-        wsrc.reserve(mdst.size());
-        for (int g = 0; g < G; ++g) {
-          hvec<int32_t> ds;
-          for (int64_t r = b->row_off[dst][g]; r < b->row_off[dst][g + 1]; ++r) ds.push_back((int32_t)r);
-          std::stable_sort(ds.begin(), ds.end(), [&](int32_t x, int32_t y) { return flen[x] > flen[y]; });
-          for (size_t c0 = 0; c0 < ds.size(); c0 += 256) {
-            const size_t c1 = std::min(ds.size(), c0 + 256);
-            wg.push_back((int64_t)wdst.size());
-            wg.push_back((int64_t)(wdst.size() + (c1 - c0)));
-            wg.push_back(b->row_off[se][g]);
-            wg.push_back(b->row_off[se][g + 1]);
-            for (size_t q = c0; q < c1; ++q) {
-              const int32_t r = ds[q];
-              wdst.push_back(r);
-              wsrc.insert(wsrc.end(), rows_by.begin() + dstart[r], rows_by.begin() + dstart[r + 1]);
-              wptr.push_back((int32_t)wsrc.size());
-            }
-          }
-        }
-        hvec<int32_t> id_ptr(ND + 1);
-        hvec<uint32_t> id_src(ND);
-        for (int64_t i = 0; i <= ND; ++i) id_ptr[i] = (int32_t)i;
-        for (int64_t i = 0; i < ND; ++i) id_src[i] = (uint32_t)order[i];   // slot 0: the x table
-        mb.n_win_wg = (int64_t)wg.size() / 4;
-        if ((rc = dev_upload(b.get(), &mb.d_win_wg, wg)) || (rc = dev_upload(b.get(), &mb.d_win_dst, wdst)) ||
-            (rc = dev_upload(b.get(), &mb.d_win_ptr, wptr)) || (rc = dev_upload(b.get(), &mb.d_win_src, wsrc)) ||
-            (rc = dev_upload(b.get(), &mb.d_id_ptr, id_ptr)) || (rc = dev_upload(b.get(), &mb.d_id_src, id_src)) ||
-            (rc = dev_alloc(b.get(), &mb.d_xsum, std::max<int64_t>(ND, 1) * DIN)))
-          return rc;
-      } else if (seg && mp.aggr == IGN_AGGR_SUM && S == 1 && mp.nn[0].layers.empty() && b->halo[mp.src[0].entity] == 0 &&
-                 (DIN == 16 || DIN == 32 || DIN == 64)) {
-        // segmented sum (sum_seg_kernel over the MP's own CSR, one wave per destination) for order
-        // positions [0, n_seg), then the GRU step over a mixed CSR: those positions read their x
-        // from the xsum table (one message, slot 1; the lane walk adds it to zero exactly), the
-        // others their own messages (slot 0)
-        hvec<int32_t> id_ptr(ND + 1, 0);
-        hvec<uint32_t> id_src;
-        id_src.reserve((size_t)(n_seg + (ptr[ND] - ptr[n_seg])));
-        for (int64_t i = 0; i < ND; ++i) {
-          if (i < n_seg) id_src.push_back((1u << IGN_SLOT_SHIFT) | (uint32_t)order[i]);
-          else id_src.insert(id_src.end(), msrc.begin() + ptr[i], msrc.begin() + ptr[i + 1]);
-          id_ptr[i + 1] = (int32_t)id_src.size();
-        }
-        mb.sum_seg = true;
-        mb.n_seg = n_seg;
-        if ((rc = dev_upload(b.get(), &mb.d_id_ptr, id_ptr)) || (rc = dev_upload(b.get(), &mb.d_id_src, id_src)) ||
-            (rc = dev_alloc(b.get(), &mb.d_xsum, std::max<int64_t>(ND, 1) * DIN)))
-          return rc;
-      }
-      mb.n_msgs = (int64_t)msrc.size();
-      if ((rc = dev_upload(b.get(), &mb.d_order, order))) return rc;
-      if ((rc = dev_upload(b.get(), &mb.d_msg_ptr, ptr))) return rc;
-      if ((rc = dev_upload(b.get(), &mb.d_msg_src, msrc))) return rc;
-      mb.h_order = std::move(order);
-      mb.h_msg_ptr = std::move(ptr);
-      mb.h_msg_src = std::move(msrc);
-      mb.flops = (double)ND * gru_flops(DIN, H) + (double)mb.n_msgs * DIN;
-      mb.bytes = (double)mb.n_msgs * (4.0 * DIN + 4) + (double)ND * (8.0 * H + 8);
-      b->gru_steps += ND * p->T;
-    }
+    mb.edges = ml.tot;
+    b->edges_per_forward += ml.tot * p->T;
+    const int H = p->cells[mp.cell].H;
+    if ((rc = mp.sorted ? build_ordered_mp(b.get(), mp, H, sh, ml, bm, mb)
+                        : build_sum_mp(b.get(), mp, mi, H, sh, ml, bm, mb)))
+      return rc;
     b->mp.push_back(std::move(mb));
   }
 
@@ -2184,17 +1458,73 @@ extern "C++" int ign::resident_launch(ign_plan* p, ign_batch* b, const ResidentS
   return IGN_OK;
 }
 
-// IGN_RES_GROUP=K: K graphs per workgroup.  Auto (0): two where the all-LDS form of a single graph fits
+static_assert(kResMaxSrc == kResidentMaxSrc && (int)kResAllLds == (int)IGN_RES_ALL_LDS &&
+              (int)kResPathGlobal == (int)IGN_RES_PATH_GLOBAL && (int)kResPathCsrGlobal == (int)IGN_RES_PATH_CSR_GLOBAL,
+              "batch_lower.h and kernels.h disagree");
+
+static int resident_upload(ign_batch* b, const ResidentTables& t, int S) {
+  HIP_TRY(resident_prepare_device());
+  int rc;
+  for (int s = 0; s < S; ++s)
+    if ((rc = dev_upload(b, &b->d_res_src_off[s], t.src_off[s]))) return rc;
+  if ((rc = dev_upload(b, &b->d_res_path_off, t.path_off)) || (rc = dev_upload(b, &b->d_res_urow_off, t.urow_off)) ||
+      (rc = dev_upload(b, &b->d_res_ptile_off, t.ptile_off)) || (rc = dev_upload(b, &b->d_res_hdr, t.hdr)) ||
+      (rc = dev_upload(b, &b->d_res_lmsg_off, t.lmsg_off)) || (rc = dev_upload(b, &b->d_res_lmsg_ptr, t.lmsg_ptr)) ||
+      (rc = dev_upload(b, &b->d_res_lmsg_src, t.lmsg_src)) || (rc = dev_upload(b, &b->d_res_lorder, t.lorder)) ||
+      (rc = dev_upload(b, &b->d_res_lnseg, t.lnseg)) || (rc = dev_upload(b, &b->d_res_lcode_off, t.lcode_off)) ||
+      (rc = dev_upload(b, &b->d_res_hsb, t.hsb)) || (rc = dev_upload(b, &b->d_res_gorder, t.gorder)) ||
+      (rc = dev_upload(b, &b->d_res_lcode, t.lcode)))
+    return rc;
+  b->res_train_form = t.train_form;
+  b->res_train_lds = t.lds[t.train_form];
+  b->res_lds = t.lds[t.form];
+  b->res_form = t.form;
+  b->res_graphs = t.G;
+  b->res_info = t.info;
+  b->resident = true;
+  return IGN_OK;
+}
+
+// the per-graph tables of the resident forward; leaves b->resident false where it does not apply
+// (built on the host for each K, and only the set that runs is uploaded.)  IGN_RES_GROUP=K: K graphs per workgroup.  Auto (0): two where the all-LDS form of a single graph fits
 // twice (NSFNET x512: 0.248-0.257 -> 0.203-0.208 ms/step, r06_c07; GEANT2's path states need the
 // path-global form at two per workgroup, measured slower: 0.548 -> 0.570), else one
 static int resident_batch(ign_plan* p, ign_batch* b) {
-  if (p->res_group > 0) return resident_batch_k(p, b, p->res_group);
-  int rc = resident_batch_k(p, b, 1);
-  if (rc || !b->resident || b->res_form != IGN_RES_ALL_LDS || b->G < 2 || 2 * b->res_lds > kResidentMaxDynLds)
-    return rc;
-  b->resident = false;   // (the single-graph tables stay allocated until the batch goes)
-  if ((rc = resident_batch_k(p, b, 2)) || b->resident) return rc;
-  return resident_batch_k(p, b, 1);
+  ResShape sh;
+  if (!resident_plan_shape(p, &sh)) return IGN_OK;
+  ResidentParams rp;
+  rp.path = sh.path;
+  rp.n_src = sh.n_src;
+  rp.T = p->T;
+  rp.sum_window = p->sum_window;
+  rp.path_global_ok = p->resident_pg;
+  rp.force_path_global = p->resident_path_global;
+  rp.max_tiles = kResidentMaxTiles;
+  rp.state_stride = kResidentStateStride;
+  rp.table_stride = kResidentTableStride;
+  rp.max_dyn_lds = kResidentMaxDynLds;
+  for (auto& e : p->ents) rp.feature_total.push_back(e.feature_total);
+  const MPB& a = b->mp[0];
+  const ResOrderedIn ma{a.h_order, a.h_len, a.h_step_ptr, a.h_step_code, a.src_off, a.zero_row, a.n_multi, a.n_steps,
+                        a.flops, a.bytes};
+  std::vector<ResSumIn> sums;
+  for (int s = 0; s < sh.n_src; ++s) {
+    rp.src_ent[s] = sh.src_ent[s];
+    const MPB& m = b->mp[sh.sum_mp[s]];
+    sums.push_back(ResSumIn{m.h_order, m.h_msg_ptr, m.h_msg_src, m.flops, m.bytes});
+  }
+  const BatchRows rows{b->G, b->row_off, b->rows, b->halo};
+  ResidentTables one;
+  lower_resident(rp, p->res_group > 0 ? p->res_group : 1, rows, ma, sums, &one);
+  if (!one.eligible) return IGN_OK;
+  if (p->res_group == 0 && one.form == IGN_RES_ALL_LDS && b->G >= 2 && 2 * one.lds[one.form] <= kResidentMaxDynLds) {
+    // two graphs per workgroup, where they lower; a failed upload falls back to the single-graph
+    // tables (its blocks stay with the batch until it goes)
+    ResidentTables two;
+    lower_resident(rp, 2, rows, ma, sums, &two);
+    if (two.eligible && resident_upload(b, two, sh.n_src) == IGN_OK) return IGN_OK;
+  }
+  return resident_upload(b, one, sh.n_src);
 }
 
 // the batch's resident tables, built once (the first ign_forward or training forward)
