@@ -26,6 +26,7 @@
 #include "engine_internal.h"
 #include "readout_kernels.h"
 #include "train_kernels.h"
+#include "train_lower.h"
 
 struct MPTrain {
   std::vector<float*> hs;     // sorted MPs: per iteration [(n_steps + n_dst)][H]
@@ -233,35 +234,6 @@ int tsgemm_deferred_flush(const ign_plan* p, TrainState* t, hipStream_t st) {
   return IGN_OK;
 }
 
-// CSR of (key, value) pairs over n_keys keys, values kept in insertion order per key
-void build_csr(int64_t n_keys, const hvec<std::pair<int64_t, int32_t>>& kv, hvec<int32_t>& ptr,
-               hvec<int32_t>& idx) {
-  ptr.assign(n_keys + 1, 0);
-  for (auto& p : kv) ptr[p.first + 1]++;
-  for (int64_t k = 0; k < n_keys; ++k) ptr[k + 1] += ptr[k];
-  idx.resize(kv.size());
-  hvec<int32_t> fill(ptr.begin(), ptr.end() - 1);
-  for (auto& p : kv) idx[fill[p.first]++] = p.second;
-}
-
-// Per source slot s, the CSR of the (row, value) pairs visit() emits, values in emission order
-// per row: one counting pass and one filling pass over the same visit, no pair list.
-template <class Visit>
-void build_csrs(int S, const int64_t* n_keys, Visit visit, std::vector<hvec<int32_t>>& ptr,
-                std::vector<hvec<int32_t>>& idx) {
-  ptr.assign(S, hvec<int32_t>());
-  idx.assign(S, hvec<int32_t>());
-  for (int s = 0; s < S; ++s) ptr[s].assign(n_keys[s] + 1, 0);
-  visit([&](int s, int64_t key, int32_t) { ptr[s][key + 1]++; });
-  std::vector<hvec<int32_t>> fill(S);
-  for (int s = 0; s < S; ++s) {
-    for (int64_t k = 0; k < n_keys[s]; ++k) ptr[s][k + 1] += ptr[s][k];
-    idx[s].resize(ptr[s][n_keys[s]]);
-    fill[s].assign(ptr[s].begin(), ptr[s].end() - 1);
-  }
-  visit([&](int s, int64_t key, int32_t v) { idx[s][fill[s][key]++] = v; });
-}
-
 int check_train(ign_plan* p, ign_batch* b) {
   if (!p || !b) return fail(IGN_ERR_INVALID, "null argument");
   if (b->plan != p) return fail(IGN_ERR_INVALID, "batch was created for another plan");
@@ -328,6 +300,343 @@ int msg_net_backward(ign_plan* p, ign_batch* b, TrainState* t, const MPP& mp, co
   return IGN_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// ign_batch_enable_training, step by step
+
+// every used GRU cell has its backward fragments
+int check_train_shapes(const ign_plan* p) {
+  for (size_t c = 0; c < p->cells.size(); ++c) {
+    const CellP& cp = p->cells[c];
+    if (!cp.used) continue;
+    bool concat_only = true;   // W^T is not needed by a cell fed only by axis-2 concat MPs
+    for (auto& mp : p->mps)
+      if (mp.cell == (int)c && !mp.feature_concat) concat_only = false;
+    if (cp.pk_ut < 0 || (cp.pk_wt < 0 && !concat_only))
+      return fail(IGN_ERR_UNSUPPORTED, "no backward kernel for GRU shape (input %d, units %d)", cp.din, cp.H);
+  }
+  return IGN_OK;
+}
+
+// per entity: the hidden-state versions, 1 + T x (MPs updating the entity), and the two dS buffers
+int alloc_states(const ign_plan* p, const ign_batch* b, TrainState* t) {
+  const int E = (int)p->ents.size();
+  int rc;
+  hvec<int> nver(E, 1);
+  for (auto& mp : p->mps) nver[mp.dst] += p->T;
+  t->ver.resize(E);
+  t->cur.assign(E, 0);
+  for (int e = 0; e < E; ++e) {
+    const int64_t n = (b->rows[e] + b->halo[e]) * p->ents[e].hidden_dim;   // owned rows, then halo rows
+    for (int v = 0; v < nver[e]; ++v) {
+      float* f = nullptr;
+      if ((rc = talloc(t, &f, n))) return rc;
+      t->ver[e].push_back(f);
+    }
+    for (int k = 0; k < 2; ++k) {
+      float* f = nullptr;
+      if ((rc = talloc(t, &f, n))) return rc;
+      t->dS[k].push_back(f);
+    }
+  }
+  return IGN_OK;
+}
+
+TrainMpIn host_tables(const MPB& mb) {
+  return {mb.h_order, mb.h_len, mb.h_step_ptr, mb.h_msg_ptr, mb.h_multi_ptr, mb.h_step_code,
+          mb.h_msg_src, mb.h_multi_rows, mb.src_off, mb.zero_row, mb.n_dst, mb.n_msgs};
+}
+
+// message network of source s (GM:440-475): the state row -> edge CSRs of its backward, from the
+// edge rows the batch keeps on the device
+int enable_msg_net(const ign_batch* b, TrainState* t, const MPP& mp, const MPB& mb, int s, MPTrain& mt) {
+  const int se = mp.src[s].entity;
+  const int64_t ne = mb.n_edges[s];
+  int rc;
+  hvec<int32_t> es(ne), ed(ne);
+  HIP_TRY(hipMemcpyAsync(es.data(), mb.d_edge_src[s], ne * sizeof(int32_t), hipMemcpyDeviceToHost, upload_stream()));
+  HIP_TRY(hipMemcpyAsync(ed.data(), mb.d_edge_dst[s], ne * sizeof(int32_t), hipMemcpyDeviceToHost, upload_stream()));
+  HIP_TRY(hipStreamSynchronize(upload_stream()));
+  HIP_TRY(upload_flush());
+  hvec<int32_t> p1, i1, p2, i2;
+  lower_row_edges(b->rows[se] + b->halo[se], es.data(), ne, &p1, &i1);   // sources may be halo rows (edge-cut)
+  lower_row_edges(b->rows[mp.dst], ed.data(), ne, &p2, &i2);
+  if ((rc = tupload(t, &mt.nsrc_ptr[s], p1)) || (rc = tupload(t, &mt.nsrc_idx[s], i1)) ||
+      (rc = tupload(t, &mt.ndst_ptr[s], p2)) || (rc = tupload(t, &mt.ndst_idx[s], i2)))
+    return rc;
+  return IGN_OK;
+}
+
+// MP mi: the buffers its forward saves into and the tables its backward walks.  The transposed
+// CSRs (source row -> steps / destinations reading it) are built on the GPU (mt.tptr, gidx) or on
+// the host (tptr, tidx, uploaded with the slots)
+int enable_mp(const ign_plan* p, const ign_batch* b, TrainState* t, size_t mi, bool tcsr_on) {
+  const MPP& mp = p->mps[mi];
+  const MPB& mb = b->mp[mi];
+  const int H = p->cells[mp.cell].H, DIN = mp.din, S = (int)mp.src.size();
+  const TrainMpIn in = host_tables(mb);
+  int rc;
+  MPTrain mt;
+  std::vector<hvec<int32_t>> tptr, tidx;
+  int32_t* gidx = nullptr;
+  int64_t tkeys[IGN_MAX_SLOTS] = {0, 0, 0, 0};
+  for (int s = 0; s < S; ++s) tkeys[s] = train_keys(mp, s, b->rows, b->halo, mb.n_edges);
+  if (mb.sorted) {
+    mt.hs_rows = mb.n_steps + mb.n_dst;
+    for (int it = 0; it < p->T; ++it) {
+      float* f = nullptr;
+      // + one pad row: the resident training forward's tile headers point padding positions there
+      // (resident.hip, hsb; its stores skip them, so the row stays unwritten)
+      if ((rc = talloc(t, &f, (mt.hs_rows + 1) * H))) return rc;
+      mt.hs.push_back(f);
+    }
+    {
+      const int64_t n_pos = (mb.n_dst + 15) / 16 * 16;
+      float* f = nullptr;
+      if ((rc = talloc(t, &f, 4 * n_pos))) return rc;
+      mt.hdrb = reinterpret_cast<int32_t*>(f);
+      // on the upload stream, behind the block's IGN_POOL_POISON fill (pool_alloc) and before the
+      // synchronisation at the end of this call: a launch on the plan stream could land first
+      HIP_TRY(launch_seq_bwd_hdr(mb.d_seq_hdr, mb.d_step_code, n_pos, mt.hdrb, upload_stream()));
+    }
+    // a pre-summed row expands into its source rows on the host only
+    if (tcsr_on && mb.n_multi == 0) {
+      if ((rc = tcsr_gpu(t, mb, S, tkeys, true, mt.tptr, gidx))) return rc;
+    } else lower_train_ordered(S, tkeys, in, tptr, tidx);
+  } else {
+    for (int it = 0; it < p->T; ++it) {
+      float* f = nullptr;
+      if ((rc = talloc(t, &f, mb.n_dst * DIN))) return rc;
+      mt.xs.push_back(f);
+      if (mp.aggr == IGN_AGGR_CONVOLUTION) {
+        if ((rc = talloc(t, &f, mb.n_dst * DIN))) return rc;
+        mt.ss.push_back(f);
+      }
+    }
+    if (mp.aggr == IGN_AGGR_ATTENTION) {
+      // (no halo rows under attention; a message network's codes address its edges, the per-edge message rows)
+      TrainAttn at;
+      lower_train_attention(S, tkeys, in, &at);
+      if ((rc = tupload(t, &mt.amdst, at.mdst))) return rc;
+      for (int s = 0; s < S; ++s) {
+        int32_t *dp = nullptr, *di = nullptr;
+        if ((rc = tupload(t, &dp, at.ptr[s])) || (rc = tupload(t, &di, at.idx[s]))) return rc;
+        mt.asptr.push_back(dp);
+        mt.asidx.push_back(di);
+      }
+    }
+    if (mp.aggr == IGN_AGGR_CONVOLUTION) {
+      hvec<float> deg;
+      lower_train_degree(in, &deg);
+      if ((rc = tupload(t, &mt.deg, deg))) return rc;
+    }
+    if (tcsr_on) {
+      if ((rc = tcsr_gpu(t, mb, S, tkeys, false, mt.tptr, gidx))) return rc;
+    } else lower_train_sum(S, tkeys, in, tptr, tidx);
+  }
+  for (int s = 0; s < S; ++s) {
+    if (gidx) {
+      mt.tidx.push_back(gidx);   // (mt.tptr[s] set by tcsr_gpu)
+    } else {
+      int32_t *dp = nullptr, *di = nullptr;
+      if ((rc = tupload(t, &dp, tptr[s])) || (rc = tupload(t, &di, tidx[s]))) return rc;
+      mt.tptr.push_back(dp);
+      mt.tidx.push_back(di);
+    }
+    mt.trows.push_back(tkeys[s]);
+    if (!mp.nn[s].layers.empty() && (rc = enable_msg_net(b, t, mp, mb, s, mt))) return rc;
+  }
+  t->mp.push_back(std::move(mt));
+  return IGN_OK;
+}
+
+// floats of the scratch buffers the MP instances / readout layers of a backward share: the largest need of each
+struct TrainScratch {
+  int64_t ga = 0, gu = 0, dx = 0, dtab = 0, part = 0;
+  int64_t dmsg = 0, mz = 0, mdin = 0;            // message networks
+  int64_t amsg = 0, arows = 0;                   // attention
+  int64_t dz = 0, rz = 0, rcat = 0, ties = 0;    // readout
+};
+TrainScratch train_scratch(const ign_plan* p, const ign_batch* b) {
+  TrainScratch z;
+  auto need_part = [&](int64_t rows, int M, int N) { z.part = std::max(z.part, tsgemm_partial_floats(rows, M, N)); };
+  for (size_t mi = 0; mi < p->mps.size(); ++mi) {
+    const MPP& mp = p->mps[mi];
+    const MPB& mb = b->mp[mi];
+    const int H = p->cells[mp.cell].H, DIN = mp.din, S = (int)mp.src.size();
+    if (mb.sorted) {
+      const int64_t hs_rows = mb.n_steps + mb.n_dst;
+      z.ga = std::max(z.ga, (mb.n_steps + 1) * 3 * H);   // + the pad slot row (seq_gru_bwd_kernel)
+      z.gu = std::max(z.gu, hs_rows * 3 * H);
+      need_part(hs_rows, H, 3 * H);
+      if (p->bwd_fuse && seq_bwd_fused_supported(H)) z.part = std::max(z.part, seq_bwd_partial_floats(H));
+      for (int s = 0; s < S; ++s) {
+        z.dtab = std::max(z.dtab, mb.src_rows[s] * 3 * H);
+        need_part(mb.src_rows[s], mp.feature_concat ? p->ents[mp.src[s].entity].hidden_dim : DIN, 3 * H);
+      }
+    } else {
+      if (mp.aggr == IGN_AGGR_ATTENTION) {
+        for (int s = 0; s < S; ++s) {
+          const int64_t rows_s = train_keys(mp, s, b->rows, b->halo, mb.n_edges);
+          z.arows = std::max(z.arows, rows_s);
+          need_part(rows_s, DIN, 1);
+        }
+        z.amsg = std::max(z.amsg, mb.n_msgs);
+        z.arows = std::max(z.arows, mb.n_dst);
+        need_part(mb.n_dst, H, 1);
+      }
+      if (mp.aggr == IGN_AGGR_CONVOLUTION) {
+        z.dtab = std::max(z.dtab, 2 * mb.n_dst * DIN);   // du and d(sum) of the convolution
+        need_part(mb.n_dst, DIN, DIN);
+      }
+      z.ga = std::max(z.ga, mb.n_dst * 3 * H);
+      z.gu = std::max(z.gu, mb.n_dst * 3 * H);
+      z.dx = std::max(z.dx, mb.n_dst * DIN);
+      need_part(mb.n_dst, std::max(DIN, H), 3 * H);
+    }
+    need_part(std::max<int64_t>(mb.n_steps, mb.n_dst), 1, 3 * H);   // colsum
+    for (int s = 0; s < S; ++s) {
+      const MsgNN& nn = mp.nn[s];
+      if (nn.layers.empty()) continue;
+      const int64_t ne = mb.n_edges[s];
+      int widest = nn.din_pad;
+      for (size_t l = 0; l < nn.layers.size(); ++l) {
+        widest = std::max(widest, nn.layers[l].out);
+        need_part(ne, l == 0 ? nn.din : nn.layers[l].in, nn.layers[l].out);
+      }
+      z.dmsg = std::max(z.dmsg, ne * nn.dout());
+      z.mz = std::max(z.mz, ne * widest);
+      z.mdin = std::max(z.mdin, ne * nn.din);
+    }
+  }
+  const int64_t P = b->n_pred;
+  int64_t widest = p->ro_width;
+  for (auto& d : p->dense) {
+    widest = std::max<int64_t>(widest, d.out);
+    need_part(P, d.in, d.out);
+  }
+  z.dz = P * widest;
+  for (auto& op : p->ro_ops) {   // readout operations (GM:605-655)
+    const int64_t n = space_rows(p, b, p->ro_t[op.in[0]]);
+    if (op.type == IGN_RO_NEURAL_NETWORK) {
+      int widest = op.in_width, K = op.in_width;
+      for (auto& d : op.layers) {
+        widest = std::max(widest, d.out);
+        need_part(n, K, d.out);
+        K = d.out;
+      }
+      z.rz = std::max(z.rz, n * widest);
+      if (op.in.size() > 1) z.rcat = std::max(z.rcat, n * op.in_width);
+    } else if (op.type == IGN_RO_POOLING) {
+      z.ties = std::max(z.ties, (int64_t)b->G * p->ro_t[op.in[0]].width);
+    }
+  }
+  return z;
+}
+
+int alloc_mp_scratch(const ign_plan* p, TrainState* t, const TrainScratch& z) {
+  int rc;
+  if ((rc = talloc(t, &t->ga, z.ga)) || (rc = talloc(t, &t->gu, z.gu)) || (rc = talloc(t, &t->dx, z.dx)) ||
+      (rc = talloc(t, &t->dtab, z.dtab)))
+    return rc;
+  if (z.amsg && ((rc = talloc(t, &t->adw, z.amsg)) || (rc = talloc(t, &t->adv, z.amsg)) ||
+                 (rc = talloc(t, &t->ads_src, z.arows)) || (rc = talloc(t, &t->ads_dst, z.arows)) ||
+                 (rc = talloc(t, &t->adw12, 2 * p->attn_F))))
+    return rc;
+  if (z.dmsg && ((rc = talloc(t, &t->dmsg, z.dmsg)) || (rc = talloc(t, &t->mz[0], z.mz)) ||
+                 (rc = talloc(t, &t->mz[1], z.mz)) || (rc = talloc(t, &t->mdin, z.mdin))))
+    return rc;
+  return IGN_OK;
+}
+
+// the readout's saved activations and gradient buffers; per extend op, its two input row -> edge CSRs
+int alloc_readout(const ign_plan* p, const ign_batch* b, TrainState* t, const TrainScratch& z) {
+  const int64_t P = b->n_pred;
+  int rc;
+  for (size_t l = 0; l + 1 < p->dense.size(); ++l) {
+    float* f = nullptr;
+    if ((rc = talloc(t, &f, P * p->dense[l].out))) return rc;
+    t->act.push_back(f);
+  }
+  if ((rc = talloc(t, &t->dz[0], z.dz)) || (rc = talloc(t, &t->dz[1], z.dz))) return rc;
+  if (p->ro_in.size() > 1 &&
+      ((rc = talloc(t, &t->ro_x, P * p->ro_width)) || (rc = talloc(t, &t->dro, P * p->ro_width))))
+    return rc;
+  // readout operations (GM:605-655)
+  t->dT.assign(p->ro_t.size(), nullptr);
+  for (size_t k = 0; k < p->ro_ops.size(); ++k) {
+    const RoOp& op = p->ro_ops[k];
+    const int nout = op.type == IGN_RO_EXTEND ? 2 : 1;
+    for (int j = 0; j < nout; ++j) {
+      const RoTensor& to = p->ro_t[op.out + j];
+      if ((rc = talloc(t, &t->dT[op.out + j], space_rows(p, b, to) * to.width))) return rc;
+    }
+    if (op.type != IGN_RO_EXTEND) continue;
+    for (int j = 0; j < 2; ++j) {
+      const std::vector<int32_t>& ix = b->ro[k].h_idx[j];
+      hvec<int32_t> ptr, idx;
+      lower_row_edges(space_rows(p, b, p->ro_t[op.in[j]]), ix.data(), (int64_t)ix.size(), &ptr, &idx);
+      int32_t *dp = nullptr, *di = nullptr;
+      if ((rc = tupload(t, &dp, ptr)) || (rc = tupload(t, &di, idx))) return rc;
+      t->rx_ptr.push_back(dp);
+      t->rx_idx.push_back(di);
+    }
+  }
+  if ((z.rz && ((rc = talloc(t, &t->rz[0], z.rz)) || (rc = talloc(t, &t->rz[1], z.rz)))) ||
+      (z.rcat && (rc = talloc(t, &t->rcat, z.rcat))) || (z.ties && (rc = talloc(t, &t->rties, z.ties))))
+    return rc;
+  return IGN_OK;
+}
+
+// IGN_DEFER_WGRAD (default on): the per-instance weight gradients of the plain sum and ordered MPs
+// (ign_backward_mp): one slot per (gradient tensor, shape), room for every instance of a backward
+int alloc_deferred(const ign_plan* p, const ign_batch* b, TrainState* t) {
+  int rc;
+  struct Want { int64_t c, cb; int M, N, ones; int64_t chunks; };
+  std::vector<Want> want;
+  auto add = [&](int64_t c, int64_t cb, int M, int N, int64_t rows, int64_t min_slots = 0) {
+    const int ones = cb >= 0;
+    const int64_t ch = std::max(tsgemm_chunks(rows, M, N, ones), min_slots) * p->T;
+    for (auto& w : want)
+      if (w.c == c && w.cb == cb && w.M == M && w.N == N) { w.chunks += ch; return; }
+    want.push_back({c, cb, M, N, ones, ch});
+  };
+  for (size_t mi = 0; mi < p->mps.size(); ++mi) {
+    const MPP& mp = p->mps[mi];
+    const MPB& mb = b->mp[mi];
+    const CellP& cp = p->cells[mp.cell];
+    bool nets = false;
+    for (auto& nn : mp.nn) nets = nets || !nn.layers.empty();
+    if (nets || mp.feature_concat) continue;
+    const int H = cp.H, H3 = 3 * cp.H, DIN = mp.din;
+    if (mp.sorted) {
+      for (size_t s2 = 0; s2 < mp.src.size(); ++s2) add(cp.off_k, -1, DIN, H3, t->mp[mi].trows[s2]);
+    } else if (mp.aggr == IGN_AGGR_SUM) {
+      const int64_t fw = sum_bwd_fused_waves(mb.n_dst, DIN, H);   // the fused sum backward's partials
+      add(cp.off_k, cp.off_b, DIN, H3, mb.n_dst, fw);
+      add(cp.off_rk, cp.off_b + H3, H, H3, mb.n_dst, fw);
+    }
+  }
+  for (size_t mi = 0; mi < p->mps.size(); ++mi) {   // the fused ordered backward's partials
+    const MPP& mp = p->mps[mi];
+    const CellP& cp = p->cells[mp.cell];
+    if (!mp.sorted || !p->bwd_fuse || !seq_bwd_fused_supported(cp.H)) continue;
+    const int64_t tiles = (b->mp[mi].n_dst + 15) / 16;
+    const int64_t waves = std::min<int64_t>((tiles + 3) / 4 * 4, kBwdPartialWaves) * p->T;   // upper bound
+    bool found = false;
+    for (auto& d : t->defer_seq)
+      if (d.cell == mp.cell) { d.cap += waves; found = true; }
+    if (!found) t->defer_seq.push_back({mp.cell, cp.H, nullptr, waves, 0});
+  }
+  for (auto& d : t->defer_seq)
+    if ((rc = talloc(t, &d.part, (d.cap + kTsReduceSegs) * (int64_t)(d.H + 2) * 3 * d.H))) return rc;
+  for (auto& w : want) {
+    TrainState::DeferredGrad d{w.c, w.cb, w.M, w.N, w.ones, nullptr, w.chunks, 0};
+    if ((rc = talloc(t, &d.part, (w.chunks + kTsReduceSegs) * (int64_t)(w.M + w.ones) * w.N))) return rc;
+    t->defer.push_back(d);
+  }
+  return IGN_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -343,322 +652,20 @@ int ign_batch_enable_training(ign_plan* p, ign_batch* b) {
   const bool tcsr_on = !tcsr_env || atoi(tcsr_env) != 0;   // the transposed CSRs on the GPU (train_csr.hip)
   const char* fine = getenv("IGN_BUILD_PROF_FINE");
   BuildMarks bm(fine && atoi(fine) != 0);   // IGN_BUILD_PROF_FINE=1: host sections of this build
-  const int E = (int)p->ents.size();
-  for (size_t c = 0; c < p->cells.size(); ++c) {
-    const CellP& cp = p->cells[c];
-    if (!cp.used) continue;
-    bool concat_only = true;   // W^T is not needed by a cell fed only by axis-2 concat MPs
-    for (auto& mp : p->mps)
-      if (mp.cell == (int)c && !mp.feature_concat) concat_only = false;
-    if (cp.pk_ut < 0 || (cp.pk_wt < 0 && !concat_only))
-      return fail(IGN_ERR_UNSUPPORTED, "no backward kernel for GRU shape (input %d, units %d)", cp.din, cp.H);
-  }
+  if ((rc = check_train_shapes(p))) return rc;
   std::unique_ptr<TrainState, void (*)(TrainState*)> t(new TrainState(), train_state_destroy);
   t->pool = b->pool.get();
   t->stream = p->stream;
-  const int64_t P = b->n_pred;
-  // hidden-state versions: 1 + T x (MPs updating the entity)
-  hvec<int> nver(E, 1);
-  for (auto& mp : p->mps) nver[mp.dst] += p->T;
-  t->ver.resize(E);
-  t->cur.assign(E, 0);
-  for (int e = 0; e < E; ++e) {
-    const int64_t n = (b->rows[e] + b->halo[e]) * p->ents[e].hidden_dim;   // owned rows, then halo rows
-    for (int v = 0; v < nver[e]; ++v) {
-      float* f = nullptr;
-      if ((rc = talloc(t.get(), &f, n))) return rc;
-      t->ver[e].push_back(f);
-    }
-    for (int k = 0; k < 2; ++k) {
-      float* f = nullptr;
-      if ((rc = talloc(t.get(), &f, n))) return rc;
-      t->dS[k].push_back(f);
-    }
-  }
-  int64_t ga_n = 0, gu_n = 0, dx_n = 0, dtab_n = 0, part_n = 0, dmsg_n = 0, mz_n = 0, mdin_n = 0;
-  int64_t amsg_n = 0, arows_n = 0;
-  auto need_part = [&](int64_t rows, int M, int N) {
-    part_n = std::max(part_n, tsgemm_partial_floats(rows, M, N));
-  };
+  if ((rc = alloc_states(p, b, t.get()))) return rc;
   for (size_t mi = 0; mi < p->mps.size(); ++mi) {
-    const MPP& mp = p->mps[mi];
-    const MPB& mb = b->mp[mi];
-    const CellP& cp = p->cells[mp.cell];
-    const int H = cp.H, DIN = mp.din, S = (int)mp.src.size();
-    MPTrain mt;
-    // transposed CSRs (source row -> steps / destinations reading it), built below: on the GPU
-    // (mt.tptr, gidx) or on the host (tptr, tidx, uploaded with the slots below)
-    std::vector<hvec<int32_t>> tptr, tidx;
-    int32_t* gidx = nullptr;
-    int64_t tkeys[IGN_MAX_SLOTS] = {0, 0, 0, 0};
-    for (int s = 0; s < S; ++s)
-      tkeys[s] = mp.nn[s].layers.empty() ? b->rows[mp.src[s].entity] + b->halo[mp.src[s].entity] : mb.n_edges[s];
-    if (mb.sorted) {
-      mt.hs_rows = mb.n_steps + mb.n_dst;
-      for (int it = 0; it < p->T; ++it) {
-        float* f = nullptr;
-        // + one pad row: the resident training forward's tile headers point padding positions there
-        // (resident.hip, hsb; its stores skip them, so the row stays unwritten)
-        if ((rc = talloc(t.get(), &f, (mt.hs_rows + 1) * H))) return rc;
-        mt.hs.push_back(f);
-      }
-      {
-        const int64_t n_pos = (mb.n_dst + 15) / 16 * 16;
-        float* f = nullptr;
-        if ((rc = talloc(t.get(), &f, 4 * n_pos))) return rc;
-        mt.hdrb = reinterpret_cast<int32_t*>(f);
-        // on the upload stream, behind the block's IGN_POOL_POISON fill (pool_alloc) and before the
-        // synchronisation at the end of this call: a launch on the plan stream could land first
-        HIP_TRY(launch_seq_bwd_hdr(mb.d_seq_hdr, mb.d_step_code, n_pos, mt.hdrb, upload_stream()));
-      }
-      // source row -> steps whose input contains it (directly or through a pre-summed row)
-      if (tcsr_on && mb.n_multi == 0) {
-        if ((rc = tcsr_gpu(t.get(), mb, S, tkeys, true, mt.tptr, gidx))) return rc;
-      } else build_csrs(S, tkeys, [&](auto&& emit) {
-        auto add_row = [&](uint32_t trow, int32_t step) {
-          for (int s = S - 1; s >= 0; --s)
-            if ((int64_t)trow >= mb.src_off[s]) {
-              emit(s, (int64_t)trow - mb.src_off[s], step);
-              return;
-            }
-        };
-        for (int64_t pos = 0; pos < mb.n_dst; ++pos)
-          for (int32_t tt = 0; tt < mb.h_len[pos]; ++tt) {
-            const int32_t i = mb.h_step_ptr[pos] + tt;
-            const uint32_t code = mb.h_step_code[i];
-            if ((int64_t)code < mb.zero_row) {
-              add_row(code, i);
-            } else if ((int64_t)code > mb.zero_row) {
-              const int64_t k = code - mb.zero_row - 1;
-              for (int32_t m = mb.h_multi_ptr[k]; m < mb.h_multi_ptr[k + 1]; ++m) add_row(mb.h_multi_rows[m], i);
-            }
-          }
-      }, tptr, tidx);
-      ga_n = std::max(ga_n, (mb.n_steps + 1) * 3 * H);   // + the pad slot row (seq_gru_bwd_kernel)
-      gu_n = std::max(gu_n, mt.hs_rows * 3 * H);
-      need_part(mt.hs_rows, H, 3 * H);
-      if (p->bwd_fuse && seq_bwd_fused_supported(H)) part_n = std::max(part_n, seq_bwd_partial_floats(H));
-      for (int s = 0; s < S; ++s) {
-        dtab_n = std::max(dtab_n, mb.src_rows[s] * 3 * H);
-        need_part(mb.src_rows[s], mp.feature_concat ? p->ents[mp.src[s].entity].hidden_dim : DIN, 3 * H);
-      }
-    } else {
-      for (int it = 0; it < p->T; ++it) {
-        float* f = nullptr;
-        if ((rc = talloc(t.get(), &f, mb.n_dst * DIN))) return rc;
-        mt.xs.push_back(f);
-        if (mp.aggr == IGN_AGGR_CONVOLUTION) {
-          if ((rc = talloc(t.get(), &f, mb.n_dst * DIN))) return rc;
-          mt.ss.push_back(f);
-        }
-      }
-      if (mp.aggr == IGN_AGGR_ATTENTION) {   // AUX:287-343: message -> destination row, row -> messages
-        hvec<int32_t> mdst(mb.n_msgs);
-        for (int64_t pos = 0; pos < mb.n_dst; ++pos)
-          for (int32_t m = mb.h_msg_ptr[pos]; m < mb.h_msg_ptr[pos + 1]; ++m) mdst[m] = mb.h_order[pos];
-        if ((rc = tupload(t.get(), &mt.amdst, mdst))) return rc;
-        std::vector<hvec<std::pair<int64_t, int32_t>>> am(S);
-        for (int64_t m = 0; m < mb.n_msgs; ++m)
-          am[mb.h_msg_src[m] >> IGN_SLOT_SHIFT].push_back({(int64_t)(mb.h_msg_src[m] & IGN_ROW_MASK), (int32_t)m});
-        for (int s = 0; s < S; ++s) {
-          // a message network's codes address its edges (the per-edge message rows)
-          const int64_t rows_s = mp.nn[s].layers.empty() ? b->rows[mp.src[s].entity] : mb.n_edges[s];
-          hvec<int32_t> ptr, idx;
-          build_csr(rows_s, am[s], ptr, idx);
-          int32_t *dp = nullptr, *di = nullptr;
-          if ((rc = tupload(t.get(), &dp, ptr)) || (rc = tupload(t.get(), &di, idx))) return rc;
-          mt.asptr.push_back(dp);
-          mt.asidx.push_back(di);
-          arows_n = std::max(arows_n, rows_s);
-          need_part(rows_s, DIN, 1);
-        }
-        amsg_n = std::max(amsg_n, mb.n_msgs);
-        arows_n = std::max(arows_n, mb.n_dst);
-        need_part(mb.n_dst, H, 1);
-      }
-      if (mp.aggr == IGN_AGGR_CONVOLUTION) {
-        hvec<float> deg(mb.n_dst, 0.f);
-        for (int64_t pos = 0; pos < mb.n_dst; ++pos)
-          deg[mb.h_order[pos]] = (float)(mb.h_msg_ptr[pos + 1] - mb.h_msg_ptr[pos]);
-        if ((rc = tupload(t.get(), &mt.deg, deg))) return rc;
-        dtab_n = std::max(dtab_n, 2 * mb.n_dst * DIN);   // du and d(sum) of the convolution
-        need_part(mb.n_dst, DIN, DIN);
-      }
-      if (tcsr_on) {
-        if ((rc = tcsr_gpu(t.get(), mb, S, tkeys, false, mt.tptr, gidx))) return rc;
-      } else build_csrs(S, tkeys, [&](auto&& emit) {
-        for (int64_t pos = 0; pos < mb.n_dst; ++pos)
-          for (int32_t m = mb.h_msg_ptr[pos]; m < mb.h_msg_ptr[pos + 1]; ++m) {
-            const uint32_t code = mb.h_msg_src[m];
-            emit((int)(code >> IGN_SLOT_SHIFT), (int64_t)(code & IGN_ROW_MASK), mb.h_order[pos]);
-          }
-      }, tptr, tidx);
-      ga_n = std::max(ga_n, mb.n_dst * 3 * H);
-      gu_n = std::max(gu_n, mb.n_dst * 3 * H);
-      dx_n = std::max(dx_n, mb.n_dst * DIN);
-      need_part(mb.n_dst, std::max(DIN, H), 3 * H);
-    }
-    need_part(std::max<int64_t>(mb.n_steps, mb.n_dst), 1, 3 * H);   // colsum
-    for (int s = 0; s < S; ++s) {
-      const int se = mp.src[s].entity;
-      const MsgNN& nn = mp.nn[s];
-      const int64_t rows_s = tkeys[s];
-      if (gidx) {
-        mt.tidx.push_back(gidx);   // (mt.tptr[s] set by tcsr_gpu)
-      } else {
-        int32_t *dp = nullptr, *di = nullptr;
-        if ((rc = tupload(t.get(), &dp, tptr[s])) || (rc = tupload(t.get(), &di, tidx[s]))) return rc;
-        mt.tptr.push_back(dp);
-        mt.tidx.push_back(di);
-      }
-      mt.trows.push_back(rows_s);
-      if (nn.layers.empty()) continue;
-      // message network (GM:440-475): buffers for its backward, and the state row -> edge CSRs
-      const int64_t ne = mb.n_edges[s];
-      int widest = nn.din_pad;
-      for (size_t l = 0; l < nn.layers.size(); ++l) {
-        widest = std::max(widest, nn.layers[l].out);
-        need_part(ne, l == 0 ? nn.din : nn.layers[l].in, nn.layers[l].out);
-      }
-      dmsg_n = std::max(dmsg_n, ne * nn.dout());
-      mz_n = std::max(mz_n, ne * widest);
-      mdin_n = std::max(mdin_n, ne * nn.din);
-      hvec<int32_t> es(ne), ed(ne);
-      HIP_TRY(hipMemcpyAsync(es.data(), mb.d_edge_src[s], ne * sizeof(int32_t), hipMemcpyDeviceToHost, upload_stream()));
-      HIP_TRY(hipMemcpyAsync(ed.data(), mb.d_edge_dst[s], ne * sizeof(int32_t), hipMemcpyDeviceToHost, upload_stream()));
-      HIP_TRY(hipStreamSynchronize(upload_stream()));
-      HIP_TRY(upload_flush());
-      hvec<std::pair<int64_t, int32_t>> ks(ne), kd(ne);
-      for (int64_t e = 0; e < ne; ++e) {
-        ks[e] = {es[e], (int32_t)e};
-        kd[e] = {ed[e], (int32_t)e};
-      }
-      hvec<int32_t> p1, i1, p2, i2;
-      build_csr(b->rows[se] + b->halo[se], ks, p1, i1);   // sources may be halo rows (edge-cut)
-      build_csr(b->rows[mp.dst], kd, p2, i2);
-      if ((rc = tupload(t.get(), &mt.nsrc_ptr[s], p1)) || (rc = tupload(t.get(), &mt.nsrc_idx[s], i1)) ||
-          (rc = tupload(t.get(), &mt.ndst_ptr[s], p2)) || (rc = tupload(t.get(), &mt.ndst_idx[s], i2)))
-        return rc;
-    }
-    t->mp.push_back(std::move(mt));
+    if ((rc = enable_mp(p, b, t.get(), mi, tcsr_on))) return rc;
     bm.mark(mi == 0 ? "mp0" : mi == 1 ? "mp1" : "mp2+");
   }
-  if ((rc = talloc(t.get(), &t->ga, ga_n)) || (rc = talloc(t.get(), &t->gu, gu_n)) ||
-      (rc = talloc(t.get(), &t->dx, dx_n)) || (rc = talloc(t.get(), &t->dtab, dtab_n)))
-    return rc;
-  if (amsg_n && ((rc = talloc(t.get(), &t->adw, amsg_n)) || (rc = talloc(t.get(), &t->adv, amsg_n)) ||
-                 (rc = talloc(t.get(), &t->ads_src, arows_n)) || (rc = talloc(t.get(), &t->ads_dst, arows_n)) ||
-                 (rc = talloc(t.get(), &t->adw12, 2 * p->attn_F))))
-    return rc;
-  if (dmsg_n && ((rc = talloc(t.get(), &t->dmsg, dmsg_n)) || (rc = talloc(t.get(), &t->mz[0], mz_n)) ||
-                 (rc = talloc(t.get(), &t->mz[1], mz_n)) || (rc = talloc(t.get(), &t->mdin, mdin_n))))
-    return rc;
-  // readout
-  int64_t widest = p->ro_width;
-  for (size_t l = 0; l < p->dense.size(); ++l) {
-    const DenseP& d = p->dense[l];
-    widest = std::max<int64_t>(widest, d.out);
-    need_part(P, d.in, d.out);
-    if (l + 1 < p->dense.size()) {
-      float* f = nullptr;
-      if ((rc = talloc(t.get(), &f, P * d.out))) return rc;
-      t->act.push_back(f);
-    }
-  }
-  if ((rc = talloc(t.get(), &t->dz[0], P * widest)) || (rc = talloc(t.get(), &t->dz[1], P * widest))) return rc;
-  if (p->ro_in.size() > 1 &&
-      ((rc = talloc(t.get(), &t->ro_x, P * p->ro_width)) || (rc = talloc(t.get(), &t->dro, P * p->ro_width))))
-    return rc;
-  // readout operations (GM:605-655)
-  t->dT.assign(p->ro_t.size(), nullptr);
-  {
-    int64_t rz_n = 0, rcat_n = 0, ties_n = 0;
-    for (size_t k = 0; k < p->ro_ops.size(); ++k) {
-      const RoOp& op = p->ro_ops[k];
-      const RoBatchOp& bo = b->ro[k];
-      const int nout = op.type == IGN_RO_EXTEND ? 2 : 1;
-      for (int j = 0; j < nout; ++j) {
-        const RoTensor& to = p->ro_t[op.out + j];
-        if ((rc = talloc(t.get(), &t->dT[op.out + j], space_rows(p, b, to) * to.width))) return rc;
-      }
-      const int64_t n = space_rows(p, b, p->ro_t[op.in[0]]);
-      if (op.type == IGN_RO_NEURAL_NETWORK) {
-        int widest = op.in_width, K = op.in_width;
-        for (auto& d : op.layers) {
-          widest = std::max(widest, d.out);
-          need_part(n, K, d.out);
-          K = d.out;
-        }
-        rz_n = std::max(rz_n, n * widest);
-        if (op.in.size() > 1) rcat_n = std::max(rcat_n, n * op.in_width);
-      } else if (op.type == IGN_RO_POOLING) {
-        ties_n = std::max(ties_n, (int64_t)b->G * p->ro_t[op.in[0]].width);
-      } else if (op.type == IGN_RO_EXTEND) {
-        for (int j = 0; j < 2; ++j) {
-          const std::vector<int32_t>& ix = bo.h_idx[j];
-          hvec<std::pair<int64_t, int32_t>> kv(ix.size());
-          for (size_t e2 = 0; e2 < ix.size(); ++e2) kv[e2] = {ix[e2], (int32_t)e2};
-          hvec<int32_t> ptr, idx;
-          build_csr(space_rows(p, b, p->ro_t[op.in[j]]), kv, ptr, idx);
-          int32_t *dp = nullptr, *di = nullptr;
-          if ((rc = tupload(t.get(), &dp, ptr)) || (rc = tupload(t.get(), &di, idx))) return rc;
-          t->rx_ptr.push_back(dp);
-          t->rx_idx.push_back(di);
-        }
-      }
-    }
-    if ((rz_n && ((rc = talloc(t.get(), &t->rz[0], rz_n)) || (rc = talloc(t.get(), &t->rz[1], rz_n)))) ||
-        (rcat_n && (rc = talloc(t.get(), &t->rcat, rcat_n))) || (ties_n && (rc = talloc(t.get(), &t->rties, ties_n))))
-      return rc;
-  }
-  if ((rc = talloc(t.get(), &t->part, part_n)) || (rc = talloc(t.get(), &t->bsum, (32 + 1) * 3 * 32))) return rc;
-  if (const char* v = getenv("IGN_DEFER_WGRAD"); !v || atoi(v) != 0) {
-    // the per-instance weight gradients of the plain sum and ordered MPs (ign_backward_mp): one slot
-    // per (gradient tensor, shape), room for every instance of a backward
-    struct Want { int64_t c, cb; int M, N, ones; int64_t chunks; };
-    std::vector<Want> want;
-    auto add = [&](int64_t c, int64_t cb, int M, int N, int64_t rows, int64_t min_slots = 0) {
-      const int ones = cb >= 0;
-      const int64_t ch = std::max(tsgemm_chunks(rows, M, N, ones), min_slots) * p->T;
-      for (auto& w : want)
-        if (w.c == c && w.cb == cb && w.M == M && w.N == N) { w.chunks += ch; return; }
-      want.push_back({c, cb, M, N, ones, ch});
-    };
-    for (size_t mi = 0; mi < p->mps.size(); ++mi) {
-      const MPP& mp = p->mps[mi];
-      const MPB& mb = b->mp[mi];
-      const CellP& cp = p->cells[mp.cell];
-      bool nets = false;
-      for (auto& nn : mp.nn) nets = nets || !nn.layers.empty();
-      if (nets || mp.feature_concat) continue;
-      const int H = cp.H, H3 = 3 * cp.H, DIN = mp.din;
-      if (mp.sorted) {
-        for (size_t s2 = 0; s2 < mp.src.size(); ++s2) add(cp.off_k, -1, DIN, H3, t->mp[mi].trows[s2]);
-      } else if (mp.aggr == IGN_AGGR_SUM) {
-        const int64_t fw = sum_bwd_fused_waves(mb.n_dst, DIN, H);   // the fused sum backward's partials
-        add(cp.off_k, cp.off_b, DIN, H3, mb.n_dst, fw);
-        add(cp.off_rk, cp.off_b + H3, H, H3, mb.n_dst, fw);
-      }
-    }
-    for (size_t mi = 0; mi < p->mps.size(); ++mi) {   // the fused ordered backward's partials
-      const MPP& mp = p->mps[mi];
-      const CellP& cp = p->cells[mp.cell];
-      if (!mp.sorted || !p->bwd_fuse || !seq_bwd_fused_supported(cp.H)) continue;
-      const int64_t tiles = (b->mp[mi].n_dst + 15) / 16;
-      const int64_t waves = std::min<int64_t>((tiles + 3) / 4 * 4, kBwdPartialWaves) * p->T;   // upper bound
-      bool found = false;
-      for (auto& d : t->defer_seq)
-        if (d.cell == mp.cell) { d.cap += waves; found = true; }
-      if (!found) t->defer_seq.push_back({mp.cell, cp.H, nullptr, waves, 0});
-    }
-    for (auto& d : t->defer_seq)
-      if ((rc = talloc(t.get(), &d.part, (d.cap + kTsReduceSegs) * (int64_t)(d.H + 2) * 3 * d.H))) return rc;
-    for (auto& w : want) {
-      TrainState::DeferredGrad d{w.c, w.cb, w.M, w.N, w.ones, nullptr, w.chunks, 0};
-      if ((rc = talloc(t.get(), &d.part, (w.chunks + kTsReduceSegs) * (int64_t)(w.M + w.ones) * w.N))) return rc;
-      t->defer.push_back(d);
-    }
-  }
+  const TrainScratch z = train_scratch(p, b);
+  if ((rc = alloc_mp_scratch(p, t.get(), z)) || (rc = alloc_readout(p, b, t.get(), z))) return rc;
+  if ((rc = talloc(t.get(), &t->part, z.part)) || (rc = talloc(t.get(), &t->bsum, (32 + 1) * 3 * 32))) return rc;
+  if (const char* v = getenv("IGN_DEFER_WGRAD"); !v || atoi(v) != 0)
+    if ((rc = alloc_deferred(p, b, t.get()))) return rc;
   bm.mark("rest");
   HIP_TRY(hipStreamSynchronize(upload_stream()));   // IGN_POOL_POISON fills have landed
   HIP_TRY(upload_flush());                           // (and every staged copy)

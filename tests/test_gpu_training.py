@@ -88,6 +88,21 @@ def test_gradients_synthetic_graph():
     _check(desc, dims, graphs, [np.asarray(l, np.float32) for l in labels], prm)
 
 
+def test_gradients_duplicate_positions():
+    """test_gpu_parity's duplicate-position graph through the training step: two links at position 0
+    of path 0 (one pre-summed table row), a hole at position 1, one link at position 2.  The source
+    row -> steps table of such an MP is always built on the host, and the backward must hand the
+    summed row's gradient to both links."""
+    desc = model_examples.routenet(hidden=16, iterations=2)
+    dims = {"link_capacity": 1, "traffic": 1, "adj_links_paths": 0, "adj_paths_links": 0}
+    x = {"link_capacity": [0.5, -0.3, 0.8], "traffic": [0.2, -0.4],
+         "src_adj_links_paths": [0, 1, 2, 2], "dst_adj_links_paths": [0, 0, 0, 1], "seq_link_path": [0, 0, 2, 0],
+         "src_adj_paths_links": [0, 1, 0], "dst_adj_paths_links": [0, 1, 2], "seq_path_link": [0, 0, 0],
+         "num_link": 3, "num_path": 2}
+    prm = MPPlan.from_model_info(Model_information(copy.deepcopy(desc), dims)).init_params(3, bias_scale=0.2)
+    _check(desc, dims, [x], [np.asarray([0.3, -0.1], np.float32)], prm)
+
+
 def test_backward_extreme_scales():
     """The ordered backward's split-fp16 dh = du U^T (train_kernels.hip) scales du per row by Sd and
     folds Uᵀ's pack scale sigma_t into the seed / unseed powers of two: with a tiny recurrent kernel
