@@ -103,6 +103,10 @@ class DenseOracle:
 
     # ------------------------------------------------------------------------------------
     def forward_graph(self, x: dict) -> np.ndarray:
+        return self._readout(self.final_states(x), x)
+
+    def final_states(self, x: dict) -> dict:
+        """{entity: [num, H]} after the T message-passing iterations (what the readout reads)."""
         dt = self.dtype
         state = {}
         for ent in self.d["entities"]:                                   # AUX:140-159
@@ -123,7 +127,7 @@ class DenseOracle:
             for stage in mp_cfg["stages"]:                                # GM:410
                 for mp in stage["stage_mp"]:                              # GM:414
                     self._message_passing(mp, state, x)
-        return self._readout(state, x)
+        return state
 
     def forward(self, graphs: list) -> np.ndarray:
         """model_fn's per-graph loop + reshape(-1) + concat (GM:712-724)."""

@@ -61,6 +61,29 @@ def test_predict_networks_match_dense_oracle(case):
     _close(cpu_oracle.cpu_forward(plan, graphs, prm, 2), ref, TOL32)
 
 
+def _width_cases():
+    from tests.width_cases import CASES
+    return sorted(CASES)
+
+
+@pytest.mark.parametrize("case", _width_cases())
+def test_unequal_widths_and_wide_features_match_dense_oracle(case):
+    """tests/width_cases.py: message width != destination width, axis-2 slices of different widths, message
+    networks on inputs of different widths, features of several columns (the IEEE build of this restatement
+    is the yardstick of _ieee_tol, so it has to be right at these shapes too)."""
+    from tests.width_cases import case_inputs, reference
+    desc, dims, _, plan, graphs, _, prm = case_inputs(case)
+    ref, _ = reference(case)
+    assert np.ptp(ref) > 1e-3
+    if case.startswith("msgnet_"):   # no message networks in this restatement: refused, not computed without them
+        with pytest.raises(cpu_oracle.OracleError, match="message networks are not restated"):
+            cpu_oracle.cpu_forward(plan, graphs, prm, 2, float64=True)
+        return
+    _close(cpu_oracle.cpu_forward(plan, graphs, prm, 2, float64=True), ref, TOL64)
+    _close(cpu_oracle.cpu_forward(plan, graphs, prm, 2), ref, TOL32)
+    _close(cpu_oracle.cpu_forward(plan, graphs, prm, 0, ieee=True), ref, TOL32)
+
+
 @pytest.mark.parametrize("threads", [1, 3])
 def test_one_large_graph_parallel_over_destinations(threads):
     desc, dims, mi, graphs, _ = workloads.make_synthetic_inputs(n_nodes=2000, iterations=3, window=64)
