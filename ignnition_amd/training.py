@@ -145,6 +145,13 @@ class Trainer:
             if tick:
                 t2 = tick()
                 prof["loss_wait"] += t2 - t1
+            # sum(model.losses) is part of this step's total loss (GM:749-753): read at the parameters the
+            # step starts from, before the update below (the stream is idle here, the loss was just read)
+            reg = self.engine.l2_loss() if want_loss else None
+            if tick:
+                t1 = tick()
+                prof["l2_wait"] += t1 - t2
+                t2 = t1
             b.backward(dpred, self.grads)
             if tick:
                 t3 = tick()
@@ -167,9 +174,7 @@ class Trainer:
             if tick:
                 t5 = tick()
                 prof["close"] += t5 - t4
-        reg = self.engine.l2_loss() if want_loss else None
         if tick:
-            prof["l2_wait"] += tick() - t5
             prof["steps"] += 1
         return {"loss": loss, "regularization_loss": reg, "total_loss": loss + reg if want_loss else None,
                 "learning_rate": lr, "step": self.iterations}
