@@ -89,6 +89,11 @@ class Stats(C.Structure):
                 ("bytes", C.c_double * 8), ("mfma_bf16", C.c_double * 8), ("mfma_f32", C.c_double * 8)]
 
 
+class OptimizerDesc(C.Structure):
+    _fields_ = [("kind", i32), ("nesterov", i32), ("centered", i32), ("reserved", i32), ("momentum", f32),
+                ("rho", f32), ("beta_1", f32), ("beta_2", f32), ("epsilon", f32), ("initial_accumulator_value", f32)]
+
+
 KERNEL_KINDS = ["init_state", "seq_gru", "sum_gru", "readout", "project", "other", "mp_resident"]
 
 MSG_INPUT = {"hs_source": 0, "hs_dest": 1, "edge_params": 2}
@@ -110,7 +115,8 @@ SYMBOLS = ["ign_abi_version", "ign_last_error", "ign_device_count", "ign_plan_cr
            "ign_dataset_error", "ign_dataset_gather", "ign_dataset_get", "ign_dataset_batch_create",
            "ign_dataset_batch_get", "ign_dataset_batch_get_narrow", "ign_dataset_batch_destroy", "ign_plan_create_json", "ign_plan_describe_json", "ign_forward_train_begin", "ign_forward_train_mp",
            "ign_forward_train_end", "ign_backward_begin", "ign_backward_mp", "ign_backward_end",
-           "ign_batch_train_buffers", "ign_batch_read_predictions", "ign_batch_resident_info"]
+           "ign_batch_train_buffers", "ign_batch_read_predictions", "ign_batch_resident_info",
+           "ign_loss_kind", "ign_optimizer_kind", "ign_loss", "ign_optimizer_num_slots", "ign_optimizer_step"]
 
 ABI_VERSION = 13
 PART = {"all": 0, "interior": 1, "boundary": 2}
@@ -186,6 +192,11 @@ def _load():
         "ign_batch_train_buffers": (C.c_int, [VP, i32, P(VP), P(VP)]),
         "ign_batch_read_predictions": (C.c_int, [VP, VP, VP]),
         "ign_batch_resident_info": (C.c_int, [VP, P(ResidentInfo)]),
+        "ign_loss_kind": (C.c_int, [C.c_char_p, P(i32)]),
+        "ign_optimizer_kind": (C.c_int, [C.c_char_p, P(i32)]),
+        "ign_loss": (C.c_int, [VP, i32, VP, VP, i64, VP, P(C.c_double)]),
+        "ign_optimizer_num_slots": (C.c_int, [P(OptimizerDesc), P(i32), P(f32)]),
+        "ign_optimizer_step": (C.c_int, [VP, P(OptimizerDesc), VP, P(VP), i32, i64, f32]),
     }
     # an A/B build of an older tree may lack newer entry points: only the A/B tools, which set
     # IGN_AB_LIB=1 next to IGN_LIB_PATH, skip them; any other library must export every symbol

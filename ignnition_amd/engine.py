@@ -457,6 +457,20 @@ class Engine:
         check(lib.ign_adam_step(self.handle, _ptr(grads), _ptr(m), _ptr(v), int(iteration), lr, beta1, beta2, epsilon))
         self.params_version += 1
 
+    def loss(self, kind: int, pred, labels, dpred, want_loss: bool = True) -> float:
+        """``mse_loss`` for any lowered Keras loss (``kind``: ign_loss_kind of its name; 0 is mse_loss itself)."""
+        out = C.c_double()
+        check(lib.ign_loss(self.handle, int(kind), _ptr(pred), _ptr(labels), labels.numel(), _ptr(dpred),
+                           C.byref(out) if want_loss else None))
+        return out.value if want_loss else None
+
+    def optimizer_step(self, desc, grads, slots, iteration: int, lr: float):
+        """``adam_step`` for any lowered Keras optimizer: ``desc`` an ``_lib.OptimizerDesc``, ``slots`` its
+        ign_optimizer_num_slots device buffers of n_params floats, in that call's order."""
+        arr = (C.c_void_p * max(1, len(slots)))(*[_ptr(s) for s in slots])
+        check(lib.ign_optimizer_step(self.handle, C.byref(desc), _ptr(grads), arr, len(slots), int(iteration), lr))
+        self.params_version += 1
+
     def replicas(self, n: int) -> list:
         """``n`` more plans of this model on this device (each its own HIP stream), created once and
         kept; their parameters follow this engine's (SplitBatch re-syncs them when they changed)."""

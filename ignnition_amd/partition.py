@@ -313,8 +313,8 @@ class EdgeCutTraining:
     rows are stale, the owners send them (as EdgeCutForward does, into the version's halo rows).
     Backward: the gradient of a halo row belongs to its owner -- after each MP instance, the halo
     rows of every source entity's current gradient go back to their owners (the reverse all-to-all),
-    who add them to their rows (peer by peer: deterministic), and are zeroed.  The loss is the MSE
-    over every rank's predictions, the parameter gradients are summed over ranks (each rank's l2
+    who add them to their rows (peer by peer: deterministic), and are zeroed.  The loss is the mean
+    (MSE, or ``step``'s ``loss_kind``) over every rank's predictions, the parameter gradients are summed over ranks (each rank's l2
     terms weighted 1/ranks), so one step equals the whole graph's step up to summation order."""
 
     def __init__(self, engine: Engine, parts: list, comm):
@@ -382,8 +382,10 @@ class EdgeCutTraining:
                     grads[i].index_add_(0, self.send_idx[i][name][a:b], recvs[i][a:b])
             grads[i][h.n_owned:].zero_()
 
-    def step(self, labels: list, to_host: bool = True):
-        """Forward + loss + backward; ``labels``: per partition, its owned predictions' labels.
+    def step(self, labels: list, to_host: bool = True, loss_kind: int = 0):
+        """Forward + loss + backward; ``labels``: per partition, its owned predictions' labels;
+        ``loss_kind``: ign_loss_kind of the loss (default MeanSquaredError; every lowered loss is a
+        mean of element terms, so the n_local / n_total rescaling below holds for all of them).
         Returns (loss over all ranks, summed parameter gradient, per-partition predictions or
         None when not ``to_host``)."""
         torch = self.torch
@@ -409,7 +411,9 @@ class EdgeCutTraining:
         dpreds = []
         for b, y in zip(self.batches, ys):
             d = torch.empty_like(y)
-            loss += self.engine.mse_loss(b.predictions_ptr(), y, d) * y.numel() / n_total
+            local = (self.engine.mse_loss(b.predictions_ptr(), y, d) if loss_kind == 0
+                     else self.engine.loss(loss_kind, b.predictions_ptr(), y, d))
+            loss += local * y.numel() / n_total
             dpreds.append(d * (y.numel() / n_total))   # d(mean over every rank) = d(local mean) n_local / N
         loss = self._sum_scalar(loss)
         world = self.comm.world

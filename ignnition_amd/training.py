@@ -1,13 +1,20 @@
 """Training on the HIP engine: model_fn's TRAIN / EVAL branches (code/utils/generate_model.py:697-830,
 "GM") and the loop of train_and_evaluate (code/utils/framework_operations.py:108-166, "FO").
 
-* loss: ``learning_options.loss`` (MeanSquaredError, GM:745-753) over the batch's concatenated
-  flat predictions, plus the Dense l2 kernel regularizers (AUX:833-834).  The engine computes
-  it (``ign_mse_loss``, ``ign_l2_loss``).
+* loss: ``learning_options.loss`` (GM:745-753) over the batch's concatenated flat predictions,
+  plus the Dense l2 kernel regularizers (AUX:833-834).  The engine computes it: MeanSquaredError
+  (``ign_mse_loss``) or, through ``ign_loss``, MeanAbsoluteError, MeanAbsolutePercentageError,
+  MeanSquaredLogarithmicError, Huber, LogCosh, BinaryCrossentropy and Poisson with Keras' default
+  constructor arguments; ``ign_l2_loss`` for the regularizers.
 * gradients: ``ign_backward``, the HIP backward of the whole forward (tf.gradients, GM:790).
-* optimizer: ``learning_options.optimizer`` (GM:797-818).  Only Adam is lowered (``ign_adam_step``,
-  Keras semantics); the learning rate is a float or an ExponentialDecay schedule evaluated at
-  ``iterations`` (the global step, GM:816).
+* optimizer: ``learning_options.optimizer`` (GM:797-818), Keras optimizer_v2 semantics: Adam
+  (``ign_adam_step``) or, through ``ign_optimizer_step``, SGD (momentum, nesterov), RMSprop
+  (momentum, centered), Adagrad, Adadelta and Adamax.  Nadam, Ftrl, amsgrad and gradient clipping
+  are refused.  The learning rate is a float (default: the optimizer's own) or an ExponentialDecay,
+  PiecewiseConstantDecay, PolynomialDecay or InverseTimeDecay schedule evaluated at ``iterations``
+  (the global step, GM:816).
+* ``learning_options(model_info)`` parses all of this without a GPU and raises UnsupportedModel
+  for what is not lowered.
 * data parallel: with torch.distributed initialised, every rank trains on its own batches and
   the gradient is averaged with one all-reduce (RCCL on GPUs) before the update.
 * eval metrics (GM:755-785): label/prediction mean, MAE, MRE and the batch-mean r-squared
@@ -16,6 +23,7 @@
 
 from __future__ import annotations
 
+import ctypes as C
 import math
 import os
 import time
@@ -25,24 +33,53 @@ import numpy as np
 from .engine import UnsupportedModel
 from .generate_model import ComnetModel, _resolve
 
-SUPPORTED_LOSSES = ("MeanSquaredError",)
+SUPPORTED_LOSSES = ("MeanSquaredError", "MeanAbsoluteError", "MeanAbsolutePercentageError",
+                    "MeanSquaredLogarithmicError", "Huber", "LogCosh", "BinaryCrossentropy", "Poisson")
+SUPPORTED_SCHEDULES = ("ExponentialDecay", "PiecewiseConstantDecay", "PolynomialDecay", "InverseTimeDecay")
+
+# per optimizer: the hyper-parameters its Keras constructor takes beside learning_rate / name, with
+# Keras' defaults, and the default constant rate
+_OPTIMIZERS = {
+    "Adam": ({"beta_1": 0.9, "beta_2": 0.999, "epsilon": 1e-7}, 0.001),
+    "SGD": ({"momentum": 0.0, "nesterov": False}, 0.01),
+    "RMSprop": ({"rho": 0.9, "momentum": 0.0, "epsilon": 1e-7, "centered": False}, 0.001),
+    "Adagrad": ({"initial_accumulator_value": 0.1, "epsilon": 1e-7}, 0.001),
+    "Adadelta": ({"rho": 0.95, "epsilon": 1e-7}, 0.001),
+    "Adamax": ({"beta_1": 0.9, "beta_2": 0.999, "epsilon": 1e-7}, 0.001),
+}
+_REFUSED_KEYS = ("clipnorm", "clipvalue", "global_clipnorm")
 
 
 class LearningRate:
-    """``optimizer.learning_rate`` or ``optimizer.schedule`` (Keras ExponentialDecay)."""
+    """``optimizer.learning_rate`` or ``optimizer.schedule`` (Keras ExponentialDecay,
+    PiecewiseConstantDecay, PolynomialDecay, InverseTimeDecay), evaluated on the host at the step.
+    ``default``: the optimizer's own Keras rate where ``learning_rate`` is absent."""
 
-    def __init__(self, opt: dict):
+    def __init__(self, opt: dict, default: float = 0.001):
         sched = opt.get("schedule")
         self.kind = "constant"
-        self.lr0 = float(opt.get("learning_rate", 0.001))
+        self.lr0 = float(opt.get("learning_rate", default))
         if sched is not None:
             sched = dict(sched)
             kind = sched.pop("type")
-            if kind != "ExponentialDecay":
-                raise UnsupportedModel("learning-rate schedule %r is not lowered (ExponentialDecay only)" % kind)
+            if kind not in SUPPORTED_SCHEDULES:
+                raise UnsupportedModel("learning-rate schedule %r is not lowered (%s)" % (kind, ", ".join(SUPPORTED_SCHEDULES)))
             self.kind = kind
+            if kind == "PiecewiseConstantDecay":
+                self.boundaries = [float(b) for b in sched["boundaries"]]
+                self.values = [float(v) for v in sched["values"]]
+                if len(self.values) != len(self.boundaries) + 1:   # Keras' own check
+                    raise ValueError("PiecewiseConstantDecay: %d values for %d boundaries (one more is needed)"
+                                     % (len(self.values), len(self.boundaries)))
+                self.lr0 = self.values[0]
+                return
             self.lr0 = float(sched["initial_learning_rate"])
             self.decay_steps = float(sched["decay_steps"])
+            if kind == "PolynomialDecay":
+                self.end = float(sched.get("end_learning_rate", 1e-4))
+                self.power = float(sched.get("power", 1.0))
+                self.cycle = bool(sched.get("cycle", False))
+                return
             self.decay_rate = float(sched["decay_rate"])
             # Keras tests `if self.staircase:`; a JSON string such as "True" (QSJ:204) or even
             # "False" is truthy there
@@ -51,26 +88,117 @@ class LearningRate:
     def __call__(self, step: int) -> float:
         if self.kind == "constant":
             return self.lr0
+        if self.kind == "PiecewiseConstantDecay":
+            for b, v in zip(self.boundaries, self.values):
+                if step <= b:
+                    return v
+            return self.values[-1]
+        if self.kind == "PolynomialDecay":
+            steps = self.decay_steps
+            if self.cycle:
+                steps *= max(1, math.ceil(step / self.decay_steps))
+            else:
+                step = min(step, steps)
+            return (self.lr0 - self.end) * (1 - step / steps) ** self.power + self.end
         p = step / self.decay_steps
         if self.staircase:
             p = math.floor(p)
+        if self.kind == "InverseTimeDecay":
+            return self.lr0 / (1 + self.decay_rate * p)
         return self.lr0 * self.decay_rate ** p
+
+
+class LearningOptions:
+    """``learning_options`` lowered: ``loss`` / ``loss_kind`` (ign_loss_kind), ``optimizer`` /
+    ``desc`` (an ``_lib.OptimizerDesc``), its ``num_slots`` buffers starting at ``slot_init``, the
+    hyper-parameters as given or defaulted (``hyper``) and the ``lr`` schedule."""
+
+    def __init__(self, loss, loss_kind, optimizer, desc, num_slots, slot_init, hyper, lr):
+        self.loss, self.loss_kind, self.optimizer, self.desc = loss, loss_kind, optimizer, desc
+        self.num_slots, self.slot_init, self.hyper, self.lr = num_slots, slot_init, hyper, lr
+
+
+def _kind(fn, name) -> int:
+    from . import _lib
+    k = _lib.i32()
+    rc = fn(str(name).encode(), C.byref(k))
+    if rc != 0:   # the library's message lists the supported names
+        raise UnsupportedModel(_lib.lib.ign_last_error().decode(errors="replace"))
+    return k.value
+
+
+def learning_options(model_info) -> LearningOptions:
+    """``learning_options`` of a model description -> LearningOptions, without a GPU.  Raises
+    UnsupportedModel for a loss, optimizer or schedule that is not lowered, for gradient clipping
+    and Adam's amsgrad, and for a key the (non-Adam) optimizer's Keras constructor does not take."""
+    from . import _lib
+    loss = model_info.get_loss()
+    loss_kind = _kind(_lib.lib.ign_loss_kind, loss)
+    opt = dict(model_info.get_optimizer())
+    name = opt.get("type")
+    kind = _kind(_lib.lib.ign_optimizer_kind, name)
+    defaults, rate = _OPTIMIZERS[name]
+    for k in _REFUSED_KEYS:
+        if k in opt:
+            raise UnsupportedModel("optimizer option %r is not lowered (gradient clipping)" % k)
+    if name == "Adam":
+        if opt.get("amsgrad"):
+            raise UnsupportedModel("Adam's amsgrad is not lowered")
+    else:
+        unknown = sorted(set(opt) - set(defaults) - {"type", "schedule", "learning_rate", "name"})
+        if unknown:
+            raise UnsupportedModel("%s does not take %s (its Keras constructor: learning_rate, %s)"
+                                   % (name, ", ".join(repr(k) for k in unknown), ", ".join(defaults)))
+    hyper = {k: type(d)(opt.get(k, d)) if not isinstance(d, bool) else bool(opt.get(k, d)) for k, d in defaults.items()}
+    desc = _lib.OptimizerDesc(kind=kind, nesterov=int(hyper.get("nesterov", False)), centered=int(hyper.get("centered", False)),
+                              reserved=0, momentum=hyper.get("momentum", 0.0), rho=hyper.get("rho", 0.0),
+                              beta_1=hyper.get("beta_1", 0.0), beta_2=hyper.get("beta_2", 0.0),
+                              epsilon=hyper.get("epsilon", 0.0),
+                              initial_accumulator_value=hyper.get("initial_accumulator_value", 0.0))
+    if hyper.get("momentum", 0.0) < 0 or hyper.get("momentum", 0.0) > 1:   # Keras' own check
+        raise ValueError("momentum must be between 0 and 1")
+    n, init = _lib.i32(), _lib.f32()
+    _lib.check(_lib.lib.ign_optimizer_num_slots(C.byref(desc), C.byref(n), C.byref(init)))
+    return LearningOptions(loss, loss_kind, name, desc, n.value, init.value, hyper, LearningRate(opt, rate))
+
+
+def host_loss(kind: int, p, y) -> float:
+    """The loss of ``kind`` in float64 on the host (Keras' default constructor arguments), as the
+    engine's ign_loss defines it: the mean over the flat predictions."""
+    p, y = np.asarray(p, np.float64).reshape(-1), np.asarray(y, np.float64).reshape(-1)
+    eps, d = 1e-7, p - y
+    name = SUPPORTED_LOSSES[kind]
+    if name == "MeanSquaredError":
+        t = d * d
+    elif name == "MeanAbsoluteError":
+        t = np.abs(d)
+    elif name == "MeanAbsolutePercentageError":
+        t = 100.0 * np.abs(d) / np.maximum(np.abs(y), eps)
+    elif name == "MeanSquaredLogarithmicError":
+        t = (np.log1p(np.maximum(p, eps)) - np.log1p(np.maximum(y, eps))) ** 2
+    elif name == "Huber":
+        t = np.where(np.abs(d) <= 1.0, 0.5 * d * d, np.abs(d) - 0.5)
+    elif name == "LogCosh":
+        t = np.abs(d) + np.log1p(np.exp(-2.0 * np.abs(d))) - math.log(2.0)
+    elif name == "BinaryCrossentropy":
+        q = np.clip(p, eps, 1.0 - eps)
+        t = -(y * np.log(q + eps) + (1.0 - y) * np.log(1.0 - q + eps))
+    else:
+        t = p - y * np.log(p + eps)
+    return float(np.mean(t))
 
 
 class Trainer:
     def __init__(self, model_info, params: dict | None = None, device: int = 0, seed: int = 0, dist=None):
+        lo = learning_options(model_info)   # refuses what is not lowered before torch or the GPU are touched
         import torch
         self.torch = torch
-        loss = model_info.get_loss()
-        if loss not in SUPPORTED_LOSSES:
-            raise UnsupportedModel("loss %r is not lowered (%s)" % (loss, ", ".join(SUPPORTED_LOSSES)))
-        opt = dict(model_info.get_optimizer())
-        if opt.get("type") != "Adam":
-            raise UnsupportedModel("optimizer %r is not lowered (Adam only)" % opt.get("type"))
-        self.lr = LearningRate(opt)
-        self.beta1 = float(opt.get("beta_1", 0.9))
-        self.beta2 = float(opt.get("beta_2", 0.999))
-        self.epsilon = float(opt.get("epsilon", 1e-7))
+        self.options = lo
+        self.loss_kind = lo.loss_kind
+        self.adam = lo.optimizer == "Adam"
+        self.lr = lo.lr
+        if self.adam:
+            self.beta1, self.beta2, self.epsilon = lo.hyper["beta_1"], lo.hyper["beta_2"], lo.hyper["epsilon"]
         self.model_info = model_info
         torch.cuda.set_device(device)
         self.model = ComnetModel(model_info, device=device, params=params, seed=seed)
@@ -78,8 +206,12 @@ class Trainer:
         eng.set_stream(torch.cuda.current_stream().cuda_stream)   # torch copies / RCCL stream-ordered
         dev = torch.device("cuda", device)
         self.grads = torch.zeros(eng.n_params, dtype=torch.float32, device=dev)
-        self.m = torch.zeros_like(self.grads)
-        self.v = torch.zeros_like(self.grads)
+        # Adam's moments are m and v; any other optimizer's slot buffers (ign_optimizer_num_slots' order,
+        # all starting at its value: Adagrad's accumulator, alignment gaps included) are in slots
+        self.m = torch.zeros_like(self.grads) if self.adam else None
+        self.v = torch.zeros_like(self.grads) if self.adam else None
+        self.slots = [self.m, self.v] if self.adam else [torch.full_like(self.grads, lo.slot_init)
+                                                        for _ in range(lo.num_slots)]
         self.dpred = None
         self.device = dev
         self.dist = dist
@@ -141,7 +273,10 @@ class Trainer:
                 t1 = tick()
                 prof["forward_enqueue"] += t1 - t0
             dpred = self.torch.empty_like(y)
-            loss = self.engine.mse_loss(b.predictions_ptr(), y, dpred, want_loss=want_loss)
+            if self.loss_kind == 0:
+                loss = self.engine.mse_loss(b.predictions_ptr(), y, dpred, want_loss=want_loss)
+            else:
+                loss = self.engine.loss(self.loss_kind, b.predictions_ptr(), y, dpred, want_loss=want_loss)
             if tick:
                 t2 = tick()
                 prof["loss_wait"] += t2 - t1
@@ -165,7 +300,10 @@ class Trainer:
                     self.dist.all_reduce(self.grads)
                 self.grads /= self.dist.get_world_size()
             lr = self.lr(self.iterations)
-            self.engine.adam_step(self.grads, self.m, self.v, self.iterations, lr, self.beta1, self.beta2, self.epsilon)
+            if self.adam:
+                self.engine.adam_step(self.grads, self.m, self.v, self.iterations, lr, self.beta1, self.beta2, self.epsilon)
+            else:
+                self.engine.optimizer_step(self.options.desc, self.grads, self.slots, self.iterations, lr)
             self.iterations += 1
         finally:
             if tick:
@@ -197,7 +335,7 @@ class Trainer:
             finally:
                 b.close()
             y = np.concatenate([np.asarray(l, np.float64).reshape(-1) for l in labels])
-            losses.append(float(np.mean((y - p) ** 2)))
+            losses.append(float(np.mean((y - p) ** 2)) if self.loss_kind == 0 else host_loss(self.loss_kind, p, y))
             yd = np.asarray(self._denorm(y), np.float64)
             pd = np.asarray(self._denorm(p), np.float64)
             labels_all.append(yd)

@@ -365,6 +365,59 @@ int  ign_l2_loss(ign_plan* plan, double* loss);
  * lr_t = lr sqrt(1 - beta2^(it+1)) / (1 - beta1^(it+1)); m, v: caller-owned device state. */
 int  ign_adam_step(ign_plan* plan, const float* grads, float* m, float* v, int64_t iteration, float lr,
                    float beta1, float beta2, float epsilon);
+/* The Keras losses and optimizers the engine lowers, by the names a model description uses
+ * (learning_options.loss, optimizer.type; GM:745-747, 796-814).  The two *_kind calls are the one
+ * name table and need no GPU; an unknown name returns IGN_ERR_UNSUPPORTED and the error string
+ * lists the supported names. */
+enum ign_loss {
+  IGN_LOSS_MEAN_SQUARED_ERROR = 0,
+  IGN_LOSS_MEAN_ABSOLUTE_ERROR = 1,
+  IGN_LOSS_MEAN_ABSOLUTE_PERCENTAGE_ERROR = 2,
+  IGN_LOSS_MEAN_SQUARED_LOGARITHMIC_ERROR = 3,
+  IGN_LOSS_HUBER = 4,               /* delta 1 */
+  IGN_LOSS_LOG_COSH = 5,
+  IGN_LOSS_BINARY_CROSSENTROPY = 6, /* from_logits false */
+  IGN_LOSS_POISSON = 7
+};
+enum ign_optimizer {
+  IGN_OPT_ADAM = 0,
+  IGN_OPT_SGD = 1,
+  IGN_OPT_RMSPROP = 2,
+  IGN_OPT_ADAGRAD = 3,
+  IGN_OPT_ADADELTA = 4,
+  IGN_OPT_ADAMAX = 5
+};
+int  ign_loss_kind(const char* name, int32_t* kind);
+int  ign_optimizer_kind(const char* name, int32_t* kind);
+/* The loss of `kind` with Keras' default constructor arguments: the mean over the n flat
+ * predictions of its element term (host double, may be NULL: then no host wait), and
+ * dpred = d loss / d pred.  Kind 0 is ign_mse_loss. */
+int  ign_loss(ign_plan* plan, int32_t kind, const float* pred, const float* labels, int64_t n, float* dpred,
+              double* loss);
+/* An optimizer's configuration: the hyper-parameters of its Keras constructor that it reads
+ * (the others are ignored), as float like ign_adam_step's. */
+typedef struct {
+  int32_t kind;                    /* enum ign_optimizer */
+  int32_t nesterov;                /* SGD */
+  int32_t centered;                /* RMSprop */
+  int32_t reserved;                /* 0 */
+  float momentum;                  /* SGD, RMSprop */
+  float rho;                       /* RMSprop, Adadelta */
+  float beta_1;                    /* Adam, Adamax */
+  float beta_2;                    /* Adam, Adamax */
+  float epsilon;                   /* all but SGD */
+  float initial_accumulator_value; /* Adagrad */
+} ign_optimizer_desc;
+/* The slot buffers (n_params floats each, caller-owned device memory) the configuration needs and
+ * the value all of them start at, in this order:
+ *   Adam m, v;  SGD v (momentum > 0);  RMSprop rms, then mg (centered), then mom (momentum > 0);
+ *   Adagrad acc (starts at initial_accumulator_value);  Adadelta acc, accu;  Adamax m, u. */
+int  ign_optimizer_num_slots(const ign_optimizer_desc* desc, int32_t* n, float* init_value);
+/* One Keras optimizer_v2 update of the plan's parameters (in place) at `iteration` (t = iteration + 1)
+ * with the rate `lr`; Adam is ign_adam_step.  RMSprop's centered variance is clamped at 0, which
+ * departs from Keras only where Keras would produce NaN. */
+int  ign_optimizer_step(ign_plan* plan, const ign_optimizer_desc* desc, const float* grads, float* const* slots,
+                        int32_t n_slots, int64_t iteration, float lr);
 /* Copy the current parameters (flat layout) to host. */
 int  ign_plan_get_params(ign_plan* plan, float* host_out);
 
