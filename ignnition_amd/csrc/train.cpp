@@ -7,10 +7,7 @@
 //                       the readout activations
 //   ign_backward        tf.gradients(total_loss, trainable_variables) (GM:790) for a given
 //                       dLoss/dpredictions, plus the Dense l2 regularizer terms (AUX:833-834)
-//   ign_mse_loss        MeanSquaredError over the batch's flat predictions (GM:716-753)
-//   ign_adam_step       Keras Adam with the host-evaluated ExponentialDecay rate (GM:797-818)
-//   ign_loss            the other Keras losses a description may name (GM:745-747), by kind
-//   ign_optimizer_step  the other Keras optimizers (SGD, RMSprop, Adagrad, Adadelta, Adamax), by desc
+// The loss, the regularizer's value and the optimizer update around them are learn.cpp.
 //
 // Backward schedule: readout Dense stack in reverse, then the MP instances of the forward in
 // reverse order.  Per entity one gradient buffer tracks dLoss/d(current version); an MP turns
@@ -242,6 +239,13 @@ int check_train(ign_plan* p, ign_batch* b) {
   if (!b->train) return fail(IGN_ERR_INVALID, "training not enabled on this batch (ign_batch_enable_training)");
   if (!p->params_set) return fail(IGN_ERR_INVALID, "parameters not set (ign_plan_set_params)");
   return set_device(p->device);
+}
+
+// the l2 kernel regularizer's gradient (AUX:833-834) of Dense layer d with K inputs:
+// grads[W] += 2 l2 scale W; nothing where the layer has none
+int add_l2_grad(const ign_plan* p, const DenseP& d, float* grads, float scale, int K, hipStream_t st) {
+  if (d.l2 != 0.f) HIP_TRY(launch_axpy(grads + d.off_w, p->d_params + d.off_w, 2.f * d.l2 * scale, (int64_t)K * d.out, st));
+  return IGN_OK;
 }
 
 // project every source of sorted MP mb into its table, from the given source states
@@ -950,12 +954,11 @@ int ign_backward_begin(ign_plan* p, ign_batch* b, const float* dpred, float* gra
       HIP_TRY(launch_tsgemm_add(A, d.in, t->dz[zi], d.out, P, d.in, d.out, t->part, grads + d.off_w,
                                 d.use_bias ? grads + d.off_b : nullptr, st));
     if (l > 0 && d.out == 1 && d.in % 4 == 0 && p->fuse_outer_bwd && dense_t_bf(p->dense[l - 1])) {
-      if (d.l2 != 0.f) HIP_TRY(launch_axpy(grads + d.off_w, p->d_params + d.off_w, 2.f * d.l2 * l2_scale, (int64_t)d.in * d.out, st));
+      if ((rc = add_l2_grad(p, d, grads, l2_scale, d.in, st))) return rc;
       xo = OuterRows{t->dz[zi], p->d_params + d.off_w, p->dense[l - 1].act, t->act[l - 1]};
       continue;   // zi stays: dz[zi] holds dz_out for the layer below
     }
-    if (!outer && d.l2 != 0.f)
-      HIP_TRY(launch_axpy(grads + d.off_w, p->d_params + d.off_w, 2.f * d.l2 * l2_scale, (int64_t)d.in * d.out, st));
+    if (!outer && (rc = add_l2_grad(p, d, grads, l2_scale, d.in, st))) return rc;
     float* out;
     int act = -1, acc = 0;
     const float* aprev = nullptr;
@@ -983,8 +986,7 @@ int ign_backward_begin(ign_plan* p, ign_batch* b, const float* dpred, float* gra
     if (outer) {   // the weight gradient on the rows dense_t just wrote over act[l], then its l2 term
       HIP_TRY(launch_tsgemm_add(A, d.in, xo.out, d.out, P, d.in, d.out, t->part, grads + d.off_w,
                                 d.use_bias ? grads + d.off_b : nullptr, st));
-      if (d.l2 != 0.f)
-        HIP_TRY(launch_axpy(grads + d.off_w, p->d_params + d.off_w, 2.f * d.l2 * l2_scale, (int64_t)d.in * d.out, st));
+      if ((rc = add_l2_grad(p, d, grads, l2_scale, d.in, st))) return rc;
     }
     xo = OuterRows{};
     zi = 1 - zi;
@@ -1014,7 +1016,7 @@ int ign_backward_begin(ign_plan* p, ign_batch* b, const float* dpred, float* gra
           const float* A = l > 0 ? bo.tmp[l - 1] : op.in.size() > 1 ? bo.cat : tensor(op.in[0]);
           HIP_TRY(launch_tsgemm_add(A, K, t->rz[rz], d.out, n, K, d.out, t->part, grads + d.off_w,
                                     d.use_bias ? grads + d.off_b : nullptr, st));
-          if (d.l2 != 0.f) HIP_TRY(launch_axpy(grads + d.off_w, p->d_params + d.off_w, 2.f * d.l2 * l2_scale, (int64_t)K * d.out, st));
+          if ((rc = add_l2_grad(p, d, grads, l2_scale, K, st))) return rc;
           if (l > 0) {
             HIP_TRY(launch_row_gemm_t_generic(t->rz[rz], n, d.out, p->d_params + d.off_w, K, t->rz[1 - rz], 0,
                                               op.layers[l - 1].act, bo.tmp[l - 1], st));
@@ -1247,7 +1249,7 @@ int ign_backward_end(ign_plan* p, ign_batch* b) {
       for (size_t l = 0; l < nn.layers.size(); ++l) {
         const DenseP& d = nn.layers[l];
         const int K = l == 0 ? nn.din : nn.layers[l - 1].out;
-        if (d.l2 != 0.f) HIP_TRY(launch_axpy(grads + d.off_w, p->d_params + d.off_w, 2.f * d.l2 * t->l2_scale, (int64_t)K * d.out, st));
+        if ((rc = add_l2_grad(p, d, grads, t->l2_scale, K, st))) return rc;
       }
   return IGN_OK;
 }
@@ -1265,177 +1267,6 @@ int ign_backward(ign_plan* p, ign_batch* b, const float* dpred, float* grads) {
   int rc = ign_backward_begin(p, b, dpred, grads, 1.f);
   while (!rc && b->train->b_ri >= 0) rc = ign_backward_mp(p, b);
   return rc ? rc : ign_backward_end(p, b);
-}
-
-int ign_mse_loss(ign_plan* p, const float* pred, const float* labels, int64_t n, float* dpred, double* loss) {
-  if (!p || !pred || !labels || !dpred) return fail(IGN_ERR_INVALID, "null argument");
-  if (n <= 0) return fail(IGN_ERR_INVALID, "empty prediction vector");
-  int rc = ensure_device(p);
-  if (rc) return rc;
-  constexpr int NB = 256;
-  if (!p->d_red) HIP_TRY(hipMalloc(&p->d_red, 1024 * sizeof(double)));
-  HIP_TRY(launch_mse(pred, labels, n, dpred, p->d_red, NB, p->stream));
-  if (loss) {
-    double h[NB];
-    HIP_TRY(hipMemcpyAsync(h, p->d_red, NB * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    double s = 0;
-    for (int i = 0; i < NB; ++i) s += h[i];
-    *loss = s / (double)n;
-  }
-  return IGN_OK;
-}
-
-int ign_l2_loss(ign_plan* p, double* loss) {
-  if (!p || !loss) return fail(IGN_ERR_INVALID, "null argument");
-  if (!p->params_set) return fail(IGN_ERR_INVALID, "parameters not set (ign_plan_set_params)");
-  int rc = ensure_device(p);
-  if (rc) return rc;
-  constexpr int NB = 64;
-  if (!p->d_red) HIP_TRY(hipMalloc(&p->d_red, 1024 * sizeof(double)));
-  double total = 0;
-  std::vector<const DenseP*> layers;   // readout and message-network Dense layers (model.losses)
-  for (auto& d : p->dense) layers.push_back(&d);
-  for (auto& mp : p->mps)
-    for (auto& nn : mp.nn)
-      for (auto& d : nn.layers) layers.push_back(&d);
-  for (const DenseP* dl : layers) {
-    const DenseP& d = *dl;
-    if (d.l2 == 0.f) continue;
-    HIP_TRY(launch_sumsq(p->d_params + d.off_w, (int64_t)d.in * d.out, p->d_red, NB, p->stream));
-    double h[NB];
-    HIP_TRY(hipMemcpyAsync(h, p->d_red, NB * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    double s = 0;
-    for (int i = 0; i < NB; ++i) s += h[i];
-    total += (double)d.l2 * s;
-  }
-  *loss = total;
-  return IGN_OK;
-}
-
-int ign_adam_step(ign_plan* p, const float* grads, float* m, float* v, int64_t iteration, float lr, float beta1,
-                  float beta2, float epsilon) {
-  if (!p || !grads || !m || !v) return fail(IGN_ERR_INVALID, "null argument");
-  if (!p->params_set) return fail(IGN_ERR_INVALID, "parameters not set (ign_plan_set_params)");
-  if (iteration < 0) return fail(IGN_ERR_INVALID, "negative iteration");
-  int rc = ensure_device(p);
-  if (rc) return rc;
-  const double tstep = (double)iteration + 1.0;
-  const double lr_t = (double)lr * std::sqrt(1.0 - std::pow((double)beta2, tstep)) / (1.0 - std::pow((double)beta1, tstep));
-  HIP_TRY(launch_adam(p->d_params, grads, m, v, p->n_params, (float)lr_t, beta1, beta2, epsilon, p->stream));
-  return repack(p);
-}
-
-// the one name table of the lowered Keras losses / optimizers (index = kind)
-static const char* const kLossNames[] = {"MeanSquaredError", "MeanAbsoluteError", "MeanAbsolutePercentageError",
-                                         "MeanSquaredLogarithmicError", "Huber", "LogCosh", "BinaryCrossentropy",
-                                         "Poisson"};
-static const char* const kOptimizerNames[] = {"Adam", "SGD", "RMSprop", "Adagrad", "Adadelta", "Adamax"};
-
-static int kind_of(const char* what, const char* const* names, size_t N, const char* name, int32_t* kind) {
-  if (!name || !kind) return fail(IGN_ERR_INVALID, "null argument");
-  std::string all;
-  for (size_t i = 0; i < N; ++i) {
-    if (!std::strcmp(name, names[i])) {
-      *kind = (int32_t)i;
-      return IGN_OK;
-    }
-    all += (i ? ", " : "") + std::string(names[i]);
-  }
-  return fail(IGN_ERR_UNSUPPORTED, "%s \"%s\" is not lowered (%s)", what, name, all.c_str());
-}
-
-int ign_loss_kind(const char* name, int32_t* kind) {
-  return kind_of("loss", kLossNames, sizeof(kLossNames) / sizeof(kLossNames[0]), name, kind);
-}
-
-int ign_optimizer_kind(const char* name, int32_t* kind) {
-  return kind_of("optimizer", kOptimizerNames, sizeof(kOptimizerNames) / sizeof(kOptimizerNames[0]), name, kind);
-}
-
-int ign_loss(ign_plan* p, int32_t kind, const float* pred, const float* labels, int64_t n, float* dpred, double* loss) {
-  if (kind == IGN_LOSS_MEAN_SQUARED_ERROR) return ign_mse_loss(p, pred, labels, n, dpred, loss);
-  if (!p || !pred || !labels || !dpred) return fail(IGN_ERR_INVALID, "null argument");
-  if (kind < 0 || kind > IGN_LOSS_POISSON) return fail(IGN_ERR_INVALID, "loss kind %d out of range", (int)kind);
-  if (n <= 0) return fail(IGN_ERR_INVALID, "empty prediction vector");
-  int rc = ensure_device(p);
-  if (rc) return rc;
-  constexpr int NB = 256;
-  if (!p->d_red) HIP_TRY(hipMalloc(&p->d_red, 1024 * sizeof(double)));
-  HIP_TRY(launch_loss(kind, pred, labels, n, dpred, p->d_red, NB, p->stream));
-  if (loss) {
-    double h[NB];
-    HIP_TRY(hipMemcpyAsync(h, p->d_red, NB * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    double s = 0;
-    for (int i = 0; i < NB; ++i) s += h[i];
-    *loss = s / (double)n;
-  }
-  return IGN_OK;
-}
-
-int ign_optimizer_num_slots(const ign_optimizer_desc* d, int32_t* n, float* init_value) {
-  if (!d || !n) return fail(IGN_ERR_INVALID, "null argument");
-  float init = 0.f;
-  switch (d->kind) {
-    case IGN_OPT_ADAM: *n = 2; break;
-    case IGN_OPT_SGD: *n = d->momentum > 0.f ? 1 : 0; break;
-    case IGN_OPT_RMSPROP: *n = 1 + (d->centered ? 1 : 0) + (d->momentum > 0.f ? 1 : 0); break;
-    case IGN_OPT_ADAGRAD:
-      *n = 1;
-      init = d->initial_accumulator_value;
-      break;
-    case IGN_OPT_ADADELTA: *n = 2; break;
-    case IGN_OPT_ADAMAX: *n = 2; break;
-    default: return fail(IGN_ERR_INVALID, "optimizer kind %d out of range", (int)d->kind);
-  }
-  if (init_value) *init_value = init;
-  return IGN_OK;
-}
-
-int ign_optimizer_step(ign_plan* p, const ign_optimizer_desc* d, const float* grads, float* const* slots,
-                       int32_t n_slots, int64_t iteration, float lr) {
-  if (!p || !d || !grads) return fail(IGN_ERR_INVALID, "null argument");
-  int32_t need = 0;
-  int rc = ign_optimizer_num_slots(d, &need, nullptr);
-  if (rc) return rc;
-  if (d->reserved != 0) return fail(IGN_ERR_INVALID, "ign_optimizer_desc.reserved must be 0");
-  if (n_slots != need) return fail(IGN_ERR_INVALID, "optimizer takes %d slot buffer(s), %d given", (int)need, (int)n_slots);
-  if (need && !slots) return fail(IGN_ERR_INVALID, "null argument");
-  for (int i = 0; i < need; ++i)
-    if (!slots[i]) return fail(IGN_ERR_INVALID, "slot buffer %d is null", i);
-  if (d->kind == IGN_OPT_ADAM)
-    return ign_adam_step(p, grads, slots[0], slots[1], iteration, lr, d->beta_1, d->beta_2, d->epsilon);
-  if (!p->params_set) return fail(IGN_ERR_INVALID, "parameters not set (ign_plan_set_params)");
-  if (iteration < 0) return fail(IGN_ERR_INVALID, "negative iteration");
-  rc = ensure_device(p);
-  if (rc) return rc;
-  OptimizerLaunch o{};
-  o.kind = d->kind;
-  o.w = p->d_params;
-  o.g = grads;
-  o.n = p->n_params;
-  o.lr = lr;
-  o.momentum = d->momentum;
-  o.rho = d->rho;
-  o.b1 = d->beta_1;
-  o.b2 = d->beta_2;
-  o.eps = d->epsilon;
-  o.nesterov = d->nesterov != 0;
-  o.centered = d->centered != 0;
-  if (d->kind == IGN_OPT_RMSPROP) {   // the kernel's positions: rms, mg, mom
-    int k = 0;
-    o.slots[0] = slots[k++];
-    if (d->centered) o.slots[1] = slots[k++];
-    if (d->momentum > 0.f) o.slots[2] = slots[k++];
-  } else {
-    for (int i = 0; i < need; ++i) o.slots[i] = slots[i];
-  }
-  if (d->kind == IGN_OPT_ADAMAX)   // the bias correction depends on the step only: host, double
-    o.lr = (float)((double)lr / (1.0 - std::pow((double)d->beta_1, (double)iteration + 1.0)));
-  HIP_TRY(launch_optimizer(o, p->stream));
-  return repack(p);
 }
 
 int ign_plan_get_params(ign_plan* p, float* host_out) {

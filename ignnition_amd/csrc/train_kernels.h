@@ -1,4 +1,4 @@
-// train_kernels.h — argument blocks and launchers of the backward / optimizer kernels.
+// train_kernels.h — argument blocks and launchers of the backward kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -134,42 +134,3 @@ hipError_t launch_dense_fwd(const float* x, int64_t n, int K, int x_stride, cons
 hipError_t launch_colsum_add(const float* B, int ldb, int64_t n_rows, int N, float* part, float* C, hipStream_t st);
 // y[i] += alpha * x[i]
 hipError_t launch_axpy(float* y, const float* x, float alpha, int64_t n, hipStream_t st);
-// dpred = 2 (pred - label) / n ; part[b] = partial sums of (pred - label)^2
-hipError_t launch_mse(const float* pred, const float* label, int64_t n, float* dpred, double* part, int nblk,
-                      hipStream_t st);
-// the loss and optimizer kinds of the C ABI (enum ign_loss, enum ign_optimizer in ignmp.h)
-#define IGN_K_LOSS_MSE 0
-#define IGN_K_LOSS_MAE 1
-#define IGN_K_LOSS_MAPE 2
-#define IGN_K_LOSS_MSLE 3
-#define IGN_K_LOSS_HUBER 4
-#define IGN_K_LOSS_LOGCOSH 5
-#define IGN_K_LOSS_BCE 6
-#define IGN_K_LOSS_POISSON 7
-#define IGN_K_OPT_ADAM 0
-#define IGN_K_OPT_SGD 1
-#define IGN_K_OPT_RMSPROP 2
-#define IGN_K_OPT_ADAGRAD 3
-#define IGN_K_OPT_ADADELTA 4
-#define IGN_K_OPT_ADAMAX 5
-// dpred = d(mean of the kind's element terms)/dpred ; part[b] = partial sums of the terms
-// (kind 0 is launch_mse itself)
-hipError_t launch_loss(int kind, const float* pred, const float* label, int64_t n, float* dpred, double* part,
-                       int nblk, hipStream_t st);
-// one element-wise update of w[n] from g[n] (every kind but Adam, which is launch_adam); slots: the
-// kernel's three slot positions (see optimizer_kernel), nullptr where the configuration has none;
-// lr: the rate with the step's bias correction folded in by the host
-struct OptimizerLaunch {
-  int kind;
-  float* w;
-  const float* g;
-  float* slots[3];
-  int64_t n;
-  float lr, momentum, rho, b1, b2, eps;
-  int nesterov, centered;
-};
-hipError_t launch_optimizer(const OptimizerLaunch& o, hipStream_t st);
-// part[b] = partial sums of x^2
-hipError_t launch_sumsq(const float* x, int64_t n, double* part, int nblk, hipStream_t st);
-hipError_t launch_adam(float* w, const float* g, float* m, float* v, int64_t n, float lr_t, float b1, float b2,
-                       float eps, hipStream_t st);

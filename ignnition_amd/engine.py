@@ -440,35 +440,32 @@ class Engine:
         check(lib.ign_plan_get_params(self.handle, flat.ctypes.data_as(C.c_void_p)))
         return {name: flat[off:off + int(np.prod(shape))].reshape(shape).copy() for name, shape, off in self.layout}
 
-    def mse_loss(self, pred, labels, dpred, want_loss: bool = True) -> float:
-        """Device tensors or addresses: pred/labels/dpred [n] fp32 (n = labels.numel()).  Returns the
-        loss; writes dLoss/dpred."""
+    def loss(self, kind: int, pred, labels, dpred, want_loss: bool = True) -> float:
+        """The lowered Keras loss of ``kind`` (ign_loss_kind of its name).  Device tensors or addresses:
+        pred/labels/dpred [n] fp32 (n = labels.numel()).  Returns the loss; writes dLoss/dpred."""
         out = C.c_double()
-        check(lib.ign_mse_loss(self.handle, _ptr(pred), _ptr(labels), labels.numel(), _ptr(dpred),
-                               C.byref(out) if want_loss else None))
+        check(lib.ign_loss(self.handle, int(kind), _ptr(pred), _ptr(labels), labels.numel(), _ptr(dpred),
+                           C.byref(out) if want_loss else None))
         return out.value if want_loss else None
+
+    def mse_loss(self, pred, labels, dpred, want_loss: bool = True) -> float:
+        return self.loss(0, pred, labels, dpred, want_loss)
 
     def l2_loss(self) -> float:
         out = C.c_double()
         check(lib.ign_l2_loss(self.handle, C.byref(out)))
         return out.value
 
-    def adam_step(self, grads, m, v, iteration: int, lr: float, beta1=0.9, beta2=0.999, epsilon=1e-7):
-        check(lib.ign_adam_step(self.handle, _ptr(grads), _ptr(m), _ptr(v), int(iteration), lr, beta1, beta2, epsilon))
-        self.params_version += 1
-
-    def loss(self, kind: int, pred, labels, dpred, want_loss: bool = True) -> float:
-        """``mse_loss`` for any lowered Keras loss (``kind``: ign_loss_kind of its name; 0 is mse_loss itself)."""
-        out = C.c_double()
-        check(lib.ign_loss(self.handle, int(kind), _ptr(pred), _ptr(labels), labels.numel(), _ptr(dpred),
-                           C.byref(out) if want_loss else None))
-        return out.value if want_loss else None
-
     def optimizer_step(self, desc, grads, slots, iteration: int, lr: float):
-        """``adam_step`` for any lowered Keras optimizer: ``desc`` an ``_lib.OptimizerDesc``, ``slots`` its
+        """One update of the lowered Keras optimizer ``desc`` (an ``_lib.OptimizerDesc``); ``slots``: its
         ign_optimizer_num_slots device buffers of n_params floats, in that call's order."""
         arr = (C.c_void_p * max(1, len(slots)))(*[_ptr(s) for s in slots])
         check(lib.ign_optimizer_step(self.handle, C.byref(desc), _ptr(grads), arr, len(slots), int(iteration), lr))
+        self.params_version += 1
+
+    def adam_step(self, grads, m, v, iteration: int, lr: float, beta1=0.9, beta2=0.999, epsilon=1e-7):
+        """ign_adam_step: ``optimizer_step`` for Adam with loose hyper-parameters."""
+        check(lib.ign_adam_step(self.handle, _ptr(grads), _ptr(m), _ptr(v), int(iteration), lr, beta1, beta2, epsilon))
         self.params_version += 1
 
     def replicas(self, n: int) -> list:

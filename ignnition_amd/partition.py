@@ -411,8 +411,7 @@ class EdgeCutTraining:
         dpreds = []
         for b, y in zip(self.batches, ys):
             d = torch.empty_like(y)
-            local = (self.engine.mse_loss(b.predictions_ptr(), y, d) if loss_kind == 0
-                     else self.engine.loss(loss_kind, b.predictions_ptr(), y, d))
+            local = self.engine.loss(loss_kind, b.predictions_ptr(), y, d)
             loss += local * y.numel() / n_total
             dpreds.append(d * (y.numel() / n_total))   # d(mean over every rank) = d(local mean) n_local / N
         loss = self._sum_scalar(loss)

@@ -2,14 +2,14 @@
 "GM") and the loop of train_and_evaluate (code/utils/framework_operations.py:108-166, "FO").
 
 * loss: ``learning_options.loss`` (GM:745-753) over the batch's concatenated flat predictions,
-  plus the Dense l2 kernel regularizers (AUX:833-834).  The engine computes it: MeanSquaredError
-  (``ign_mse_loss``) or, through ``ign_loss``, MeanAbsoluteError, MeanAbsolutePercentageError,
-  MeanSquaredLogarithmicError, Huber, LogCosh, BinaryCrossentropy and Poisson with Keras' default
-  constructor arguments; ``ign_l2_loss`` for the regularizers.
+  plus the Dense l2 kernel regularizers (AUX:833-834).  The engine computes it through ``ign_loss``:
+  MeanSquaredError (kind 0, which ``ign_mse_loss`` names), MeanAbsoluteError,
+  MeanAbsolutePercentageError, MeanSquaredLogarithmicError, Huber, LogCosh, BinaryCrossentropy and
+  Poisson with Keras' default constructor arguments; ``ign_l2_loss`` for the regularizers.
 * gradients: ``ign_backward``, the HIP backward of the whole forward (tf.gradients, GM:790).
-* optimizer: ``learning_options.optimizer`` (GM:797-818), Keras optimizer_v2 semantics: Adam
-  (``ign_adam_step``) or, through ``ign_optimizer_step``, SGD (momentum, nesterov), RMSprop
-  (momentum, centered), Adagrad, Adadelta and Adamax.  Nadam, Ftrl, amsgrad and gradient clipping
+* optimizer: ``learning_options.optimizer`` (GM:797-818), Keras optimizer_v2 semantics, through
+  ``ign_optimizer_step``: Adam (kind 0, which ``ign_adam_step`` names), SGD (momentum, nesterov),
+  RMSprop (momentum, centered), Adagrad, Adadelta and Adamax.  Nadam, Ftrl, amsgrad and gradient clipping
   are refused.  The learning rate is a float (default: the optimizer's own) or an ExponentialDecay,
   PiecewiseConstantDecay, PolynomialDecay or InverseTimeDecay schedule evaluated at ``iterations``
   (the global step, GM:816).
@@ -195,10 +195,7 @@ class Trainer:
         self.torch = torch
         self.options = lo
         self.loss_kind = lo.loss_kind
-        self.adam = lo.optimizer == "Adam"
         self.lr = lo.lr
-        if self.adam:
-            self.beta1, self.beta2, self.epsilon = lo.hyper["beta_1"], lo.hyper["beta_2"], lo.hyper["epsilon"]
         self.model_info = model_info
         torch.cuda.set_device(device)
         self.model = ComnetModel(model_info, device=device, params=params, seed=seed)
@@ -206,12 +203,10 @@ class Trainer:
         eng.set_stream(torch.cuda.current_stream().cuda_stream)   # torch copies / RCCL stream-ordered
         dev = torch.device("cuda", device)
         self.grads = torch.zeros(eng.n_params, dtype=torch.float32, device=dev)
-        # Adam's moments are m and v; any other optimizer's slot buffers (ign_optimizer_num_slots' order,
-        # all starting at its value: Adagrad's accumulator, alignment gaps included) are in slots
-        self.m = torch.zeros_like(self.grads) if self.adam else None
-        self.v = torch.zeros_like(self.grads) if self.adam else None
-        self.slots = [self.m, self.v] if self.adam else [torch.full_like(self.grads, lo.slot_init)
-                                                        for _ in range(lo.num_slots)]
+        # the optimizer's slot buffers (ign_optimizer_num_slots' order, all starting at its value:
+        # Adagrad's accumulator, alignment gaps included); Adam's moments are also m and v
+        self.slots = [torch.full_like(self.grads, lo.slot_init) for _ in range(lo.num_slots)]
+        self.m, self.v = self.slots if lo.optimizer == "Adam" else (None, None)
         self.dpred = None
         self.device = dev
         self.dist = dist
@@ -273,10 +268,7 @@ class Trainer:
                 t1 = tick()
                 prof["forward_enqueue"] += t1 - t0
             dpred = self.torch.empty_like(y)
-            if self.loss_kind == 0:
-                loss = self.engine.mse_loss(b.predictions_ptr(), y, dpred, want_loss=want_loss)
-            else:
-                loss = self.engine.loss(self.loss_kind, b.predictions_ptr(), y, dpred, want_loss=want_loss)
+            loss = self.engine.loss(self.loss_kind, b.predictions_ptr(), y, dpred, want_loss=want_loss)
             if tick:
                 t2 = tick()
                 prof["loss_wait"] += t2 - t1
@@ -300,10 +292,7 @@ class Trainer:
                     self.dist.all_reduce(self.grads)
                 self.grads /= self.dist.get_world_size()
             lr = self.lr(self.iterations)
-            if self.adam:
-                self.engine.adam_step(self.grads, self.m, self.v, self.iterations, lr, self.beta1, self.beta2, self.epsilon)
-            else:
-                self.engine.optimizer_step(self.options.desc, self.grads, self.slots, self.iterations, lr)
+            self.engine.optimizer_step(self.options.desc, self.grads, self.slots, self.iterations, lr)
             self.iterations += 1
         finally:
             if tick:
@@ -335,7 +324,7 @@ class Trainer:
             finally:
                 b.close()
             y = np.concatenate([np.asarray(l, np.float64).reshape(-1) for l in labels])
-            losses.append(float(np.mean((y - p) ** 2)) if self.loss_kind == 0 else host_loss(self.loss_kind, p, y))
+            losses.append(host_loss(self.loss_kind, p, y))   # (kind 0: bitwise np.mean((y - p) ** 2))
             yd = np.asarray(self._denorm(y), np.float64)
             pd = np.asarray(self._denorm(p), np.float64)
             labels_all.append(yd)

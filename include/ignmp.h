@@ -357,12 +357,14 @@ int  ign_backward_begin(ign_plan* plan, ign_batch* batch, const float* dpred, fl
 int  ign_backward_mp(ign_plan* plan, ign_batch* batch);
 int  ign_backward_end(ign_plan* plan, ign_batch* batch);
 int  ign_batch_train_buffers(const ign_batch* batch, int32_t entity, float** state, float** grad);
-/* MeanSquaredError: loss = mean((pred - labels)^2) (host, may be NULL), dpred = 2 (pred - labels) / n */
+/* MeanSquaredError: loss = mean((pred - labels)^2) (host, may be NULL), dpred = 2 (pred - labels) / n.
+ * This is ign_loss with kind IGN_LOSS_MEAN_SQUARED_ERROR. */
 int  ign_mse_loss(ign_plan* plan, const float* pred, const float* labels, int64_t n, float* dpred, double* loss);
 /* sum over Dense layers of l2 * sum(W^2) for the current parameters (the regularization loss) */
 int  ign_l2_loss(ign_plan* plan, double* loss);
 /* Keras Adam on the plan's parameters (in place) with lr = the schedule at `iteration`:
- * lr_t = lr sqrt(1 - beta2^(it+1)) / (1 - beta1^(it+1)); m, v: caller-owned device state. */
+ * lr_t = lr sqrt(1 - beta2^(it+1)) / (1 - beta1^(it+1)); m, v: caller-owned device state.
+ * This is ign_optimizer_step with kind IGN_OPT_ADAM, these hyper-parameters and the slots m, v. */
 int  ign_adam_step(ign_plan* plan, const float* grads, float* m, float* v, int64_t iteration, float lr,
                    float beta1, float beta2, float epsilon);
 /* The Keras losses and optimizers the engine lowers, by the names a model description uses
@@ -391,7 +393,7 @@ int  ign_loss_kind(const char* name, int32_t* kind);
 int  ign_optimizer_kind(const char* name, int32_t* kind);
 /* The loss of `kind` with Keras' default constructor arguments: the mean over the n flat
  * predictions of its element term (host double, may be NULL: then no host wait), and
- * dpred = d loss / d pred.  Kind 0 is ign_mse_loss. */
+ * dpred = d loss / d pred.  ign_mse_loss is its kind 0. */
 int  ign_loss(ign_plan* plan, int32_t kind, const float* pred, const float* labels, int64_t n, float* dpred,
               double* loss);
 /* An optimizer's configuration: the hyper-parameters of its Keras constructor that it reads
@@ -414,7 +416,7 @@ typedef struct {
  *   Adagrad acc (starts at initial_accumulator_value);  Adadelta acc, accu;  Adamax m, u. */
 int  ign_optimizer_num_slots(const ign_optimizer_desc* desc, int32_t* n, float* init_value);
 /* One Keras optimizer_v2 update of the plan's parameters (in place) at `iteration` (t = iteration + 1)
- * with the rate `lr`; Adam is ign_adam_step.  RMSprop's centered variance is clamped at 0, which
+ * with the rate `lr`; ign_adam_step is its kind 0.  RMSprop's centered variance is clamped at 0, which
  * departs from Keras only where Keras would produce NaN. */
 int  ign_optimizer_step(ign_plan* plan, const ign_optimizer_desc* desc, const float* grads, float* const* slots,
                         int32_t n_slots, int64_t iteration, float lr);

@@ -112,13 +112,33 @@ def test_loss_kernel(loss_engine, name, n):
 
 @pytest.mark.parametrize("n", SIZES)
 def test_loss_kind_0_is_mse_loss(loss_engine, n):
+    """ign_mse_loss forwards to ign_loss with kind 0, and Engine.mse_loss is Engine.loss(0): both give
+    the loss and dpred of kind 0 bit for bit."""
     p, y = _loss_inputs("MeanSquaredError", n)
     pd, yd = torch.from_numpy(p).cuda(), torch.from_numpy(y).cuda()
+    l1, d1 = _run_loss(loss_engine, 0, p, y)
     d0 = torch.empty_like(pd)
     l0 = loss_engine.mse_loss(pd, yd, d0)
-    l1, d1 = _run_loss(loss_engine, 0, p, y)
     assert l0 == l1
     np.testing.assert_array_equal(d0.cpu().numpy(), d1)
+    d0 = torch.empty_like(pd)
+    out = C.c_double()
+    _lib.check(_lib.lib.ign_mse_loss(loss_engine.handle, C.c_void_p(pd.data_ptr()), C.c_void_p(yd.data_ptr()), n,
+                                     C.c_void_p(d0.data_ptr()), C.byref(out)))
+    assert out.value == l1
+    np.testing.assert_array_equal(d0.cpu().numpy(), d1)
+
+
+@pytest.mark.parametrize("n", [1, 255, 256, 257, 65537])   # the block edge; 65537: one thread's second trip
+def test_mse_dpred_is_the_float32_expression(loss_engine, n):
+    """MeanSquaredError's dpred against numpy, independent of the engine: one correctly rounded float32
+    division, subtraction and multiplication on both sides (nothing to contract), so bit for bit."""
+    p, y = _loss_inputs("MeanSquaredError", n)
+    loss, d = _run_loss(loss_engine, 0, p, y)
+    ref = (F32(2) / F32(n)) * (p - y)
+    assert ref.dtype == np.float32
+    np.testing.assert_array_equal(d.view(np.uint32), ref.view(np.uint32))
+    assert loss == pytest.approx(kr.loss("MeanSquaredError", p, y), rel=1e-5)
 
 
 def test_loss_kind_out_of_range(loss_engine):
@@ -249,6 +269,8 @@ def test_forward_follows_the_update():
 
 
 def test_optimizer_kind_0_is_adam_step():
+    """ign_adam_step fills a desc of kind 0 from its loose hyper-parameters and forwards to
+    ign_optimizer_step: two steps through either give the same parameters, m and v bit for bit."""
     mi, prm, _, g = _real_grads("routenet")
     a, b = Engine(MPPlan.from_model_info(mi), 0), Engine(MPPlan.from_model_info(mi), 0)
     try:
@@ -279,6 +301,23 @@ def test_optimizer_step_argument_checks():
         with pytest.raises(_lib.EngineError) as ei:
             eng.optimizer_step(desc, torch.from_numpy(g).cuda(), slots[:1], 0, 0.01)
         assert ei.value.code == -1 and "slot" in str(ei.value)
+        # Adam takes the same checks (and leaves the parameters alone when one fails)
+        before = _flat(eng)
+        gd = torch.from_numpy(g).cuda()
+        h = {"beta_1": 0.9, "beta_2": 0.999, "epsilon": 1e-7}
+        desc, slots = _slots("Adam", h, eng.n_params)
+        assert desc.kind == 0
+        bad = _desc("Adam", h)
+        bad.reserved = 1
+        for d, s, it, word in ((desc, slots[:1], 0, "slot"), (desc, slots + slots[:1], 0, "slot"),
+                               (desc, [slots[0], 0], 0, "slot buffer 1 is null"), (bad, slots, 0, "reserved"),
+                               (desc, slots, -1, "negative iteration")):
+            with pytest.raises(_lib.EngineError) as ei:
+                eng.optimizer_step(d, gd, s, it, 0.01)
+            assert ei.value.code == -1 and word in str(ei.value), word
+        torch.cuda.synchronize()
+        np.testing.assert_array_equal(_flat(eng).view(np.uint32), before.view(np.uint32))
+        assert not any(bool(s.any()) for s in slots)
     finally:
         eng.close()
 

@@ -188,6 +188,7 @@ def test_restated_dpred_is_the_derivative_of_the_restated_loss(name):
     assert not kr.dpred_is_zero(name, p, y).any()
     # the package's host loss (Trainer.evaluate) is the same formula
     assert training.host_loss(kr.LOSSES.index(name), p, y) == pytest.approx(kr.loss(name, p, y), rel=1e-13)
+    assert training.host_loss(0, p, y) == float(np.mean((y - p) ** 2))   # what evaluate computed for MeanSquaredError
 
 
 def test_restated_optimizers_zero_gradient_is_a_zero_update():
