@@ -116,7 +116,8 @@ SYMBOLS = ["ign_abi_version", "ign_last_error", "ign_device_count", "ign_plan_cr
            "ign_dataset_batch_get", "ign_dataset_batch_get_narrow", "ign_dataset_batch_destroy", "ign_plan_create_json", "ign_plan_describe_json", "ign_forward_train_begin", "ign_forward_train_mp",
            "ign_forward_train_end", "ign_backward_begin", "ign_backward_mp", "ign_backward_end",
            "ign_batch_train_buffers", "ign_batch_read_predictions", "ign_batch_resident_info",
-           "ign_loss_kind", "ign_optimizer_kind", "ign_loss", "ign_optimizer_num_slots", "ign_optimizer_step"]
+           "ign_loss_kind", "ign_optimizer_kind", "ign_loss", "ign_optimizer_num_slots", "ign_optimizer_step",
+           "ign_plan_add_dropout", "ign_batch_set_dropout", "ign_dropout_keep"]
 
 ABI_VERSION = 13
 PART = {"all": 0, "interior": 1, "boundary": 2}
@@ -197,6 +198,9 @@ def _load():
         "ign_loss": (C.c_int, [VP, i32, VP, VP, i64, VP, P(C.c_double)]),
         "ign_optimizer_num_slots": (C.c_int, [P(OptimizerDesc), P(i32), P(f32)]),
         "ign_optimizer_step": (C.c_int, [VP, P(OptimizerDesc), VP, P(VP), i32, i64, f32]),
+        "ign_plan_add_dropout": (C.c_int, [VP, i32, i32, f32, C.c_uint64]),
+        "ign_batch_set_dropout": (C.c_int, [VP, C.c_uint64, C.c_uint32]),
+        "ign_dropout_keep": (C.c_int, [C.c_uint64, i32, C.c_uint32, i64, i64, f32, P(C.c_uint8)]),
     }
     # an A/B build of an older tree may lack newer entry points: only the A/B tools, which set
     # IGN_AB_LIB=1 next to IGN_LIB_PATH, skip them; any other library must export every symbol

@@ -843,6 +843,7 @@ static int build_sum_mp(ign_batch* b, const MPP& mp, size_t mi, int H, const Bat
 int ign_batch_create(ign_plan* p, const ign_batch_desc* d, ign_batch** out) {
   if (!p || !d || !out) return fail(IGN_ERR_INVALID, "null argument");
   *out = nullptr;
+  p->batch_made = true;   // the plan's Dropout sites are final from this call on (ign_plan_add_dropout)
   const int G = d->num_graphs;
   const int E = (int)p->ents.size();
   if (G <= 0) return fail(IGN_ERR_INVALID, "num_graphs must be > 0");

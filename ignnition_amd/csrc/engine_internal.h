@@ -16,6 +16,7 @@
 
 #include "../../include/ignmp.h"
 #include "kernels.h"
+#include "dropout_kernels.h"
 #include "host_types.h"   // the host-only types (MPP, hvec, IdxArr, ...), shared with batch_lower.h
 
 struct TrainState;                 // train.cpp
@@ -140,6 +141,22 @@ struct RoBatchOp {
   std::vector<int32_t> h_idx[2];  // extend: host copies of idx (the backward's transposed CSRs)
 };
 
+// A Dropout layer of a readout Dense stack (ign_plan_add_dropout): live in training only.  The
+// plan keeps them in site order: readout ops in order, then predict; within a stack by position,
+// then by insertion.  A site's ordinal is its index there.
+struct DropSite {
+  int stack = -1;        // readout-op index, or -1 for predict
+  int before = 0;        // Dense layer it precedes; the stack's layer count = after the last one
+  float rate = 0.f, scale = 1.f;
+  uint64_t seed = 0;     // the layer's own seed option, xor-mixed into the batch's stream seed
+};
+// a training forward / backward's stream and the per-site buffers of its batch
+struct DropRun {
+  uint64_t seed = 0;
+  uint32_t step = 0;
+  float* const* buf = nullptr;   // per site: its output (a site before a layer) or its input (after the last)
+};
+
 }  // namespace ign
 
 using namespace ign;
@@ -214,7 +231,65 @@ struct ign_plan {
   ign_stats_t stats{};
   std::shared_ptr<DevPool> pool;  // batch / training buffers (created with the stream, ensure_device)
   std::string describe;           // ign_plan_create_json: ign_plan_describe_json's document
+  std::vector<DropSite> drops;    // Dropout sites of the readout stacks, in site order (rate > 0 only)
+  bool batch_made = false;        // ign_plan_add_dropout is refused from the first batch on
 };
+
+namespace ign {
+// the sites of `stack` in front of Dense layer `before`: [*first, *first + count)
+inline int drop_range(const ign_plan* p, int stack, int before, int* first) {
+  int n = 0;
+  *first = 0;
+  for (size_t s = 0; s < p->drops.size(); ++s)
+    if (p->drops[s].stack == stack && p->drops[s].before == before) {
+      if (!n) *first = (int)s;
+      ++n;
+    }
+  return n;
+}
+inline bool stack_has_dropout(const ign_plan* p, int stack) {
+  for (auto& d : p->drops)
+    if (d.stack == stack) return true;
+  return false;
+}
+// x through the sites [first, first + count) in front of a layer: each writes its own buffer;
+// *out = the last one (x itself when count is 0)
+inline hipError_t drop_fwd_chain(const ign_plan* p, const DropRun& dr, int first, int count, const float* x, int64_t n,
+                                 hipStream_t st, const float** out) {
+  for (int s = first; s < first + count; ++s) {
+    const DropSite& d = p->drops[s];
+    hipError_t e = launch_dropout_fwd(x, dr.buf[s], n, d.rate, d.scale, dr.seed ^ d.seed, (uint32_t)s, dr.step, st);
+    if (e != hipSuccess) return e;
+    x = dr.buf[s];
+  }
+  *out = x;
+  return hipSuccess;
+}
+// the sites after a stack's last layer, which wrote its output y to buf[first]: each site reads
+// its buffer and writes the next one, the last writes `final`
+inline hipError_t drop_fwd_tail(const ign_plan* p, const DropRun& dr, int first, int count, float* final, int64_t n,
+                                hipStream_t st) {
+  for (int s = first; s < first + count; ++s) {
+    const DropSite& d = p->drops[s];
+    hipError_t e = launch_dropout_fwd(dr.buf[s], s + 1 < first + count ? dr.buf[s + 1] : final, n, d.rate, d.scale,
+                                      dr.seed ^ d.seed, (uint32_t)s, dr.step, st);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+// the gradient back through the sites [first, first + count), last site first: g_in -> g_out,
+// the later launches in place on g_out (g_out may be g_in)
+inline hipError_t drop_bwd_chain(const ign_plan* p, const DropRun& dr, int first, int count, const float* g_in,
+                                 float* g_out, int64_t n, hipStream_t st) {
+  for (int s = first + count - 1; s >= first; --s) {
+    const DropSite& d = p->drops[s];
+    hipError_t e = launch_dropout_bwd(g_in, g_out, n, d.rate, d.scale, dr.seed ^ d.seed, (uint32_t)s, dr.step, st);
+    if (e != hipSuccess) return e;
+    g_in = g_out;
+  }
+  return hipSuccess;
+}
+}  // namespace ign
 
 // the ordered update of the training forward saves every step's state, which the split-fp16 kernels
 // (variant 6 at H = 64) do not: training runs the x6 split-bf16 form there
@@ -278,6 +353,8 @@ struct ign_batch {
   std::vector<void*> allocs;                    // blocks of pool (returned on destroy)
   std::shared_ptr<DevPool> pool;                // the plan's (outlives the plan if need be)
   TrainState* train = nullptr;                  // ign_batch_enable_training
+  uint64_t drop_seed = 0;                       // ign_batch_set_dropout: the next training forward's
+  uint32_t drop_step = 0;                       // mask stream (never set: (0, 0))
   // captured ign_forward (init .. readout) for replay; the event slots it records
   hipGraphExec_t graph = nullptr;
   bool graph_timing = false;
@@ -315,7 +392,11 @@ int64_t readout_packed(ign_plan* p, int64_t pk);               // packed Dense f
 int readout_repack(ign_plan* p);
 int readout_batch(ign_plan* p, ign_batch* b, const ign_batch_desc* d);
 // ent: entity-state tensors to read (training keeps every version); null = the batch's current states
-int readout_ops_run(ign_plan* p, ign_batch* b, hipStream_t st, const float* const* ent = nullptr);
+// drop: the training forward's Dropout stream and buffers; null = inference (Dropout is identity)
+int readout_ops_run(ign_plan* p, ign_batch* b, hipStream_t st, const float* const* ent = nullptr,
+                    const DropRun* drop = nullptr);
+// ign_plan_add_dropout's routine (also called by ign_plan_create_json's lowering)
+int plan_add_dropout(ign_plan* p, int stack, int before_layer, float rate, uint64_t layer_seed);
 const float* readout_tensor(const ign_plan* p, const ign_batch* b, int id);
 int64_t space_rows(const ign_plan* p, const ign_batch* b, const RoTensor& t);
 // Batch construction (ign_batch_create, ign_batch_enable_training) copies and clears on a

@@ -101,13 +101,38 @@ struct Layer {
   ign_dense_desc d;
 };
 
-// Feed_forward_model (AUX:869-1003) + MPPlan._dense_layers
-std::vector<Layer> dense_layers(const JVal& architecture, const std::string& role, const char* what) {
+struct Drop {   // a Dropout layer of a readout stack (engine.py MPPlan: (before_layer, rate, seed))
+  int before;
+  double rate;
+  uint64_t seed;
+};
+
+// Feed_forward_model (AUX:869-1003) + MPPlan._dense_layers.  drops: where the stack's Dropout
+// layers go (a readout stack); null for a message-creation network, which takes none.  The
+// default-name counter counts every layer, Dropout included.
+std::vector<Layer> dense_layers(const JVal& architecture, const std::string& role, const char* what,
+                                std::vector<Drop>* drops) {
   std::vector<Layer> out;
   int counter = 0;
   for (const JVal& l : arr(architecture, std::string(what) + " nn_architecture")) {
     const std::string type = str(need(l, "type_layer", what), std::string(what) + " type_layer");
-    if (type != "Dense") unsupported(std::string(what) + " layer type " + type + " is not lowered (Dense only)");
+    if (type == "Dropout") {
+      if (!drops)
+        unsupported("message layer type Dropout is not lowered: a message-creation network would need a fresh mask "
+                    "per iteration (Dropout is lowered in the readout's Dense stacks only)");
+      for (auto& kv : l.obj)
+        if (kv.first != "type_layer" && kv.first != "rate" && kv.first != "name" && kv.first != "seed")
+          unsupported(std::string("Dropout option '") + kv.first + "' is not lowered");
+      const double rate = number(need(l, "rate", "Dropout"), "Dropout rate");
+      if (!(rate >= 0.0 && rate < 1.0)) invalid("Dropout rate must be in [0, 1), got " + std::to_string(rate));
+      const JVal* sd = opt(l, "seed");
+      const uint64_t seed = sd && sd->t != JVal::Null ? (uint64_t)(int64_t)number(*sd, "Dropout seed") : 0;
+      if (rate > 0.0) drops->push_back({(int)out.size(), rate, seed});   // rate 0: no layer (TF returns x)
+      ++counter;
+      continue;
+    }
+    if (type != "Dense")
+      unsupported(std::string(what) + " layer type " + type + " is not lowered (" + (drops ? "Dense and Dropout" : "Dense") + " only)");
     for (auto& kv : l.obj)
       if (kv.first != "type_layer" && kv.first != "units" && kv.first != "activation" &&
           kv.first != "kernel_regularizer" && kv.first != "name" && kv.first != "use_bias")
@@ -124,6 +149,7 @@ std::vector<Layer> dense_layers(const JVal& architecture, const std::string& rol
     out.push_back(y);
     ++counter;
   }
+  if (drops && !drops->empty() && out.empty()) invalid(std::string(what) + " network has a Dropout but no Dense layer");
   return out;
 }
 
@@ -162,6 +188,7 @@ struct Lowered {
     int type, mode = 0, adj = -1, counter = 0, in_width = 0;
     std::vector<int32_t> inputs;
     std::vector<Layer> layers;
+    std::vector<Drop> drops;
   };
   std::vector<RoOp> ro_ops;
   std::vector<int32_t> ro_inputs;
@@ -169,6 +196,7 @@ struct Lowered {
   int predict_counter = 0;
   std::string label;
   std::vector<Layer> dense;
+  std::vector<Drop> drops;   // the predict network's
 
   std::vector<std::pair<std::string, std::vector<int64_t>>> param_specs() const {
     std::vector<std::pair<std::string, std::vector<int64_t>>> s;
@@ -385,7 +413,7 @@ Lowered lower(const JVal& data, const JVal& dims) {
             }
           const JVal* arch_n = nets[str(need(op, "nn_name", "message network"), "nn_name")];
           net.layers = dense_layers(need(*arch_n, "nn_architecture", "message network"),
-                                    "message_creation_" + std::to_string(net_counter), "message");
+                                    "message_creation_" + std::to_string(net_counter), "message", nullptr);
           net.param_dim = extra_params;
           net.prefix = sname + "_to_" + dst + "_message_creation_0/";
         }
@@ -456,7 +484,7 @@ Lowered lower(const JVal& data, const JVal& dims) {
       d.type = IGN_RO_NEURAL_NETWORK;
       const std::string nn = str(need(op, "nn_name", "readout neural_network"), "nn_name");
       if (!nets.count(nn)) invalid("readout nn_name '" + nn + "' is not defined");
-      d.layers = dense_layers(need(*nets[nn], "nn_architecture", "readout network"), "readout", "readout");
+      d.layers = dense_layers(need(*nets[nn], "nn_architecture", "readout network"), "readout", "readout", &d.drops);
       for (int i : d.inputs) d.in_width += p.ro_widths[i];
       const JVal* on = opt(op, "output_name");
       add(on ? str(*on, "output_name") : "None", d.layers.back().d.units, first);
@@ -497,7 +525,7 @@ Lowered lower(const JVal& data, const JVal& dims) {
   p.label = str(need(*pred, "label", "predict"), "label");
   for (const JVal& i : arr(need(*pred, "input", "predict"), "input")) p.ro_inputs.push_back(resolve(i));
   const std::string nn = pred->get("nn_name")->str;
-  p.dense = dense_layers(need(*nets[nn], "nn_architecture", "predict network"), "readout", "readout");
+  p.dense = dense_layers(need(*nets[nn], "nn_architecture", "predict network"), "readout", "readout", &p.drops);
   return p;
 }
 
@@ -524,6 +552,24 @@ std::string describe(const Lowered& p) {
     for (size_t d = 0; d < specs[i].second.size(); ++d) s += (d ? ", " : "") + std::to_string(specs[i].second[d]);
     s += "]}";
   }
+  // Dropout sites in site order (readout operations in order, then predict): stack = the
+  // operation's index among the lowered operations (ign_plan_add_dropout's), -1 for predict
+  s += "], \"dropout\": [";
+  int site = 0;
+  auto sites = [&](int stack, const std::vector<Drop>& drops) {
+    std::vector<Drop> d = drops;
+    std::stable_sort(d.begin(), d.end(), [](const Drop& a, const Drop& b) { return a.before < b.before; });
+    for (const Drop& x : d) {
+      char rate[32];
+      snprintf(rate, sizeof rate, "%.9g", (double)(float)x.rate);
+      s += (site ? ", " : "") + std::string("{\"site\": ") + std::to_string(site) + ", \"stack\": " + std::to_string(stack) +
+           ", \"before_layer\": " + std::to_string(x.before) + ", \"rate\": " + rate + ", \"seed\": " +
+           std::to_string(x.seed) + "}";
+      ++site;
+    }
+  };
+  for (size_t k = 0; k < p.ro_ops.size(); ++k) sites((int)k, p.ro_ops[k].drops);
+  sites(-1, p.drops);
   return s + "]}";
 }
 
@@ -614,6 +660,16 @@ int ign_plan_create_json(const char* model_json, const char* dims_json, int32_t 
   if ((size_t)nt != specs.size()) {
     ign_plan_destroy(plan);
     return fail(IGN_ERR_INVALID, "internal: %zu parameter names for %d tensors", specs.size(), nt);
+  }
+  // the Dropout layers (ign_plan_add_dropout's routine)
+  for (size_t k = 0; k < p.ro_ops.size() && !rc; ++k)
+    for (const Drop& x : p.ro_ops[k].drops)
+      if ((rc = plan_add_dropout(plan, (int)k, x.before, (float)x.rate, x.seed))) break;
+  for (size_t i = 0; i < p.drops.size() && !rc; ++i)
+    rc = plan_add_dropout(plan, -1, p.drops[i].before, (float)p.drops[i].rate, p.drops[i].seed);
+  if (rc) {
+    ign_plan_destroy(plan);
+    return rc;
   }
   plan->describe = describe(p);
   *out = plan;

@@ -290,7 +290,7 @@ int readout_batch(ign_plan* p, ign_batch* b, const ign_batch_desc* d) {
   return IGN_OK;
 }
 
-int readout_ops_run(ign_plan* p, ign_batch* b, hipStream_t st, const float* const* ent) {
+int readout_ops_run(ign_plan* p, ign_batch* b, hipStream_t st, const float* const* ent, const DropRun* drop) {
   const float* prm = p->d_params;
   const int NE = (int)p->ents.size();
   auto readout_tensor = [&](const ign_plan* pp, const ign_batch* bb, int id) -> const float* {
@@ -313,14 +313,24 @@ int readout_ops_run(ign_plan* p, ign_batch* b, hipStream_t st, const float* cons
           x = bo.cat;
         }
         int stride = op.in_width;
-        for (size_t l = 0; l < op.layers.size(); ++l) {
+        const int NL = (int)op.layers.size();
+        // Dropout sites (training only): in front of a layer each masks into its own buffer, never
+        // the tensor another operation reads; after the last layer the output goes to the first
+        // site's buffer and the masked result to the op's tensor
+        int tail0 = 0;
+        const int tail = drop ? drop_range(p, (int)k, NL, &tail0) : 0;
+        for (int l = 0; l < NL; ++l) {
           const DenseP& dl = op.layers[l];
-          float* y = l + 1 == op.layers.size() ? bo.out[0] : bo.tmp[l];
+          int s0 = 0;
+          if (const int ns = drop ? drop_range(p, (int)k, l, &s0) : 0)
+            HIP_TRY(drop_fwd_chain(p, *drop, s0, ns, x, n * dl.in, st, &x));
+          float* y = l + 1 < NL ? bo.tmp[l] : tail ? drop->buf[tail0] : bo.out[0];
           HIP_TRY(launch_dense_fwd(x, n, dl.in, stride, dl.pk_w >= 0 ? p->d_packed + dl.pk_w : nullptr,
                                    prm + dl.off_w, dl.use_bias ? prm + dl.off_b : nullptr, dl.out, dl.act, y, st));
           x = y;
           stride = dl.out;
         }
+        if (tail) HIP_TRY(drop_fwd_tail(p, *drop, tail0, tail, bo.out[0], n * op.layers.back().out, st));
         break;
       }
       case IGN_RO_POOLING:            // GM:632-637

@@ -81,6 +81,11 @@ struct TrainState {
   float* rcat = nullptr;
   float* rties = nullptr;
   std::vector<int32_t*> rx_ptr, rx_idx;   // extend ops: per op 2 transposed CSRs (input row -> edges)
+  // Dropout sites of the readout stacks, per site [rows][units]: the masked input z of the layer it
+  // precedes (the backward's weight gradient reads it; the unmasked y stays where the layer below
+  // wrote it, for its activation derivative), or, after a stack's last layer, that layer's output y
+  std::vector<float*> dbuf;
+  DropRun drop;                           // the forward's mask stream: its backward regenerates the masks
   bool forward_done = false;
   // stepped forward / backward (ign_forward_train_begin .. _end, ign_backward_begin .. _end): the
   // edge-cut driver exchanges halo rows between the steps
@@ -461,6 +466,7 @@ struct TrainScratch {
   int64_t dmsg = 0, mz = 0, mdin = 0;            // message networks
   int64_t amsg = 0, arows = 0;                   // attention
   int64_t dz = 0, rz = 0, rcat = 0, ties = 0;    // readout
+  std::vector<int64_t> drop;                     // per Dropout site: rows x units
 };
 TrainScratch train_scratch(const ign_plan* p, const ign_batch* b) {
   TrainScratch z;
@@ -536,6 +542,11 @@ TrainScratch train_scratch(const ign_plan* p, const ign_batch* b) {
       z.ties = std::max(z.ties, (int64_t)b->G * p->ro_t[op.in[0]].width);
     }
   }
+  for (const DropSite& d : p->drops) {
+    const std::vector<DenseP>& layers = d.stack < 0 ? p->dense : p->ro_ops[d.stack].layers;
+    const int64_t rows = d.stack < 0 ? P : space_rows(p, b, p->ro_t[p->ro_ops[d.stack].in[0]]);
+    z.drop.push_back(rows * (d.before < (int)layers.size() ? layers[d.before].in : layers.back().out));
+  }
   return z;
 }
 
@@ -590,6 +601,11 @@ int alloc_readout(const ign_plan* p, const ign_batch* b, TrainState* t, const Tr
   if ((z.rz && ((rc = talloc(t, &t->rz[0], z.rz)) || (rc = talloc(t, &t->rz[1], z.rz)))) ||
       (z.rcat && (rc = talloc(t, &t->rcat, z.rcat))) || (z.ties && (rc = talloc(t, &t->rties, z.ties))))
     return rc;
+  for (int64_t n : z.drop) {   // one [rows][units] buffer per Dropout site
+    float* f = nullptr;
+    if ((rc = talloc(t, &f, n))) return rc;
+    t->dbuf.push_back(f);
+  }
   return IGN_OK;
 }
 
@@ -778,7 +794,9 @@ int ign_forward_train_end(ign_plan* p, ign_batch* b, float* pred_out) {
   // readout operations, then the predict stack with every activation kept (GM:605-629)
   std::vector<const float*> ent(E);
   for (int e = 0; e < E; ++e) ent[e] = t->ver[e][t->cur[e]];
-  if (!p->ro_ops.empty() && (rc = readout_ops_run(p, b, st, ent.data()))) return rc;
+  // this forward's Dropout masks (ign_batch_set_dropout), kept for the backward that regenerates them
+  t->drop = DropRun{b->drop_seed, b->drop_step, t->dbuf.data()};
+  if (!p->ro_ops.empty() && (rc = readout_ops_run(p, b, st, ent.data(), &t->drop))) return rc;
   auto tensor = [&](int id) -> const float* { return id < E ? ent[id] : b->ro_buf[id]; };
   const int64_t P = b->n_pred;
   const float* x = tensor(p->ro_in[0]);
@@ -794,9 +812,13 @@ int ign_forward_train_end(ign_plan* p, ign_batch* b, float* pred_out) {
   int in_stride = p->ro_width;
   // the inference readout kernel (readout_h16) with its activations written out: one launch, no
   // re-read of layer 1's output (readout.cpp's fused-readout conditions, variant 4)
+  // (a stack with a Dropout site runs layer by layer: the mask sits between two of its launches)
   const bool fused = p->train_fused_readout && p->fused_readout && p->readout_variant >= 4 && p->dense.size() == 3 &&
                      p->dense[1].pk_h >= 0 && p->dense[0].pk_bf >= 0 && p->dense[1].pk_bf >= 0 &&
-                     p->dense[0].use_bias && p->dense[1].use_bias;
+                     p->dense[0].use_bias && p->dense[1].use_bias && !stack_has_dropout(p, -1);
+  const int L = (int)p->dense.size();
+  int tail0 = 0;
+  const int tail = drop_range(p, -1, L, &tail0);   // sites after the last layer mask the predictions
   if (fused) {
     const DenseP &l1 = p->dense[0], &l2 = p->dense[1], &l3 = p->dense[2];
     Readout3Args a{x, P, in_stride,
@@ -811,7 +833,10 @@ int ign_forward_train_end(ign_plan* p, ign_batch* b, float* pred_out) {
   }
   for (size_t l = 0; !fused && l < p->dense.size(); ++l) {
     const DenseP& d = p->dense[l];
-    float* o = l + 1 == p->dense.size() ? b->d_pred : t->act[l];
+    int s0 = 0;
+    if (const int ns = drop_range(p, -1, (int)l, &s0))   // masks a copy of the layer's input
+      HIP_TRY(drop_fwd_chain(p, t->drop, s0, ns, in, P * d.in, st, &in));
+    float* o = l + 1 < p->dense.size() ? t->act[l] : tail ? t->dbuf[tail0] : b->d_pred;
     if (p->train_dense_bf && p->train_dense_h16 && d.pk_hn >= 0 && in_stride % 4 == 0)   // split-fp16 (x3)
       HIP_TRY(launch_dense_h16(in, P, d.in, in_stride, p->d_packed + d.pk_hn, d.use_bias ? p->d_params + d.off_b : nullptr,
                                d.out, d.act, o, st));
@@ -824,6 +849,7 @@ int ign_forward_train_end(ign_plan* p, ign_batch* b, float* pred_out) {
     in = o;
     in_stride = d.out;
   }
+  if (tail) HIP_TRY(drop_fwd_tail(p, t->drop, tail0, tail, b->d_pred, P * b->out_units, st));
   if (pred_out) {
     HIP_TRY(hipMemcpyAsync(pred_out, b->d_pred, P * b->out_units * sizeof(float), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -940,6 +966,15 @@ int ign_backward_begin(ign_plan* p, ign_batch* b, const float* dpred, float* gra
   const int L = (int)p->dense.size();
   const float* X = p->ro_in.size() > 1 ? t->ro_x : tensor(p->ro_in[0]);
   int zi = 0;
+  // Dropout sites (ign_plan_add_dropout): the masks of this forward, regenerated.  A site in front
+  // of layer l sits between act[l - 1] = y (the layer below's activation derivative reads it) and
+  // its own buffer z (layer l's input: its weight gradient reads it); the fusions below that form a
+  // layer's gradient rows from the layer above's decline across one
+  int s0 = 0, ns = drop_range(p, -1, L, &s0);
+  if (ns) {   // after the last layer: d(pred) -> d(y), y in the first site's buffer
+    HIP_TRY(drop_bwd_chain(p, t->drop, s0, ns, dpred, t->dz[1], P * p->dense[L - 1].out, st));
+    HIP_TRY(launch_act_bwd(t->dz[1], t->dbuf[s0], P * p->dense[L - 1].out, p->dense[L - 1].act, t->dz[0], st));
+  } else
   HIP_TRY(launch_act_bwd(dpred, b->d_pred, P * p->dense[L - 1].out, p->dense[L - 1].act, t->dz[0], st));
   // a 1-unit output layer's backward rows, dz[r][k] = dz_out[r] w[k] act'(a[r][k]), are formed by
   // the layer below's input-gradient kernel (dense_bf) as it loads a, and written over a in place
@@ -948,12 +983,13 @@ int ign_backward_begin(ign_plan* p, ign_batch* b, const float* dpred, float* gra
   auto dense_t_bf = [&](const DenseP& d) { return p->train_dense_bf && (p->train_dense_h16 ? d.pk_ht >= 0 : d.pk_bft >= 0); };
   for (int l = L - 1; l >= 0; --l) {
     const DenseP& d = p->dense[l];
-    const float* A = l == 0 ? X : t->act[l - 1];
+    ns = drop_range(p, -1, l, &s0);   // sites in front of this layer: its input is the last one's z
+    const float* A = ns ? t->dbuf[s0 + ns - 1] : l == 0 ? X : t->act[l - 1];
     const bool outer = xo.s != nullptr;   // this layer's dz is formed by its dense_t from act[l]
     if (!outer)
       HIP_TRY(launch_tsgemm_add(A, d.in, t->dz[zi], d.out, P, d.in, d.out, t->part, grads + d.off_w,
                                 d.use_bias ? grads + d.off_b : nullptr, st));
-    if (l > 0 && d.out == 1 && d.in % 4 == 0 && p->fuse_outer_bwd && dense_t_bf(p->dense[l - 1])) {
+    if (l > 0 && d.out == 1 && d.in % 4 == 0 && p->fuse_outer_bwd && dense_t_bf(p->dense[l - 1]) && !ns) {
       if ((rc = add_l2_grad(p, d, grads, l2_scale, d.in, st))) return rc;
       xo = OuterRows{t->dz[zi], p->d_params + d.off_w, p->dense[l - 1].act, t->act[l - 1]};
       continue;   // zi stays: dz[zi] holds dz_out for the layer below
@@ -964,10 +1000,14 @@ int ign_backward_begin(ign_plan* p, ign_batch* b, const float* dpred, float* gra
     const float* aprev = nullptr;
     if (l > 0) {
       out = t->dz[1 - zi];
-      act = p->dense[l - 1].act;
-      aprev = t->act[l - 1];
+      if (!ns) {   // (across a site: d(z) here, the mask and the activation derivative below)
+        act = p->dense[l - 1].act;
+        aprev = t->act[l - 1];
+      }
     } else if (p->ro_in.size() > 1) {
       out = t->dro;
+    } else if (ns) {
+      out = t->dz[1 - zi];   // d(masked copy of the input): masked below, then added to the input's gradient
     } else {
       out = grad_of(p->ro_in[0]);
       acc = 1;
@@ -989,6 +1029,14 @@ int ign_backward_begin(ign_plan* p, ign_batch* b, const float* dpred, float* gra
       if ((rc = add_l2_grad(p, d, grads, l2_scale, d.in, st))) return rc;
     }
     xo = OuterRows{};
+    if (ns) {   // d(z) -> d(y) through the sites, last first
+      HIP_TRY(drop_bwd_chain(p, t->drop, s0, ns, out, out, P * d.in, st));
+      if (l > 0) {
+        HIP_TRY(launch_act_bwd(out, t->act[l - 1], P * d.in, p->dense[l - 1].act, t->dz[zi], st));
+        continue;   // the layer below's dz is in dz[zi]: zi stays
+      }
+      if (p->ro_in.size() == 1) HIP_TRY(launch_split_cols_add(grad_of(p->ro_in[0]), P, d.in, out, d.in, 0, st));
+    }
     zi = 1 - zi;
   }
   if (p->ro_in.size() > 1) {   // split dX by columns into the input tensors (concat axis 1)
@@ -1009,14 +1057,37 @@ int ign_backward_begin(ign_plan* p, ign_batch* b, const float* dpred, float* gra
       case IGN_RO_NEURAL_NETWORK: {   // Readout_nn (AUX:1188-1211): Dense stack on concat(inputs)
         const int NL = (int)op.layers.size();
         int rz = 0;
+        ns = drop_range(p, k, NL, &s0);   // Dropout sites, as in the predict stack above
+        if (ns) {
+          HIP_TRY(drop_bwd_chain(p, t->drop, s0, ns, t->dT[op.out], t->rz[1], n * op.layers[NL - 1].out, st));
+          HIP_TRY(launch_act_bwd(t->rz[1], t->dbuf[s0], n * op.layers[NL - 1].out, op.layers[NL - 1].act, t->rz[0], st));
+        } else
         HIP_TRY(launch_act_bwd(t->dT[op.out], bo.out[0], n * op.layers[NL - 1].out, op.layers[NL - 1].act, t->rz[0], st));
         for (int l = NL - 1; l >= 0; --l) {
           const DenseP& d = op.layers[l];
           const int K = l == 0 ? op.in_width : op.layers[l - 1].out;
-          const float* A = l > 0 ? bo.tmp[l - 1] : op.in.size() > 1 ? bo.cat : tensor(op.in[0]);
+          ns = drop_range(p, k, l, &s0);
+          const float* A = ns ? t->dbuf[s0 + ns - 1] : l > 0 ? bo.tmp[l - 1] : op.in.size() > 1 ? bo.cat : tensor(op.in[0]);
           HIP_TRY(launch_tsgemm_add(A, K, t->rz[rz], d.out, n, K, d.out, t->part, grads + d.off_w,
                                     d.use_bias ? grads + d.off_b : nullptr, st));
           if ((rc = add_l2_grad(p, d, grads, l2_scale, K, st))) return rc;
+          if (ns) {   // d(z), the masks last first, then the layer below's activation derivative or the input's gradient
+            float* g = l == 0 && op.in.size() > 1 ? t->rcat : t->rz[1 - rz];
+            HIP_TRY(launch_row_gemm_t_generic(t->rz[rz], n, d.out, p->d_params + d.off_w, K, g, 0, -1, nullptr, st));
+            HIP_TRY(drop_bwd_chain(p, t->drop, s0, ns, g, g, n * K, st));
+            if (l > 0) {
+              HIP_TRY(launch_act_bwd(g, bo.tmp[l - 1], n * K, op.layers[l - 1].act, t->rz[rz], st));
+            } else if (op.in.size() > 1) {
+              int col = 0;
+              for (int id : op.in) {
+                const int w = p->ro_t[id].width;
+                HIP_TRY(launch_split_cols_add(grad_of(id), n, w, t->rcat, op.in_width, col, st));
+                col += w;
+              }
+            } else {
+              HIP_TRY(launch_split_cols_add(grad_of(op.in[0]), n, K, g, K, 0, st));
+            }
+          } else
           if (l > 0) {
             HIP_TRY(launch_row_gemm_t_generic(t->rz[rz], n, d.out, p->d_params + d.off_w, K, t->rz[1 - rz], 0,
                                               op.layers[l - 1].act, bo.tmp[l - 1], st));

@@ -72,6 +72,9 @@ def _message_net(s, dst, plan, eidx):
             raise UnsupportedModel("message input %r is not readable in the reference (GM:458/470)" % name)
     layers = []
     for l in op.model.layers:
+        if l.type == "Dropout":
+            raise UnsupportedModel("message layer type Dropout is not lowered: a message-creation network would need a "
+                                   "fresh mask per iteration (Dropout is lowered in the readout's Dense stacks only)")
         if l.type != "Dense":
             raise UnsupportedModel("message layer type %s is not lowered (Dense only)" % l.type)
         prm = dict(l.parameters)
@@ -106,6 +109,7 @@ class MPPlan:
     ro_spaces: list = field(default_factory=list)       # row space per tensor: ("entity", e) / ("graph",) / ("adj", slot)
     predict_counter: int = 0                           # readout_model_<index of predict in the readout list>
     dense: list = field(default_factory=list)          # [(name, units, act, use_bias, l2)]
+    dropout: list = field(default_factory=list)        # predict's Dropout layers: [(before_layer, rate, seed)]
     iterations: int = 0
     readout_label: str = ""
     convolution_dim: int = 0                           # F of convolution/kernel [F, F] (0: none)
@@ -182,10 +186,25 @@ class MPPlan:
 
     @staticmethod
     def _dense_layers(arch, what):
-        out = []
+        """(Dense layers, Dropout records) of a readout stack.  A Dropout layer (tf.nn.dropout in
+        training, the identity otherwise) is recorded as (before_layer, rate, seed): the Dense layer
+        it precedes, len(layers) after the last one.  rate 0 is no layer, as TF returns x."""
+        out, drops = [], []
         for l in arch.layers:
+            if l.type == "Dropout":
+                prm = dict(l.parameters)
+                if set(prm) - {"rate", "name", "seed"}:
+                    raise UnsupportedModel("Dropout options %s are not lowered" % sorted(set(prm) - {"rate", "name", "seed"}))
+                if "rate" not in prm:
+                    raise ValueError("Dropout: missing key 'rate'")
+                rate = float(prm["rate"])
+                if not 0.0 <= rate < 1.0:   # tf.nn.dropout raises ValueError
+                    raise ValueError("Dropout rate must be in [0, 1), got %r" % rate)
+                if rate > 0.0:
+                    drops.append((len(out), rate, int(prm.get("seed") or 0) & 0xFFFFFFFFFFFFFFFF))
+                continue
             if l.type != "Dense":
-                raise UnsupportedModel("%s layer type %s is not lowered (Dense only)" % (what, l.type))
+                raise UnsupportedModel("%s layer type %s is not lowered (Dense and Dropout only)" % (what, l.type))
             prm = dict(l.parameters)
             act = prm.get("activation", None)
             if act not in _lib.ACT:
@@ -195,7 +214,9 @@ class MPPlan:
                 raise UnsupportedModel("Dense options %s are not lowered" % sorted(set(prm) - known))
             out.append((prm.get("name"), int(prm["units"]), _lib.ACT[act], int(bool(prm.get("use_bias", True))),
                         float(prm.get("kernel_regularizer", 0.0) or 0.0)))
-        return out
+        if drops and not out:
+            raise ValueError("%s network has a Dropout but no Dense layer" % what)
+        return out, drops
 
     def _lower_readout(self, mi):
         """The readout list (GM:605-655) up to the first predict, which returns (GM:629); names
@@ -225,7 +246,7 @@ class MPPlan:
             first = self.ro_spaces[ids[0]]
             d = {"type": op.type, "inputs": ids, "mode": 0, "adj": -1, "layers": [], "counter": counter}
             if op.type == "neural_network":
-                d["layers"] = self._dense_layers(op.architecture, "readout")
+                d["layers"], d["dropout"] = self._dense_layers(op.architecture, "readout")
                 d["in_width"] = sum(self.ro_widths[i] for i in ids)
                 add(op.output_name, d["layers"][-1][1], first)
             elif op.type == "pooling":
@@ -257,11 +278,18 @@ class MPPlan:
         self.predict_counter, op = pred
         self.readout_label = op.label
         self.readout_inputs = [resolve(n) for n in op.input]
-        self.dense = self._dense_layers(op.architecture, "readout")
+        self.dense, self.dropout = self._dense_layers(op.architecture, "readout")
 
     @property
     def predict_space(self):
         return self.ro_spaces[self.readout_inputs[0]]
+
+    def dropout_sites(self):
+        """[(site, stack, before_layer, rate, seed)] in site order: readout operations in order, then
+        predict (stack -1), by position within a stack (ign_plan_add_dropout)."""
+        recs = [(k, d) for k, op in enumerate(self.readout_ops) for d in sorted(op.get("dropout", []), key=lambda d: d[0])]
+        recs += [(-1, d) for d in sorted(self.dropout, key=lambda d: d[0])]
+        return [(site, stack) + tuple(d) for site, (stack, d) in enumerate(recs)]
 
     # ------------------------------------------------------------------ C structures
     def to_desc(self):
@@ -371,6 +399,8 @@ class Engine:
         h = C.c_void_p()
         check(lib.ign_plan_create(C.byref(desc), device, C.byref(h)))
         self.handle = h
+        for _, stack, before, rate, seed in plan.dropout_sites():   # ign_dense_desc has no room for them
+            check(lib.ign_plan_add_dropout(h, stack, before, rate, seed))
         self.params_version = 0   # bumped by every parameter update (SplitBatch re-syncs its replicas)
         self._replicas = []
         _LIVE_ENGINES.add(self)
@@ -682,6 +712,11 @@ class Batch:
     def enable_training(self):
         check(lib.ign_batch_enable_training(self.engine.handle, self.handle))
 
+    def set_dropout(self, seed: int, step: int):
+        """The Dropout mask stream of the next ``forward_train`` (ign_batch_set_dropout); never
+        called: (0, 0)."""
+        check(lib.ign_batch_set_dropout(self.handle, int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF))
+
     def forward_train(self, to_host: bool = True):
         out = np.empty((self.predictions, self.output_units), np.float32) if to_host else None
         check(lib.ign_forward_train(self.engine.handle, self.handle,
@@ -826,6 +861,16 @@ class SplitBatch:
 
     def __del__(self):
         self.close()
+
+
+def dropout_keep(seed: int, site: int, step: int, rows: int, units: int, rate: float) -> np.ndarray:
+    """The keep mask [rows, units] (uint8) of Dropout site ``site`` on the host (ign_dropout_keep; no
+    GPU): the mask the training forward applies under ``Batch.set_dropout(s, step)`` when ``seed`` is
+    ``s`` xor the layer's own seed."""
+    out = np.empty((rows, units), np.uint8)
+    check(lib.ign_dropout_keep(int(seed) & 0xFFFFFFFFFFFFFFFF, int(site), int(step) & 0xFFFFFFFF, rows, units, rate,
+                               out.ctypes.data_as(C.POINTER(C.c_uint8))))
+    return out
 
 
 def device_count() -> int:

@@ -134,6 +134,7 @@ def debug(model_description, out_dir: str = "../debug_model/"):
         "readout_ops": plan.readout_ops,
         "readout_inputs": plan.readout_inputs,
         "dense": plan.dense,
+        "dropout_sites": [dict(zip(("site", "stack", "before_layer", "rate", "seed"), s)) for s in plan.dropout_sites()],
         "parameters": [[n, list(s)] for n, s in plan.param_specs()],
         "created": str(datetime.datetime.now()),
     }

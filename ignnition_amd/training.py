@@ -211,6 +211,10 @@ class Trainer:
         self.device = dev
         self.dist = dist
         self.iterations = 0
+        # the Dropout mask stream: the trainer's seed mixed with the data-parallel rank (ranks draw
+        # different masks); the step number is ``iterations``, so a run resumed at step k redraws step k's
+        rank = dist.get_rank() if dist is not None and dist.is_initialized() else 0
+        self.dropout_seed = (int(seed) + 0x9E3779B97F4A7C15 * rank) & 0xFFFFFFFFFFFFFFFF
         # IGN_STEP_PROF=1: host seconds per phase of train_prepared (bench.py --fresh-batches reports them)
         self.step_prof = (dict.fromkeys(("forward_enqueue", "loss_wait", "backward_enqueue", "close", "l2_wait",
                                          "steps"), 0.0) if os.environ.get("IGN_STEP_PROF") == "1" else None)
@@ -263,6 +267,7 @@ class Trainer:
         # return to that stream's pool before the step has read it
         y.record_stream(self.torch.cuda.current_stream(y.device))
         try:
+            b.set_dropout(self.dropout_seed, self.iterations)
             b.forward_train(to_host=False)
             if tick:
                 t1 = tick()

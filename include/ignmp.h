@@ -357,6 +357,36 @@ int  ign_backward_begin(ign_plan* plan, ign_batch* batch, const float* dpred, fl
 int  ign_backward_mp(ign_plan* plan, ign_batch* batch);
 int  ign_backward_end(ign_plan* plan, ign_batch* batch);
 int  ign_batch_train_buffers(const ign_batch* batch, int32_t entity, float** state, float** grad);
+/* ---- Dropout layers of the readout's Dense stacks (ABI 13 additions) ---------------------------
+ * The reference builds each layer of a network with getattr(tf.keras.layers, type_layer)
+ * (AUX:869-1003) and calls the readout networks with training=(mode == TRAIN) (GM:612-629).  A
+ * Dropout layer is tf.nn.dropout there: in ign_forward_train, keep = uniform >= rate and
+ * z = keep ? y * (1 / (1 - rate)) : 0 (a select: inf or NaN under a dropped element gives 0); in
+ * ign_forward it is the identity and costs nothing.  ign_dense_desc has no room for it, so a plan's
+ * Dropout layers are added after ign_plan_create, before the plan's first ign_batch_create:
+ *   stack         -1 for the predict network, else the index of a readout neural_network operation
+ *   before_layer  the Dense layer it precedes, 0 .. num_dense; num_dense = after the last one
+ *                 (it then masks the stack's output: the predictions, for predict).  Layers added
+ *                 at one position apply in the order they were added.
+ *   rate          in [0, 1), else IGN_ERR_INVALID (TF raises ValueError); 0 adds nothing (TF returns x)
+ *   layer_seed    the layer's own `seed` option (0 if none), xor-mixed into the stream seed below
+ * Each added layer is a site; sites are numbered over the plan: readout operations in order, then
+ * predict, by position within a stack.  ign_plan_create_json adds the sites of its description
+ * itself.  noise_shape and Dropout in a message-creation network are IGN_ERR_UNSUPPORTED. */
+int  ign_plan_add_dropout(ign_plan* plan, int32_t stack, int32_t before_layer, float rate, uint64_t layer_seed);
+/* The mask stream of the batch's next ign_forward_train (and the backward that follows it): site s
+ * draws the mask ign_dropout_keep(seed ^ layer_seed(s), s, step, rows, units, rate(s)).  A batch
+ * on which this was never called uses (0, 0): the same mask every step.  A trainer passes its seed
+ * (mixed with its data-parallel rank) and its global step, so a resumed run repeats the step's mask. */
+int  ign_batch_set_dropout(ign_batch* batch, uint64_t seed, uint32_t step);
+/* The keep mask of one site on the host, without a GPU: out[row * units + unit] = 1 (kept) or 0.
+ * Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter (g & 0xffffffff, g >> 32,
+ * site, step) for g = i >> 2, i = row * units + unit; element i takes output word i & 3,
+ * u = (word >> 8) * 2^-24, keep = u >= rate (csrc/dropout_rng.h, which the kernels share).  Rows
+ * are the batch's rows of the stack's input space: an edge-cut partition indexes its own rows, so
+ * the masks of a partitioned graph are not those of the whole one. */
+int  ign_dropout_keep(uint64_t seed, int32_t site, uint32_t step, int64_t rows, int64_t units, float rate,
+                      uint8_t* out);
 /* MeanSquaredError: loss = mean((pred - labels)^2) (host, may be NULL), dpred = 2 (pred - labels) / n.
  * This is ign_loss with kind IGN_LOSS_MEAN_SQUARED_ERROR. */
 int  ign_mse_loss(ign_plan* plan, const float* pred, const float* labels, int64_t n, float* dpred, double* loss);
