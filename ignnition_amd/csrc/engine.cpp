@@ -1,4 +1,5 @@
-// engine.cpp — C ABI (include/ignmp.h), plan lowering, native batch builder, forward driver.
+// engine.cpp — C ABI (include/ignmp.h), the plan's switches and repack (its lowering: plan_lower.cpp),
+// native batch builder, forward driver.
 //
 // Reference behaviour restated here (generate_model.py = GM, auxilary_classes.py = AUX):
 //  * hidden-state init per entity                                  GM:396-400, AUX:128-160
@@ -213,75 +214,85 @@ int dev_alloc(ign_batch* b, float** out, int64_t n) {
   return IGN_OK;
 }
 
-int act_ok(int a) { return a >= IGN_ACT_LINEAR && a <= IGN_ACT_TANH; }
-
 // Per-launch algorithmic cost: one GRU application = 2*3H*(DIN+H) + 14H flops.
 double gru_flops(int din, int H) { return 2.0 * 3 * H * (din + H) + 14.0 * H; }
 
 }  // namespace ign
 
 
+// Every plan-level IGN_* switch, read here once per ign_plan_create and nowhere else.
+static PlanSwitches switches_from_env() {
+  PlanSwitches s;
+  auto flag = [](const char* name, bool* out) {
+    if (const char* v = getenv(name)) *out = atoi(v) != 0;
+  };
+  flag("IGN_FUSE_PROJ", &s.fuse_proj);
+  if (const char* v = getenv("IGN_SEQ_VARIANT")) {   // 6 (default), 4 or 2; anything else: 6
+    const int sv = atoi(v);
+    s.seq_variant = sv == 2 || sv == 4 ? sv : 6;
+  }
+  flag("IGN_HIP_GRAPH", &s.use_graph);
+  if (const char* v = getenv("IGN_SUM_VARIANT")) s.sum_variant = atoi(v) == 7 || atoi(v) == 8 ? atoi(v) : 3;
+  if (const char* v = getenv("IGN_SUM_WINDOW")) s.sum_window = atoi(v);
+  if (const char* v = getenv("IGN_RESIDENT")) {   // 0 off; 1 default; 2 also force the global-path form
+    s.resident = atoi(v) != 0;
+    s.resident_path_global = atoi(v) == 2;
+  }
+  flag("IGN_RESIDENT_PG", &s.resident_pg);
+  flag("IGN_RESIDENT_TRAIN", &s.resident_train);
+  s.resident_eager = env_flag("IGN_RESIDENT_EAGER", true);   // (an empty value: the default)
+  flag("IGN_RES_LPT", &s.res_lpt);
+  if (const char* v = getenv("IGN_RES_GROUP")) s.res_group = std::max(0, atoi(v));
+  flag("IGN_RESIDENT_SAVE_TABLE", &s.resident_save_table);
+  flag("IGN_BWD_FUSE", &s.bwd_fuse);
+  flag("IGN_SUM_BWD_FUSE", &s.sum_bwd_fuse);
+  flag("IGN_DEFER_WGRAD", &s.defer_wgrad);
+  flag("IGN_TRAIN_CSR_GPU", &s.train_csr_gpu);
+  flag("IGN_TRAIN_DENSE_BF", &s.train_dense_bf);
+  flag("IGN_TRAIN_DENSE_H16", &s.train_dense_h16);
+  flag("IGN_TSGEMM_BF", &s.tsgemm_bf);
+  flag("IGN_FUSE_OUTER_BWD", &s.fuse_outer_bwd);
+  flag("IGN_TRAIN_FUSED_READOUT", &s.train_fused_readout);
+  flag("IGN_BWD_BF", &s.bwd_bf);
+  flag("IGN_TRAIN_SEQ_H16", &s.train_seq_h16);
+  if (const char* v = getenv("IGN_READOUT_VARIANT")) {   // 4 (default), 5, 2 or 1; anything else: 4
+    const int rv = atoi(v);
+    s.readout_variant = rv == 1 || rv == 2 || rv == 5 ? rv : 4;
+  }
+  return s;
+}
+
+// p->packs (plan_lower.cpp's layout_packed) in order: one launch per record
 int ign::repack(ign_plan* p) {
-  for (auto& cp : p->cells) {
-    if (!cp.used) continue;
-    HIP_TRY(launch_pack_gru(p->d_params + cp.off_k, p->d_params + cp.off_rk, p->d_params + cp.off_b,
-                            p->d_packed + cp.pk_w, p->d_packed + cp.pk_u, p->d_packed + cp.pk_b, cp.din, cp.H,
-                            p->stream));
-    if (cp.pk_ubf >= 0) HIP_TRY(launch_pack_u_bf16(p->d_params + cp.off_rk, p->d_packed + cp.pk_ubf, cp.H, p->stream));
-    if (cp.pk_uh >= 0) HIP_TRY(launch_pack_u_f16(p->d_params + cp.off_rk, p->d_packed + cp.pk_uh, cp.H, p->stream));
-    if (cp.pk_wh >= 0) HIP_TRY(launch_pack_w_f16(p->d_params + cp.off_k, p->d_packed + cp.pk_wh, cp.din, cp.H, p->stream));
-    if (cp.pk_wbf >= 0)
-      HIP_TRY(launch_pack_w_bf16(p->d_params + cp.off_k, p->d_packed + cp.pk_wbf, cp.din, cp.H, p->stream));
-    if (cp.pk_wt >= 0) HIP_TRY(launch_pack_a(p->d_params + cp.off_k, cp.din, 3 * cp.H, p->d_packed + cp.pk_wt, p->stream));
-    if (cp.pk_ut >= 0) HIP_TRY(launch_pack_a(p->d_params + cp.off_rk, cp.H, 3 * cp.H, p->d_packed + cp.pk_ut, p->stream));
-    if (cp.pk_uth >= 0) HIP_TRY(launch_pack_ut_f16(p->d_params + cp.off_rk, p->d_packed + cp.pk_uth, cp.H, p->stream));
-  }
-  for (auto& mp : p->mps)
-    if (mp.feature_concat) {
-      const CellP& cp = p->cells[mp.cell];
-      for (size_t s = 0; s < mp.src.size(); ++s)
-        HIP_TRY(launch_pack_gru(p->d_params + cp.off_k + (int64_t)mp.slice_off[s] * 3 * cp.H, nullptr, nullptr,
-                                p->d_packed + mp.pk_slice[s], nullptr, nullptr, p->ents[mp.src[s].entity].hidden_dim,
-                                cp.H, p->stream));
+  const hipStream_t st = p->stream;
+  const PackJob* const end = p->packs.data() + p->packs.size();
+  for (const PackJob* j = p->packs.data(); j != end; ++j) {
+    const float* s[3];
+    for (int k = 0; k < 3; ++k) s[k] = j->src[k] >= 0 ? p->d_params + j->src[k] : nullptr;
+    float* const dst = p->d_packed + j->dst;
+    switch (j->kind) {
+      case PK_GRU:   // the two records after it: its U and bias slots
+        HIP_TRY(launch_pack_gru(s[0], s[1], s[2], dst, p->d_packed + j[1].dst, p->d_packed + j[2].dst, j->a, j->b, st));
+        break;
+      case PK_GRU_U:
+      case PK_GRU_B: break;
+      case PK_GRU_W: HIP_TRY(launch_pack_gru(s[0], nullptr, nullptr, dst, nullptr, nullptr, j->a, j->b, st)); break;
+      case PK_U_BF16: HIP_TRY(launch_pack_u_bf16(s[0], dst, j->a, st)); break;
+      case PK_U_F16: HIP_TRY(launch_pack_u_f16(s[0], dst, j->a, st)); break;
+      case PK_UT_F16: HIP_TRY(launch_pack_ut_f16(s[0], dst, j->a, st)); break;
+      case PK_W_F16: HIP_TRY(launch_pack_w_f16(s[0], dst, j->a, j->b, st)); break;
+      case PK_W_BF16: HIP_TRY(launch_pack_w_bf16(s[0], dst, j->a, j->b, st)); break;
+      case PK_A: HIP_TRY(launch_pack_a(s[0], j->a, j->b, dst, st)); break;
+      case PK_DENSE_PAD: HIP_TRY(launch_pack_dense_pad(s[0], dst, j->a, j->b, j->c, st)); break;
+      case PK_DENSE_BF16: HIP_TRY(launch_pack_dense_bf16(s[0], dst, j->a, j->b, j->c, st)); break;
+      case PK_DENSE_BF16_T: HIP_TRY(launch_pack_dense_bf16_t(s[0], dst, j->a, j->b, st)); break;
+      case PK_DENSE_F16: HIP_TRY(launch_pack_dense_f16(s[0], dst, j->a, j->b, j->c, st)); break;
+      case PK_READOUT_H16: HIP_TRY(launch_pack_readout_h16(s[0], s[1], s[2], dst, j->a, j->b, j->c, st)); break;
+      case PK_READOUT_H32: HIP_TRY(launch_pack_readout_h32(s[0], s[1], s[2], dst, j->a, j->b, j->c, st)); break;
+      case PK_ATTN_VECTORS: HIP_TRY(launch_attn_vectors(s[0], s[1], s[2], j->a, dst, st)); break;
     }
-  for (auto& mp : p->mps)
-    for (auto& nn : mp.nn)
-      for (size_t l = 0; l < nn.layers.size(); ++l) {
-        const DenseP& dp = nn.layers[l];
-        if (dp.pk_w >= 0)
-          HIP_TRY(launch_pack_dense_pad(p->d_params + dp.off_w, p->d_packed + dp.pk_w, dp.in,
-                                        l == 0 ? nn.din_pad : dp.in, dp.out, p->stream));
-      }
-  if (p->pk_conv >= 0)
-    HIP_TRY(launch_pack_dense(p->d_params + p->off_conv, p->d_packed + p->pk_conv, p->conv_F, p->conv_F, p->stream));
-  if (p->pk_w12 >= 0)
-    HIP_TRY(launch_attn_vectors(p->d_params + p->off_k1, p->d_params + p->off_k2, p->d_params + p->off_att, p->attn_F,
-                                p->d_packed + p->pk_w12, p->stream));
-  if (p->dense.size() >= 2 && p->dense[1].pk_h >= 0) {
-    const DenseP &l1 = p->dense[0], &l2 = p->dense[1];
-    HIP_TRY(launch_pack_readout_h16(p->d_params + l1.off_w, l1.use_bias ? p->d_params + l1.off_b : nullptr,
-                                    p->d_params + l2.off_w, p->d_packed + l2.pk_h, l1.in, l1.out, l2.out, p->stream));
-    if (l2.pk_h32 >= 0)
-      HIP_TRY(launch_pack_readout_h32(p->d_params + l1.off_w, l1.use_bias ? p->d_params + l1.off_b : nullptr,
-                                      p->d_params + l2.off_w, p->d_packed + l2.pk_h32, l1.in, l1.out, l2.out, p->stream));
   }
-  for (auto& dp : p->dense) {
-    if (dp.pk_w >= 0) HIP_TRY(launch_pack_dense(p->d_params + dp.off_w, p->d_packed + dp.pk_w, dp.in, dp.out, p->stream));
-    if (dp.pk_bf >= 0)   // layer 1 reads its input from memory (natural k), layer 2 chains from registers
-      HIP_TRY(launch_pack_dense_bf16(p->d_params + dp.off_w, p->d_packed + dp.pk_bf, dp.in, dp.out, &dp != &p->dense[0],
-                                     p->stream));
-    if (dp.pk_bfn >= 0)
-      HIP_TRY(launch_pack_dense_bf16(p->d_params + dp.off_w, p->d_packed + dp.pk_bfn, dp.in, dp.out, 0, p->stream));
-    if (dp.pk_bft >= 0)
-      HIP_TRY(launch_pack_dense_bf16_t(p->d_params + dp.off_w, p->d_packed + dp.pk_bft, dp.in, dp.out, p->stream));
-    if (dp.pk_hn >= 0)
-      HIP_TRY(launch_pack_dense_f16(p->d_params + dp.off_w, p->d_packed + dp.pk_hn, dp.in, dp.out, 0, p->stream));
-    if (dp.pk_ht >= 0)
-      HIP_TRY(launch_pack_dense_f16(p->d_params + dp.off_w, p->d_packed + dp.pk_ht, dp.out, dp.in, 1, p->stream));
-  }
-  for (auto& dp : p->dense)
-    if (dp.pk_wt >= 0) HIP_TRY(launch_pack_a(p->d_params + dp.off_w, dp.in, dp.out, p->d_packed + dp.pk_wt, p->stream));
-  return readout_repack(p);
+  return IGN_OK;
 }
 
 // =============================================================================================
@@ -301,285 +312,9 @@ int ign_device_count(int32_t* n) {
 int ign_plan_create(const ign_plan_desc* d, int32_t device, ign_plan** out) {
   if (!d || !out) return fail(IGN_ERR_INVALID, "null argument");
   *out = nullptr;
-  if (d->num_iterations <= 0) return fail(IGN_ERR_INVALID, "num_iterations must be > 0");
-  if (d->num_entities <= 0 || d->num_entities > 8) return fail(IGN_ERR_INVALID, "1..8 entities supported");
   std::unique_ptr<ign_plan> p(new ign_plan());
   p->device = device;
-  if (const char* v = getenv("IGN_FUSE_PROJ")) p->fuse_proj = atoi(v) != 0;
-  if (const char* v = getenv("IGN_SEQ_VARIANT")) {   // 6 (default), 4 or 2; anything else: 6
-    const int sv = atoi(v);
-    p->seq_variant = sv == 2 || sv == 4 ? sv : 6;
-  }
-  if (const char* v = getenv("IGN_HIP_GRAPH")) p->use_graph = atoi(v) != 0;
-  if (const char* v = getenv("IGN_SUM_VARIANT")) p->sum_variant = atoi(v) == 7 || atoi(v) == 8 ? atoi(v) : 3;
-  if (const char* v = getenv("IGN_SUM_WINDOW")) p->sum_window = atoi(v);
-  if (const char* v = getenv("IGN_RESIDENT")) {   // 0 off; 1 default; 2 also force the global-path form
-    p->resident = atoi(v) != 0;
-    p->resident_path_global = atoi(v) == 2;
-  }
-  if (const char* v = getenv("IGN_RESIDENT_PG")) p->resident_pg = atoi(v) != 0;
-  if (const char* v = getenv("IGN_RESIDENT_TRAIN")) p->resident_train = atoi(v) != 0;
-  if (const char* v = getenv("IGN_RES_LPT")) p->res_lpt = atoi(v) != 0;
-  if (const char* v = getenv("IGN_RES_GROUP")) p->res_group = std::max(0, atoi(v));
-  if (const char* v = getenv("IGN_RESIDENT_SAVE_TABLE")) p->resident_save_table = atoi(v) != 0;
-  if (const char* v = getenv("IGN_BWD_FUSE")) p->bwd_fuse = atoi(v) != 0;
-  if (const char* v = getenv("IGN_SUM_BWD_FUSE")) p->sum_bwd_fuse = atoi(v) != 0;
-  if (const char* v = getenv("IGN_TRAIN_DENSE_BF")) p->train_dense_bf = atoi(v) != 0;
-  if (const char* v = getenv("IGN_TRAIN_DENSE_H16")) p->train_dense_h16 = atoi(v) != 0;
-  if (const char* v = getenv("IGN_TSGEMM_BF")) p->tsgemm_bf = atoi(v) != 0;
-  if (const char* v = getenv("IGN_FUSE_OUTER_BWD")) p->fuse_outer_bwd = atoi(v) != 0;
-  if (const char* v = getenv("IGN_TRAIN_FUSED_READOUT")) p->train_fused_readout = atoi(v) != 0;
-  if (const char* v = getenv("IGN_BWD_BF")) p->bwd_bf = atoi(v) != 0;
-  if (const char* v = getenv("IGN_TRAIN_SEQ_H16")) p->train_seq_h16 = atoi(v) != 0;
-  if (const char* v = getenv("IGN_READOUT_VARIANT")) {   // 4 (default), 5, 2 or 1; anything else: 4
-    const int rv = atoi(v);
-    p->readout_variant = rv == 1 || rv == 2 || rv == 5 ? rv : 4;
-  }
-  p->T = d->num_iterations;
-  p->ents.assign(d->entities, d->entities + d->num_entities);
-  for (size_t e = 0; e < p->ents.size(); ++e) {
-    const auto& en = p->ents[e];
-    if (en.hidden_dim <= 0) return fail(IGN_ERR_INVALID, "entity %zu: hidden_state_dimension must be > 0", e);
-    if (en.feature_total > en.hidden_dim)   // AUX:155-159: zeros(H - total) needs total <= H
-      return fail(IGN_ERR_INVALID, "entity %zu: total feature size %d exceeds hidden_state_dimension %d", e,
-                  en.feature_total, en.hidden_dim);
-  }
-  p->n_adj = d->num_adjacencies;
-  p->n_il = d->num_interleave;
-  for (int c = 0; c < d->num_cells; ++c) {
-    CellP cp;
-    cp.din = d->cells[c].input_dim;
-    cp.H = d->cells[c].units;
-    p->cells.push_back(cp);
-  }
-  for (int m = 0; m < d->num_mps; ++m) {
-    const ign_mp_desc& md = d->mps[m];
-    MPP mp;
-    mp.dst = md.dst_entity;
-    mp.aggr = md.aggregation;
-    mp.concat_axis = md.concat_axis;
-    mp.cell = md.cell;
-    if (mp.dst < 0 || mp.dst >= d->num_entities) return fail(IGN_ERR_INVALID, "mp %d: bad destination", m);
-    if (md.num_sources <= 0) return fail(IGN_ERR_INVALID, "mp %d: no source entities", m);
-    if (md.num_sources > IGN_MAX_SLOTS)
-      return fail(IGN_ERR_UNSUPPORTED, "mp %d: more than %d source entities", m, IGN_MAX_SLOTS);
-    mp.src.assign(md.sources, md.sources + md.num_sources);
-    switch (mp.aggr) {
-      case IGN_AGGR_SUM: mp.sorted = false; break;
-      case IGN_AGGR_ORDERED: mp.sorted = true; break;
-      case IGN_AGGR_INTERLEAVE:
-        mp.sorted = true;
-        if (md.num_sources != 2)  // tf.stack of the index lists (GM:518) needs exactly two sources
-          return fail(IGN_ERR_UNSUPPORTED, "mp %d: interleave aggregation supports exactly 2 sources (GM:518)", m);
-        break;
-      case IGN_AGGR_CONCAT:
-        if (mp.concat_axis != 1 && mp.concat_axis != 2)
-          return fail(IGN_ERR_INVALID, "mp %d: concat_axis must be 1 or 2", m);
-        mp.sorted = true;
-        mp.feature_concat = mp.concat_axis == 2;
-        break;
-      case IGN_AGGR_ATTENTION:
-      case IGN_AGGR_CONVOLUTION:
-        mp.sorted = false;
-        mp.act = md.activation;
-        if (mp.aggr == IGN_AGGR_CONVOLUTION && !act_ok(mp.act))
-          return fail(IGN_ERR_UNSUPPORTED, "mp %d: convolution activation %d", m, mp.act);
-        break;
-      default:
-        return fail(IGN_ERR_UNSUPPORTED, "mp %d: aggregation %d is not lowered", m, mp.aggr);
-    }
-    int din = -1;
-    for (auto& s : mp.src) {
-      if (s.entity < 0 || s.entity >= d->num_entities) return fail(IGN_ERR_INVALID, "mp %d: bad source entity", m);
-      if (s.adjacency < 0 || s.adjacency >= p->n_adj) return fail(IGN_ERR_INVALID, "mp %d: bad adjacency slot", m);
-      if (mp.aggr == IGN_AGGR_INTERLEAVE && (s.interleave < 0 || s.interleave >= p->n_il))
-        return fail(IGN_ERR_INVALID, "mp %d: interleave slot missing", m);
-      int dm = p->ents[s.entity].hidden_dim;   // direct_assignation: message = source state
-      MsgNN nn;
-      if (s.msg_num_layers > 0) {               // message-creation network (GM:440-475)
-        nn.param_dim = s.msg_param_dim;
-        for (int q = 0; q < s.msg_num_inputs; ++q) {
-          const int kind = s.msg_inputs[q];
-          nn.inputs.push_back(kind);
-          int w = 0;
-          if (kind == IGN_MSG_HS_SOURCE) w = p->ents[s.entity].hidden_dim;
-          else if (kind == IGN_MSG_HS_DEST) w = p->ents[mp.dst].hidden_dim;
-          else if (kind == IGN_MSG_EDGE_PARAMS) w = s.msg_param_dim;
-          else return fail(IGN_ERR_UNSUPPORTED, "mp %d: message input %d is not lowered", m, kind);
-          if (w <= 0) return fail(IGN_ERR_INVALID, "mp %d: message input %d has no width", m, kind);
-          if (q >= 4) return fail(IGN_ERR_UNSUPPORTED, "mp %d: more than 4 message inputs", m);
-          nn.widths.push_back(w);
-          nn.din += w;
-        }
-        if (nn.din <= 0) return fail(IGN_ERR_INVALID, "mp %d: empty message-network input", m);
-        nn.din_pad = (nn.din + 15) / 16 * 16;
-        int in = nn.din;
-        for (int l = 0; l < s.msg_num_layers; ++l) {
-          DenseP dp;
-          dp.in = in;
-          dp.out = s.msg_layers[l].units;
-          dp.act = s.msg_layers[l].activation;
-          dp.use_bias = s.msg_layers[l].use_bias;
-          dp.l2 = s.msg_layers[l].l2;   // kernel_regularizer: part of model.losses (AUX:833-834)
-          if (dp.out <= 0) return fail(IGN_ERR_INVALID, "mp %d: message layer %d units", m, l);
-          if (!act_ok(dp.act)) return fail(IGN_ERR_UNSUPPORTED, "mp %d: message layer activation %d", m, dp.act);
-          nn.layers.push_back(dp);
-          in = dp.out;
-        }
-        dm = nn.dout();
-      }
-      mp.nn.push_back(nn);
-      if (mp.feature_concat) {                 // axis 2: the step input is the sources' concatenation
-        mp.slice_off.push_back(din < 0 ? 0 : din);
-        din = (din < 0 ? 0 : din) + dm;
-        continue;
-      }
-      if (din >= 0 && dm != din)
-        return fail(IGN_ERR_INVALID, "mp %d: sources have different message dimensions (%d vs %d)", m, din, dm);
-      din = dm;
-    }
-    mp.din = din;
-    if (mp.cell < 0 || mp.cell >= (int)p->cells.size()) return fail(IGN_ERR_INVALID, "mp %d: bad cell index", m);
-    CellP& cp = p->cells[mp.cell];
-    if (cp.H != p->ents[mp.dst].hidden_dim)
-      return fail(IGN_ERR_INVALID, "mp %d: cell units %d != destination hidden dim %d", m, cp.H, p->ents[mp.dst].hidden_dim);
-    if (cp.din != din)
-      return fail(IGN_ERR_INVALID, "mp %d: cell input_dim %d != message dim %d", m, cp.din, din);
-    if (mp.feature_concat) {   // x.W is hoisted per source slice: the shapes that matter are (slice, H)
-      for (auto& s : mp.src)
-        if (!gru_shape_supported(p->ents[s.entity].hidden_dim, cp.H))
-          return fail(IGN_ERR_UNSUPPORTED, "mp %d: concat slice (input %d, units %d) not instantiated", m,
-                      p->ents[s.entity].hidden_dim, cp.H);
-    } else if (!gru_shape_supported(din, cp.H)) {
-      return fail(IGN_ERR_UNSUPPORTED, "mp %d: GRU shape (input %d, units %d) not instantiated (16/32, 64/64)", m,
-                  din, cp.H);
-    }
-    if (mp.aggr == IGN_AGGR_ATTENTION || mp.aggr == IGN_AGGR_CONVOLUTION) {
-      const int F = p->ents[mp.dst].hidden_dim;
-      // AUX:311-319 / GM:293-298: the messages and the destination states must have one width
-      if (din != F)
-        return fail(IGN_ERR_INVALID, "mp %d: %s needs message dim %d == destination dim %d", m,
-                    mp.aggr == IGN_AGGR_ATTENTION ? "attention" : "convolution", din, F);
-      if (F != 16 && F != 32)
-        return fail(IGN_ERR_UNSUPPORTED, "mp %d: attention / convolution lowered for 16 or 32 units", m);
-      int& pf = mp.aggr == IGN_AGGR_ATTENTION ? p->attn_F : p->conv_F;
-      if (pf && pf != F)
-        return fail(IGN_ERR_INVALID, "mp %d: the shared %s weights have width %d, this MP needs %d (GM:288-300)", m,
-                    mp.aggr == IGN_AGGR_ATTENTION ? "attention" : "convolution", pf, F);
-      pf = F;
-    }
-    cp.used = true;
-    p->mps.push_back(mp);
-  }
-  // readout program and predict (GM:605-629)
-  if (int rc = readout_plan(p.get(), d)) return rc;
-
-  // parameter layout (256-B aligned tensors)
-  auto align = [](int64_t x) { return (x + 63) & ~int64_t(63); };
-  int64_t off = 0;
-  for (size_t c = 0; c < p->cells.size(); ++c) {
-    CellP& cp = p->cells[c];
-    int g3 = 3 * cp.H;
-    cp.off_k = off; p->tensors.push_back({0, (int)c, off, cp.din, g3}); off = align(off + (int64_t)cp.din * g3);
-    cp.off_rk = off; p->tensors.push_back({1, (int)c, off, cp.H, g3}); off = align(off + (int64_t)cp.H * g3);
-    cp.off_b = off; p->tensors.push_back({2, (int)c, off, 2, g3}); off = align(off + 2LL * g3);
-  }
-  for (size_t mi = 0; mi < p->mps.size(); ++mi)
-    for (size_t s = 0; s < p->mps[mi].nn.size(); ++s)
-      for (auto& dp : p->mps[mi].nn[s].layers) {
-        const int owner = (int)(mi * IGN_MAX_SLOTS + s);
-        dp.off_w = off; p->tensors.push_back({9, owner, off, dp.in, dp.out}); off = align(off + (int64_t)dp.in * dp.out);
-        if (dp.use_bias) { dp.off_b = off; p->tensors.push_back({10, owner, off, 1, dp.out}); off = align(off + dp.out); }
-      }
-  if (p->conv_F) {
-    const int F = p->conv_F;
-    p->off_conv = off; p->tensors.push_back({5, -1, off, F, F}); off = align(off + (int64_t)F * F);
-  }
-  if (p->attn_F) {
-    const int F = p->attn_F;
-    p->off_k1 = off; p->tensors.push_back({6, -1, off, F, F}); off = align(off + (int64_t)F * F);
-    p->off_k2 = off; p->tensors.push_back({7, -1, off, F, F}); off = align(off + (int64_t)F * F);
-    p->off_att = off; p->tensors.push_back({8, -1, off, 2 * F, 1}); off = align(off + 2LL * F);
-  }
-  off = readout_layout(p.get(), off);
-  for (size_t l = 0; l < p->dense.size(); ++l) {
-    DenseP& dp = p->dense[l];
-    dp.off_w = off; p->tensors.push_back({3, (int)l, off, dp.in, dp.out}); off = align(off + (int64_t)dp.in * dp.out);
-    // use_bias false: Keras' Dense owns no bias variable, so the layout has none either
-    if (dp.use_bias) { dp.off_b = off; p->tensors.push_back({4, (int)l, off, 1, dp.out}); off = align(off + dp.out); }
-  }
-  p->n_params = off;
-  int64_t pk = 0;
-  for (auto& cp : p->cells) {
-    if (!cp.used) continue;
-    cp.pk_w = pk; pk = align(pk + 3LL * cp.din * cp.H);
-    cp.pk_u = pk; pk = align(pk + 3LL * cp.H * cp.H);
-    cp.pk_b = pk; pk = align(pk + 4LL * cp.H);
-    if (pack_u_bf16_floats(cp.H)) { cp.pk_ubf = pk; pk = align(pk + pack_u_bf16_floats(cp.H)); }
-    if (pack_u_f16_floats(cp.H)) { cp.pk_uh = pk; pk = align(pk + pack_u_f16_floats(cp.H)); }
-    if (cp.din == 64 && cp.H == 64) { cp.pk_wh = pk; pk = align(pk + pack_w_f16_floats(cp.din, cp.H)); }
-    if ((cp.din == 64 && cp.H == 64) || (cp.din == 32 && cp.H == 32)) { cp.pk_wbf = pk; pk = align(pk + pack_w_bf16_floats(cp.din, cp.H)); }
-  }
-  for (size_t l = 0; l < p->dense.size(); ++l) {
-    DenseP& dp = p->dense[l];
-    if ((p->fused_readout && l < 2) || dense_fwd_supported(dp.in, dp.out)) {
-      dp.pk_w = pk;
-      pk = align(pk + (int64_t)dp.in * dp.out);
-    }
-    if (p->fused_readout && l < 2 && dp.in % 32 == 0 && dp.out % 16 == 0 &&
-        readout_bf_supported(p->dense[0].in, p->dense[0].out, p->dense[1].out, p->dense[0].act, p->dense[1].act)) {
-      dp.pk_bf = pk;
-      pk = align(pk + 3LL * dp.in * dp.out / 2);
-      if (l == 1) {
-        dp.pk_h = pk; pk = align(pk + (int64_t)dp.in * dp.out + 64 + (int64_t)p->dense[0].in * dp.in + 64);
-        if (p->readout_variant == 5)   // (otherwise neither packed after each optimizer step nor allocated)
-          dp.pk_h32 = pk, pk = align(pk + (int64_t)dp.in * dp.out + 64 + (int64_t)p->dense[0].in * dp.in + 64);
-      }
-    }
-    if (dense_bf_supported(dp.in, dp.out)) {
-      dp.pk_bfn = pk;
-      pk = align(pk + 3LL * dp.in * dp.out / 2);
-      dp.pk_hn = pk;
-      pk = align(pk + (int64_t)dp.in * dp.out + 64);
-    }
-    if (dense_bf_supported(dp.out, dp.in)) {
-      dp.pk_bft = pk;
-      pk = align(pk + 3LL * dp.in * dp.out / 2);
-      dp.pk_ht = pk;
-      pk = align(pk + (int64_t)dp.in * dp.out + 64);
-    }
-  }
-  // backward fragments (training): W^T / U^T per cell, W^T per Dense layer where the MFMA
-  // row GEMM is instantiated
-  for (auto& cp : p->cells) {
-    if (!cp.used || !bwd_shape_supported(cp.H, cp.H)) continue;   // U^T: the recurrent backward
-    cp.pk_ut = pk; pk = align(pk + 3LL * cp.H * cp.H);
-    if (pack_ut_f16_floats(cp.H)) { cp.pk_uth = pk; pk = align(pk + pack_ut_f16_floats(cp.H)); }
-    if (!bwd_shape_supported(cp.din, cp.H)) continue;            // W^T (an axis-2 concat cell goes generic)
-    cp.pk_wt = pk; pk = align(pk + 3LL * cp.din * cp.H);
-  }
-  for (auto& dp : p->dense) {
-    if (!row_gemm_supported(dp.out, dp.in)) continue;
-    dp.pk_wt = pk; pk = align(pk + (int64_t)dp.in * dp.out);
-  }
-  for (auto& mp : p->mps)
-    for (auto& nn : mp.nn)
-      for (size_t l = 0; l < nn.layers.size(); ++l) {
-        DenseP& dp = nn.layers[l];
-        const int kin = l == 0 ? nn.din_pad : dp.in;
-        if (dense_fwd_supported(kin, dp.out)) { dp.pk_w = pk; pk = align(pk + (int64_t)kin * dp.out); }
-      }
-  for (auto& mp : p->mps)
-    if (mp.feature_concat)
-      for (auto& s : mp.src) {
-        mp.pk_slice.push_back(pk);
-        pk = align(pk + 3LL * p->ents[s.entity].hidden_dim * p->cells[mp.cell].H);
-      }
-  if (p->conv_F) { p->pk_conv = pk; pk = align(pk + (int64_t)p->conv_F * p->conv_F); }
-  if (p->attn_F) { p->pk_w12 = pk; pk = align(pk + 2LL * p->attn_F); }
-  pk = readout_packed(p.get(), pk);
-  p->n_packed = pk;
-
+  if (int rc = lower_plan(d, switches_from_env(), p.get())) return rc;
   // Device resources are allocated on first use (ensure_device), so plan validation and the
   // parameter layout are available without a GPU.
   *out = p.release();
@@ -924,7 +659,7 @@ int ign_batch_create(ign_plan* p, const ign_batch_desc* d, ign_batch** out) {
   // builders run ahead of the step, and the step's thread would otherwise build them inside the step
   // (fresh 512 x synth50 batches: 28 -> 56 ms per step once the training forward went resident)
   const double t_res0 = build_prof ? now_ms() : 0.0;
-  if (env_flag("IGN_RESIDENT_EAGER", true) && (rc = resident_tables(p, b.get()))) return rc;
+  if (p->resident_eager && (rc = resident_tables(p, b.get()))) return rc;
   if (build_prof) {
     std::string s;
     double prev = t_mp0;

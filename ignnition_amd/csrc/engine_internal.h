@@ -18,6 +18,7 @@
 #include "kernels.h"
 #include "dropout_kernels.h"
 #include "host_types.h"   // the host-only types (MPP, hvec, IdxArr, ...), shared with batch_lower.h
+#include "plan_lower.h"   // PlanModel: the lowered plan without the device
 
 struct TrainState;                 // train.cpp
 void train_state_destroy(TrainState* t);
@@ -48,12 +49,6 @@ enum { K_INIT = 0, K_SEQ = 1, K_SUM = 2, K_READOUT = 3, K_PROJECT = 4, K_OTHER =
 struct EvCost {
   double flops = 0, bytes = 0, mfma_bf16 = 0, mfma_f32 = 0;
 };
-struct Tensor {
-  int kind, owner;
-  int64_t offset;
-  int rows, cols;
-};
-
 
 struct MPB {
   bool sorted = false;
@@ -111,20 +106,6 @@ struct MPB {
   hvec<uint32_t> h_step_code, h_msg_src, h_multi_rows;
 };
 
-// readout program (GM:611-655): tensors on row spaces, operations before predict
-enum { RS_ENTITY = 0, RS_GRAPH = 1, RS_ADJ = 2 };
-struct RoTensor {
-  int space = RS_ENTITY, sid = 0;   // sid: entity or adjacency slot
-  int width = 0;
-  bool same_space(const RoTensor& o) const { return space == o.space && (space == RS_GRAPH || sid == o.sid); }
-};
-struct RoOp {
-  int type = 0, mode = 0, adj = -1;
-  std::vector<int> in;            // tensor ids
-  std::vector<DenseP> layers;     // IGN_RO_NEURAL_NETWORK
-  int in_width = 0;               // neural_network: concatenated input width
-  int out = -1;                   // first output tensor id
-};
 struct RoBatchOp {
   float* out[2] = {nullptr, nullptr};
   float* cat = nullptr;           // neural_network: concatenated input
@@ -141,15 +122,6 @@ struct RoBatchOp {
   std::vector<int32_t> h_idx[2];  // extend: host copies of idx (the backward's transposed CSRs)
 };
 
-// A Dropout layer of a readout Dense stack (ign_plan_add_dropout): live in training only.  The
-// plan keeps them in site order: readout ops in order, then predict; within a stack by position,
-// then by insertion.  A site's ordinal is its index there.
-struct DropSite {
-  int stack = -1;        // readout-op index, or -1 for predict
-  int before = 0;        // Dense layer it precedes; the stack's layer count = after the last one
-  float rate = 0.f, scale = 1.f;
-  uint64_t seed = 0;     // the layer's own seed option, xor-mixed into the batch's stream seed
-};
 // a training forward / backward's stream and the per-site buffers of its batch
 struct DropRun {
   uint64_t seed = 0;
@@ -161,64 +133,15 @@ struct DropRun {
 
 using namespace ign;
 
-struct ign_plan {
+// the lowered model, its layouts and switches (PlanModel), plus what needs a device or a run
+struct ign_plan : PlanModel {
   int device = 0;
   hipStream_t stream = nullptr;
   bool own_stream = false;
   bool external_stream = false;   // set by ign_plan_set_stream (may be the null stream)
-  int T = 0;
-  std::vector<ign_entity_desc> ents;
-  int n_adj = 0, n_il = 0;
-  std::vector<MPP> mps;
-  std::vector<CellP> cells;
-  std::vector<int> ro_in;         // predict inputs: readout tensor ids
-  std::vector<DenseP> dense;
-  std::vector<RoTensor> ro_t;     // readout tensors: entity states, then the op outputs
-  std::vector<RoOp> ro_ops;
-  std::vector<int> adj_src_ent, adj_dst_ent;   // per adjacency slot (from the MPs that read it)
-  // one convolution / attention weight set per plan (GM:288-300: the last MP's weights serve all)
-  int conv_F = 0, attn_F = 0;
-  int64_t off_conv = -1, off_k1 = -1, off_k2 = -1, off_att = -1;
-  int64_t pk_conv = -1, pk_w12 = -1;
-  std::vector<Tensor> tensors;
-  int64_t n_params = 0, n_packed = 0;
   float* d_params = nullptr;
   float* d_packed = nullptr;
   bool params_set = false;
-  bool fused_readout = false;
-  int readout_variant = 4;        // fused readout: 4 = both layers on split-fp16 (3 products) on 16x16x32 MFMAs
-                                  // (readout_h16), 5 = the same on 32x32x16 (readout_h32.hip, slower: DESIGN
-                                  // §3b), 1 = f32
-                                  // MFMA (readout3), 2 = split-bf16 x6 (readout_bf); IGN_READOUT_VARIANT
-  int ro_width = 0;
-  int seq_variant = 6;            // ordered update: 6 = split-fp16 h.U with 3 piece products (H = 32,
-                                  // 64), 4 = split-bf16 x6, 2 = f32 MFMA; IGN_SEQ_VARIANT
-  int xcd_remap = 0;              // XCD-aware tile order in the GRU kernels (placement only; off:
-                                  // measured slower, profiles/r02/seq_experiments)
-  bool fuse_proj = true;          // sum_gru_g32 projects for the next ordered MP (IGN_FUSE_PROJ=0: off)
-  int sum_variant = 8;            // sum update: 8 = split-fp16 GRU step at DIN = H = 64 and split-bf16
-                                  // at 32, 7 = split-bf16 at both, 3 = f32 MFMA; IGN_SUM_VARIANT
-  bool train_dense_bf = true;     // training forward's Dense layers on dense_bf (IGN_TRAIN_DENSE_BF=0: f32)
-  bool train_dense_h16 = true;    // ... on the split-fp16 form of dense_bf (IGN_TRAIN_DENSE_H16=0: split-bf16)
-  bool tsgemm_bf = true;          // weight-gradient row contractions on tsgemm_bf (IGN_TSGEMM_BF=0: f32 MFMA)
-  bool train_fused_readout = true;   // training forward's readout on readout_h16 with saves (IGN_TRAIN_FUSED_READOUT=0: per layer)
-  bool fuse_outer_bwd = true;     // 1-unit output layer's backward formed on the fly (IGN_FUSE_OUTER_BWD=0: row_outer_t)
-  bool bwd_bf = true;             // ordered backward's gate recompute on split-bf16 (IGN_BWD_BF=0: f32 MFMA)
-  bool train_seq_h16 = true;      // training forward's ordered update on split-fp16 (IGN_TRAIN_SEQ_H16=0: bf16)
-  bool bwd_fuse = true;           // ordered backward forms dU in the kernel (IGN_BWD_FUSE=0: tsgemm)
-  bool sum_bwd_fuse = true;       // sum backward forms dW / dU in the kernel (IGN_SUM_BWD_FUSE=0: tsgemm)
-  bool resident = true;           // graph-resident forward for small RouteNet-shaped graphs (IGN_RESIDENT=0: off)
-  bool resident_pg = true;        // ... with the path states in global memory where they do not fit LDS (IGN_RESIDENT_PG)
-  bool resident_path_global = false;   // IGN_RESIDENT=2: that form for every eligible batch (tests)
-  bool resident_train = true;     // the training forward on the resident form's SAVE variant (IGN_RESIDENT_TRAIN=0: off)
-  bool res_lpt = true;            // resident workgroups take their graphs longest first (IGN_RES_LPT=0: batch order)
-  int res_group = 0;              // consecutive graphs per resident workgroup (IGN_RES_GROUP; 0: auto, 1 or 2)
-  bool resident_save_table = true;   // ... which also saves the ordered MP's tables (IGN_RESIDENT_SAVE_TABLE=0: recompute)
-  int sum_window = -1;            // IGN_SUM_WINDOW: 1 windowed sum aggregation where eligible; -1 (default)
-                                  // segmented for destinations of >= 64 messages, 0 of >= 128, 2 for all.
-                                  // (The windowed form:)
-                                  // Measured 0.120 vs 0.112 ms (RouteNet link update, 37 messages per link);
-                                  // Q-size x512 7.33 -> 6.44 ms/step with both sum MPs windowed
   // timing
   bool timing = false;
   uint32_t timing_kinds = ~0u;    // kernel kinds that get event pairs (ign_plan_set_timing_kinds)
@@ -227,11 +150,9 @@ struct ign_plan {
   std::vector<EvCost> ev_cost;
   int ev_slot = 0;                // events recorded since ign_forward_begin
   double* d_red = nullptr;        // loss reductions (training)
-  bool use_graph = true;          // replay ign_forward as one captured hipGraph; IGN_HIP_GRAPH=0 disables
   ign_stats_t stats{};
   std::shared_ptr<DevPool> pool;  // batch / training buffers (created with the stream, ensure_device)
   std::string describe;           // ign_plan_create_json: ign_plan_describe_json's document
-  std::vector<DropSite> drops;    // Dropout sites of the readout stacks, in site order (rate > 0 only)
   bool batch_made = false;        // ign_plan_add_dropout is refused from the first batch on
 };
 
@@ -290,17 +211,6 @@ inline hipError_t drop_bwd_chain(const ign_plan* p, const DropRun& dr, int first
   return hipSuccess;
 }
 }  // namespace ign
-
-// the ordered update of the training forward saves every step's state, which the split-fp16 kernels
-// (variant 6 at H = 64) do not: training runs the x6 split-bf16 form there
-// the training forward's ordered update: split-fp16 x3 with state saving (seq_gru_h16<SAVE>) where
-// the backward can recompute its gates bitwise (fused seq_gru_bwd, H = 32; IGN_TRAIN_SEQ_H16=0: the
-// split-bf16 x6 form), else split-bf16 x6 / f32
-inline int train_seq_variant(const ign_plan* p, int H) {
-  if (p->seq_variant == 6 && H == 32 && p->train_seq_h16 && p->bwd_bf && p->bwd_fuse) return 6;
-  return p->seq_variant >= 6 ? 4 : std::max(2, p->seq_variant);
-}
-
 
 struct ign_batch {
   ign_plan* plan = nullptr;
@@ -377,7 +287,7 @@ int resident_sum_mps(const ign_plan* p, int* sum_mp, int* n_src);   // 0: not a 
 int set_device(int dev);
 int ensure_device(ign_plan* p);
 int dev_alloc(ign_batch* b, float** out, int64_t n);
-int repack(ign_plan* p);                      // fragments from d_params (set_params, optimizer)
+int repack(ign_plan* p);                      // runs p->packs: fragments from d_params (set_params, optimizer)
 // message-creation network of MP source s (GM:440-475): per-edge inputs, then the Dense stack into
 // mb.d_msg_layer[s] (the last layer's rows are the messages)
 int run_message_net(ign_plan* p, const MsgNN& nn, const MPB& mb, int s, const float* src_state,
@@ -386,10 +296,6 @@ int run_message_net(ign_plan* p, const MsgNN& nn, const MPB& mb, int s, const fl
 int attention_weights(ign_plan* p, ign_batch* b, const MPP& mp, const MPB& mb, const float* const* srcs,
                       const float* hin, hipStream_t st);
 // readout.cpp: the readout program (operations before predict, GM:611-655)
-int readout_plan(ign_plan* p, const ign_plan_desc* d);          // parse + row spaces + widths
-int64_t readout_layout(ign_plan* p, int64_t off);              // raw parameter tensors (kinds 11/12)
-int64_t readout_packed(ign_plan* p, int64_t pk);               // packed Dense fragments
-int readout_repack(ign_plan* p);
 int readout_batch(ign_plan* p, ign_batch* b, const ign_batch_desc* d);
 // ent: entity-state tensors to read (training keeps every version); null = the batch's current states
 // drop: the training forward's Dropout stream and buffers; null = inference (Dropout is identity)

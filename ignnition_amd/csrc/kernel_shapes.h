@@ -1,0 +1,56 @@
+// kernel_shapes.h — the shapes the kernels are instantiated for and the floats their packed weight
+// fragments take, for the plan lowering (plan_lower.cpp) and the launchers alike.  No HIP header.
+// A launcher returns hipErrorInvalidValue for a shape its predicate refuses: that check ties each
+// predicate here to its dispatch.
+#pragma once
+#include <stdint.h>
+
+inline bool gru_shape_supported(int din, int h) {
+  return ((din == 16 || din == 32) && (h == 16 || h == 32)) || (din == 64 && h == 64);
+}
+inline bool readout3_supported(int din, int n1, int n2, int act1, int act2) {
+  return (din == 16 || din == 32 || din == 64) && n1 == 256 && n2 == 256 && act1 == act2;
+}
+inline bool readout_bf_supported(int din, int n1, int n2, int act1, int act2) {
+  return (din == 32 || din == 64) && n1 == 256 && n2 == 256 && act1 == act2;
+}
+// dense_bf / dense_h16 and their transposed forms: K in {32, 64, 128, 256}, M a multiple of 128
+inline bool dense_bf_supported(int K, int M) {
+  // whole stages of G 16-unit tiles: G <= 8 for K < 256; K = 256 stages two tiles (NP = 2) or one,
+  // so the readout's first-layer input gradient (K = 256 -> M = 32, RouteNet's state width) runs
+  // here instead of on row_gemm_t's f32 MFMA
+#ifndef IGN_DENSE_BF_M128
+  if (K == 256) return M > 0 && M % 32 == 0;
+#endif
+  return (K == 32 || K == 64 || K == 128 || K == 256) && M % 128 == 0 && M > 0;
+}
+inline bool bwd_shape_supported(int din, int h) {
+  return (din == 16 || din == 32 || din == 64) && (h == 16 || h == 32 || h == 64) && (h != 64 || din == 64) &&
+         (din != 64 || h == 64);
+}
+inline bool seq_bwd_fused_supported(int h) { return h == 16 || h == 32; }
+inline bool row_gemm_supported(int K, int M) {
+  return (K == 48 || K == 96 || K == 192 || K == 256) && (M == 16 || M == 32 || M == 64 || M == 256);
+}
+inline bool dense_fwd_supported(int K, int M) {
+  return (K == 16 || K == 32 || K == 48 || K == 64 || K == 96 || K == 128 || K == 256) &&
+         (M == 16 || M == 32 || M == 64 || M == 128 || M == 256);
+}
+
+// floats of d_packed each pack launch writes (0: the launch is not instantiated for the shape)
+inline int64_t pack_gru_w_floats(int din, int H) { return 3LL * din * H; }   // pack_gru's W / pack_a of W, U
+inline int64_t pack_gru_u_floats(int H) { return 3LL * H * H; }
+inline int64_t pack_gru_b_floats(int H) { return 4LL * H; }                  // the combined biases [4][H]
+inline int64_t pack_u_bf16_floats(int H) { return (H == 32 || H == 64) ? 9LL * H * H / 2 : 0; }
+inline int64_t pack_u_f16_floats(int H) { return (H == 32 || H == 64) ? 3LL * H * H + 64 : 0; }
+inline int64_t pack_ut_f16_floats(int H) { return H == 32 ? 3LL * H * H + 64 : 0; }
+inline int64_t pack_w_f16_floats(int K, int H) { return ((H == 32 || H == 64) && K % 32 == 0) ? 3LL * K * H + 64 : 0; }
+inline int64_t pack_w_bf16_floats(int K, int H) { return ((H == 32 || H == 64) && K % 32 == 0) ? 9LL * K * H / 2 : 0; }
+inline int64_t pack_dense_floats(int in, int out) { return (int64_t)in * out; }            // pack_dense(_pad), pack_a
+inline int64_t pack_dense_bf16_floats(int in, int out) { return 3LL * in * out / 2; }      // three bf16 pieces
+inline int64_t pack_dense_f16_floats(int in, int out) { return (int64_t)in * out + 64; }   // two fp16 pieces + header
+// the fused readout's split-fp16 block: W2, header, W1, header (pack_readout_h16 / _h32)
+inline int64_t pack_readout_h16_floats(int in1, int n1, int n2) {
+  return pack_dense_f16_floats(n1, n2) + pack_dense_f16_floats(in1, n1);
+}
+inline int64_t attn_vectors_floats(int F) { return 2LL * F; }

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kernel_shapes.h"   // the *_supported predicates and pack_*_floats sizes
+
 #define IGN_SLOT_SHIFT 29u
 #define IGN_ROW_MASK ((1u << IGN_SLOT_SHIFT) - 1u)
 #define IGN_MAX_SLOTS 4
@@ -96,7 +98,6 @@ hipError_t launch_init_state(float* state, const float* feats, int64_t n, int H,
 hipError_t launch_pack_gru(const float* W, const float* U, const float* bias, float* Wp, float* Up, float* bp,
                            int DIN, int H, hipStream_t st);
 hipError_t launch_pack_dense(const float* W, float* Wp, int IN, int OUT, hipStream_t st);
-bool gru_shape_supported(int din, int h);
 hipError_t launch_project(const float* x, int64_t n, const float* Wp, const float* bp, float* out, float* bias_row,
                           int din, int h, hipStream_t st);
 hipError_t launch_multi_sum(float* table, int64_t multi_base, int64_t n_multi, const int32_t* ptr,
@@ -106,25 +107,20 @@ hipError_t launch_seq_gru(const SeqGruArgs& args, int h, int variant, hipStream_
 hipError_t launch_seq_gru_bf(const SeqGruArgs& args, int h, int passes, hipStream_t st);
 // recurrent kernel -> split-bf16 A fragments for seq variants 4/5 (H = 32 or 64); floats used: 9 H^2 / 2
 hipError_t launch_pack_u_bf16(const float* U, void* out, int H, hipStream_t st);
-inline int64_t pack_u_bf16_floats(int H) { return (H == 32 || H == 64) ? 9LL * H * H / 2 : 0; }
 // split-fp16 ordered update (kernels_bf.hip, inference only), passes 3 or 4
 hipError_t launch_seq_gru_h16(const SeqGruArgs& args, int h, int passes, hipStream_t st);
 // recurrent kernel -> scaled 2-piece fp16 A fragments for seq variants 6/7 (H = 32 or 64), then the
 // scale's exponent; floats used: 3 H^2 + 64
 hipError_t launch_pack_u_f16(const float* U, void* out, int H, hipStream_t st);
-inline int64_t pack_u_f16_floats(int H) { return (H == 32 || H == 64) ? 3LL * H * H + 64 : 0; }
 // U (unscaled, [H][3H]) as the A operand of dh = du . U^T in the ordered backward (rows: the H state
 // units, k: the 3H gate units in the chained order), scaled fp16 pieces + scale exponent; H = 32
 hipError_t launch_pack_ut_f16(const float* U, void* out, int H, hipStream_t st);
-inline int64_t pack_ut_f16_floats(int H) { return H == 32 ? 3LL * H * H + 64 : 0; }
 // [K][3H] input kernel -> the same scaled fp16 layout (K % 32 == 0) for sum variant 8
 hipError_t launch_pack_w_f16(const float* W, void* out, int K, int H, hipStream_t st);
-inline int64_t pack_w_f16_floats(int K, int H) { return ((H == 32 || H == 64) && K % 32 == 0) ? 3LL * K * H + 64 : 0; }
 // sum variant 8: the split-fp16 sum update (DIN = H = 64; Wbf / Ubf carry pack_w_f16 / pack_u_f16)
 hipError_t launch_sum_gru_h16(const SumGruArgs& args, int din, int h, hipStream_t st);
 // pieces of a [K][3H] input kernel (K % 32 == 0) for the split-bf16 sum update
 hipError_t launch_pack_w_bf16(const float* W, void* out, int K, int H, hipStream_t st);
-inline int64_t pack_w_bf16_floats(int K, int H) { return ((H == 32 || H == 64) && K % 32 == 0) ? 9LL * K * H / 2 : 0; }
 // split-bf16 sum update (DIN = H = 64, no message weights / convolution); hipErrorInvalidValue otherwise
 hipError_t launch_sum_gru_bf(const SumGruArgs& args, int din, int h, hipStream_t st);
 // sum update at DIN = H = 32: code-prefetched gather (gu rows in flight per lane), split-bf16 GRU step
@@ -235,11 +231,9 @@ struct ResidentArgs {
 hipError_t resident_prepare_device();
 hipError_t launch_resident_forward(const ResidentArgs& a, int n_graphs, size_t lds_bytes, int form, bool save,
                                    hipStream_t st);
-bool readout3_supported(int din, int n1, int n2, int act1, int act2);
 hipError_t launch_readout3(const Readout3Args& args, int din, int n1, int n2, hipStream_t st);
 // readout on split-bf16 contractions (fp32-exact operands; passes 6 or 9), weights from
 // launch_pack_dense_bf16 (W1 natural k order, W2 chained); floats used: 3 IN OUT / 2
-bool readout_bf_supported(int din, int n1, int n2, int act1, int act2);
 // readout variant 4: both layers on scaled 2-piece fp16 pieces (pack_readout_h16: W2, header, W1,
 // header; floats 256 * 256 + 64 + IN1 * 256 + 64)
 hipError_t launch_readout_h16(const Readout3Args& args, const void* Wh, int din, hipStream_t st);
@@ -257,7 +251,6 @@ hipError_t launch_readout_bf(const Readout3Args& args, const void* W1f, const vo
 hipError_t launch_pack_dense_bf16(const float* W, void* out, int IN, int OUT, int chained, hipStream_t st);
 // y[r][0..M) = act(x[r] . W + b), split-bf16 (x6) with fp32 accumulation; W packed by
 // launch_pack_dense_bf16 with chained = 0.  K in {32, 64, 128, 256}, M a multiple of 128.
-bool dense_bf_supported(int K, int M);
 hipError_t launch_dense_bf(const float* x, int64_t n, int K, int x_stride, const void* Wbf, const float* bias, int M,
                            int act, float* y, hipStream_t st);
 // the backward row GEMM out[r][0..M) (+)= (dz[r] . W^T) * act'(aprev[r]) (act < 0: no act'), dz [n][K]

@@ -957,10 +957,6 @@ hipError_t launch_pack_dense_pad(const float* W, float* Wp, int IN, int IN_pad, 
     return hipGetLastError();                                                                     \
   }
 
-bool gru_shape_supported(int din, int h) {
-  return ((din == 16 || din == 32) && (h == 16 || h == 32)) || (din == 64 && h == 64);
-}
-
 hipError_t launch_project(const float* x, int64_t n, const float* Wp, const float* bp, float* out, float* bias_row,
                           int din, int h, hipStream_t st) {
   dim3 grid(std::max(1, grid_for(n, 64))), block(256);
@@ -1065,10 +1061,6 @@ hipError_t launch_sum_gru(const SumGruArgs& args, int din, int h, int variant, h
     return hipGetLastError();
   }
   return hipErrorInvalidValue;
-}
-
-bool readout3_supported(int din, int n1, int n2, int act1, int act2) {
-  return (din == 16 || din == 32 || din == 64) && n1 == 256 && n2 == 256 && act1 == act2;
 }
 
 template <int DIN>

@@ -2036,10 +2036,6 @@ static hipError_t readout_bf_din(const Readout3Args& args, const void* W1f, cons
   return hipGetLastError();
 }
 
-bool readout_bf_supported(int din, int n1, int n2, int act1, int act2) {
-  return (din == 32 || din == 64) && n1 == 256 && n2 == 256 && act1 == act2;
-}
-
 hipError_t launch_readout_bf(const Readout3Args& args, const void* W1f, const void* W2f, int din, int passes,
                              hipStream_t st) {
   if (args.n_rows == 0) return hipSuccess;
@@ -2116,16 +2112,6 @@ hipError_t launch_pack_readout_h16(const float* W1, const float* b1, const float
   hipLaunchKernelGGL(pack_readout_h16_frag_kernel, dim3(128), dim3(256), 0, st, W1, W2, static_cast<uint16_t*>(out), in1,
                      n1, n2);
   return hipGetLastError();
-}
-
-bool dense_bf_supported(int K, int M) {
-  // whole stages of G 16-unit tiles: G <= 8 for K < 256; K = 256 stages two tiles (NP = 2) or one,
-  // so the readout's first-layer input gradient (K = 256 -> M = 32, RouteNet's state width) runs
-  // here instead of on row_gemm_t's f32 MFMA
-#ifndef IGN_DENSE_BF_M128
-  if (K == 256) return M > 0 && M % 32 == 0;
-#endif
-  return (K == 32 || K == 64 || K == 128 || K == 256) && M % 128 == 0 && M > 0;
 }
 
 template <int KS, int G, bool BWD, int NP>

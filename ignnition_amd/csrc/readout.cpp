@@ -28,162 +28,6 @@
 
 namespace ign {
 
-int act_ok(int a);
-
-namespace {
-
-int parse_dense(const ign_dense_desc* d, int n, int in, std::vector<DenseP>& out, const char* what, int idx) {
-  for (int l = 0; l < n; ++l) {
-    DenseP dp;
-    dp.in = in;
-    dp.out = d[l].units;
-    dp.act = d[l].activation;
-    dp.use_bias = d[l].use_bias;
-    dp.l2 = d[l].l2;
-    if (dp.out <= 0) return fail(IGN_ERR_INVALID, "%s %d, dense layer %d: units must be > 0", what, idx, l);
-    if (!act_ok(dp.act)) return fail(IGN_ERR_UNSUPPORTED, "%s %d, dense layer %d: activation %d", what, idx, l, dp.act);
-    out.push_back(dp);
-    in = dp.out;
-  }
-  return IGN_OK;
-}
-
-const char* space_name(int s) { return s == RS_ENTITY ? "entity" : s == RS_GRAPH ? "graph" : "adjacency"; }
-
-}  // namespace
-
-int readout_plan(ign_plan* p, const ign_plan_desc* d) {
-  const int NE = (int)p->ents.size();
-  p->adj_src_ent.assign(p->n_adj, -1);
-  p->adj_dst_ent.assign(p->n_adj, -1);
-  for (const MPP& mp : p->mps)
-    for (const auto& s : mp.src) {
-      p->adj_src_ent[s.adjacency] = s.entity;
-      p->adj_dst_ent[s.adjacency] = mp.dst;
-    }
-  p->ro_t.clear();
-  p->ro_ops.clear();
-  for (int e = 0; e < NE; ++e) p->ro_t.push_back({RS_ENTITY, e, p->ents[e].hidden_dim});
-  if (d->num_readout_ops < 0 || (d->num_readout_ops > 0 && !d->readout_ops))
-    return fail(IGN_ERR_INVALID, "bad readout operation list");
-  for (int k = 0; k < d->num_readout_ops; ++k) {
-    const ign_readout_op_desc& od = d->readout_ops[k];
-    RoOp op;
-    op.type = od.type;
-    op.mode = od.mode;
-    op.adj = od.adjacency;
-    if (od.num_inputs <= 0 || !od.inputs) return fail(IGN_ERR_INVALID, "readout op %d: no input", k);
-    for (int i = 0; i < od.num_inputs; ++i) {
-      const int id = od.inputs[i];
-      if (id < 0 || id >= (int)p->ro_t.size()) return fail(IGN_ERR_INVALID, "readout op %d: input tensor %d", k, id);
-      op.in.push_back(id);
-    }
-    const RoTensor t0 = p->ro_t[op.in[0]];   // copies: ro_t grows below
-    op.out = (int)p->ro_t.size();
-    int rc;
-    switch (op.type) {
-      case IGN_RO_NEURAL_NETWORK: {
-        for (int id : op.in) {
-          if (!p->ro_t[id].same_space(t0))
-            return fail(IGN_ERR_UNSUPPORTED, "readout op %d: inputs on different row spaces (concat axis 1)", k);
-          op.in_width += p->ro_t[id].width;
-        }
-        if (od.num_dense <= 0 || !od.dense) return fail(IGN_ERR_INVALID, "readout op %d: no Dense layer", k);
-        if ((rc = parse_dense(od.dense, od.num_dense, op.in_width, op.layers, "readout op", k))) return rc;
-        p->ro_t.push_back({t0.space, t0.sid, op.layers.back().out});
-        break;
-      }
-      case IGN_RO_POOLING:   // Pooling_operation reads input[0] only (GM:634)
-        if (op.mode < IGN_POOL_SUM || op.mode > IGN_POOL_MAX)
-          return fail(IGN_ERR_INVALID, "readout op %d: pooling type %d", k, op.mode);
-        p->ro_t.push_back({RS_GRAPH, 0, t0.width});
-        break;
-      case IGN_RO_PRODUCT: {  // input[0] * input[1] (GM:641-642)
-        if (op.mode != 0)
-          return fail(IGN_ERR_UNSUPPORTED, "readout op %d: dot_product (tf.tensordot axes=0) is a rank-4 outer "
-                      "product the reference records as width 1 (GM:374-375); only element_wise is lowered", k);
-        if (op.in.size() < 2) return fail(IGN_ERR_INVALID, "readout op %d: product needs two inputs", k);
-        const RoTensor t1 = p->ro_t[op.in[1]];
-        if (t1.width != t0.width && t1.width != 1)
-          return fail(t0.width == 1 ? IGN_ERR_UNSUPPORTED : IGN_ERR_INVALID,
-                      "readout op %d: product of widths %d and %d (the result keeps input 0's width, GM:372-373)",
-                      k, t0.width, t1.width);
-        RoTensor o = t0;
-        if (!t0.same_space(t1)) {
-          if (t0.space == RS_GRAPH) o = {t1.space, t1.sid, t0.width};
-          else if (t1.space != RS_GRAPH)
-            return fail(IGN_ERR_UNSUPPORTED, "readout op %d: product of tensors on different row spaces (%s %d, %s %d)",
-                        k, space_name(t0.space), t0.sid, space_name(t1.space), t1.sid);
-        }
-        p->ro_t.push_back(o);
-        break;
-      }
-      case IGN_RO_EXTEND: {
-        if (op.in.size() < 2) return fail(IGN_ERR_INVALID, "readout op %d: extend_adjacencies needs two inputs", k);
-        if (op.adj < 0 || op.adj >= p->n_adj || p->adj_src_ent[op.adj] < 0)
-          return fail(IGN_ERR_INVALID, "readout op %d: adjacency slot %d is not read by any message passing", k, op.adj);
-        const RoTensor t1 = p->ro_t[op.in[1]];
-        if (t0.space != RS_ENTITY || t0.sid != p->adj_src_ent[op.adj] || t1.space != RS_ENTITY ||
-            t1.sid != p->adj_dst_ent[op.adj])
-          return fail(IGN_ERR_INVALID, "readout op %d: extend_adjacencies inputs must live on the adjacency's source "
-                      "and destination entities", k);
-        p->ro_t.push_back({RS_ADJ, op.adj, t0.width});
-        p->ro_t.push_back({RS_ADJ, op.adj, t1.width});
-        break;
-      }
-      default:
-        return fail(IGN_ERR_UNSUPPORTED, "readout op %d: type %d", k, op.type);
-    }
-    p->ro_ops.push_back(std::move(op));
-  }
-
-  // predict (GM:612-629)
-  p->ro_in.assign(d->readout_inputs, d->readout_inputs + d->num_readout_inputs);
-  if (p->ro_in.empty()) return fail(IGN_ERR_INVALID, "readout has no input");
-  int width = 0;
-  for (int id : p->ro_in) {
-    if (id < 0 || id >= (int)p->ro_t.size()) return fail(IGN_ERR_INVALID, "readout input tensor %d", id);
-    if (!p->ro_t[id].same_space(p->ro_t[p->ro_in[0]]))
-      return fail(IGN_ERR_UNSUPPORTED, "predict inputs on different row spaces (concat axis 1)");
-    width += p->ro_t[id].width;
-  }
-  p->ro_width = width;
-  int rc = parse_dense(d->dense, d->num_dense, width, p->dense, "predict", 0);
-  if (rc) return rc;
-  if (p->dense.empty()) return fail(IGN_ERR_INVALID, "readout has no Dense layer");
-  p->fused_readout = p->dense.size() == 3 &&
-                     readout3_supported(width, p->dense[0].out, p->dense[1].out, p->dense[0].act, p->dense[1].act) &&
-                     p->dense[2].out == 1 && p->dense[0].use_bias && p->dense[1].use_bias;
-  return IGN_OK;
-}
-
-static int64_t align64(int64_t x) { return (x + 63) & ~int64_t(63); }
-
-int64_t readout_layout(ign_plan* p, int64_t off) {
-  for (size_t k = 0; k < p->ro_ops.size(); ++k)
-    for (size_t l = 0; l < p->ro_ops[k].layers.size(); ++l) {
-      DenseP& dp = p->ro_ops[k].layers[l];
-      const int owner = (int)(k * 64 + l);
-      dp.off_w = off; p->tensors.push_back({11, owner, off, dp.in, dp.out}); off = align64(off + (int64_t)dp.in * dp.out);
-      if (dp.use_bias) { dp.off_b = off; p->tensors.push_back({12, owner, off, 1, dp.out}); off = align64(off + dp.out); }
-    }
-  return off;
-}
-
-int64_t readout_packed(ign_plan* p, int64_t pk) {
-  for (auto& op : p->ro_ops)
-    for (auto& dp : op.layers)
-      if (dense_fwd_supported(dp.in, dp.out)) { dp.pk_w = pk; pk = align64(pk + (int64_t)dp.in * dp.out); }
-  return pk;
-}
-
-int readout_repack(ign_plan* p) {
-  for (auto& op : p->ro_ops)
-    for (auto& dp : op.layers)
-      if (dp.pk_w >= 0) HIP_TRY(launch_pack_dense(p->d_params + dp.off_w, p->d_packed + dp.pk_w, dp.in, dp.out, p->stream));
-  return IGN_OK;
-}
-
 int64_t space_rows(const ign_plan* p, const ign_batch* b, const RoTensor& t) {
   (void)p;
   if (t.space == RS_ENTITY) return b->rows[t.sid];

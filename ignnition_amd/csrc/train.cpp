@@ -670,8 +670,6 @@ int ign_batch_enable_training(ign_plan* p, ign_batch* b) {
   int rc = ensure_device(p);
   if (rc) return rc;
   UploadScope scope("ign_batch_enable_training");
-  const char* tcsr_env = getenv("IGN_TRAIN_CSR_GPU");
-  const bool tcsr_on = !tcsr_env || atoi(tcsr_env) != 0;   // the transposed CSRs on the GPU (train_csr.hip)
   const char* fine = getenv("IGN_BUILD_PROF_FINE");
   BuildMarks bm(fine && atoi(fine) != 0);   // IGN_BUILD_PROF_FINE=1: host sections of this build
   if ((rc = check_train_shapes(p))) return rc;
@@ -680,14 +678,13 @@ int ign_batch_enable_training(ign_plan* p, ign_batch* b) {
   t->stream = p->stream;
   if ((rc = alloc_states(p, b, t.get()))) return rc;
   for (size_t mi = 0; mi < p->mps.size(); ++mi) {
-    if ((rc = enable_mp(p, b, t.get(), mi, tcsr_on))) return rc;
+    if ((rc = enable_mp(p, b, t.get(), mi, p->train_csr_gpu))) return rc;
     bm.mark(mi == 0 ? "mp0" : mi == 1 ? "mp1" : "mp2+");
   }
   const TrainScratch z = train_scratch(p, b);
   if ((rc = alloc_mp_scratch(p, t.get(), z)) || (rc = alloc_readout(p, b, t.get(), z))) return rc;
   if ((rc = talloc(t.get(), &t->part, z.part)) || (rc = talloc(t.get(), &t->bsum, (32 + 1) * 3 * 32))) return rc;
-  if (const char* v = getenv("IGN_DEFER_WGRAD"); !v || atoi(v) != 0)
-    if ((rc = alloc_deferred(p, b, t.get()))) return rc;
+  if (p->defer_wgrad && (rc = alloc_deferred(p, b, t.get()))) return rc;
   bm.mark("rest");
   HIP_TRY(hipStreamSynchronize(upload_stream()));   // IGN_POOL_POISON fills have landed
   HIP_TRY(upload_flush());                           // (and every staged copy)

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kernel_shapes.h"
+
 // Backward of the ordered update (reverse-time GRU, AUX:767-796).
 struct SeqBwdArgs {
   const float* hs;           // [n_steps + n_dst][H]: order position p owns rows step_ptr[p]+p .. +len[p]
@@ -56,13 +58,11 @@ struct SumBwdArgs {
 };
 
 hipError_t launch_pack_a(const float* M, int rows, int cols, float* out, hipStream_t st);
-bool bwd_shape_supported(int din, int h);
 hipError_t launch_seq_gru_bwd(const SeqBwdArgs& a, int h, hipStream_t st);
 // the ordered backward's tile headers from the forward's (SeqGruArgs::hdr: {row, len, step_ptr,
 // first code}): the same with the code of each position's last step; n_pos padded to whole tiles
 hipError_t launch_seq_bwd_hdr(const int32_t* fwd_hdr, const uint32_t* step_code, int64_t n_pos, int32_t* out,
                               hipStream_t st);
-bool seq_bwd_fused_supported(int h);
 // fused form: the per-wave partial slots one launch writes, and their reduction into dU / db_rec /
 // db_in (part may hold the partials of several launches, waves = their total)
 int64_t seq_bwd_fused_waves(const SeqBwdArgs& a, int h);
@@ -98,7 +98,6 @@ hipError_t launch_csr_gather_add(float* out, int64_t n_rows, const int32_t* ptr,
                                  const float* in, int cols, int accumulate, hipStream_t st);
 // out[r][m] (+)= sum_k in[r][k] * Mat[m][k] (Mat packed by launch_pack_a, K % 16 == 0, M % 16 == 0),
 // then (act >= 0) multiplied by act'(aprev[r][m]) given the activation values aprev.
-bool row_gemm_supported(int K, int M);
 hipError_t launch_row_gemm_t(const float* in, int64_t n, int K, const float* Ap, int M, float* out, int accumulate,
                              int act, const float* aprev, hipStream_t st);
 // generic VALU version (any K, M): out[r][m] (+)= sum_k in[r][k] * Mat[m][k] (Mat row-major [M][K])
@@ -127,7 +126,6 @@ hipError_t launch_tsgemm_partials(const float* A, int lda, const float* B, int l
 hipError_t launch_tsgemm_add(const float* A, int lda, const float* B, int ldb, int64_t n_rows, int M, int N,
                              float* part, float* C, float* Cb, hipStream_t st);
 // forward Dense layer for the training readout: y = act(x W + b), MFMA when packed fragments exist
-bool dense_fwd_supported(int K, int M);
 hipError_t launch_dense_fwd(const float* x, int64_t n, int K, int x_stride, const float* Wp, const float* W,
                             const float* bias, int M, int act, float* y, hipStream_t st);
 // C[N] += sum_r B[r][:N]

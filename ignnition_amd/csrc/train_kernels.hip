@@ -1177,13 +1177,6 @@ hipError_t launch_pack_a(const float* M, int rows, int cols, float* out, hipStre
   return hipGetLastError();
 }
 
-bool bwd_shape_supported(int din, int h) {
-  return (din == 16 || din == 32 || din == 64) && (h == 16 || h == 32 || h == 64) && (h != 64 || din == 64) &&
-         (din != 64 || h == 64);
-}
-
-bool seq_bwd_fused_supported(int h) { return h == 16 || h == 32; }
-
 int64_t seq_bwd_partial_floats(int h) { return (int64_t)(kBwdMaxWaves + kTsSegs) * (h + 2) * 3 * h; }
 
 template <int H, int RC>
@@ -1562,10 +1555,6 @@ hipError_t launch_csr_gather_add(float* out, int64_t n_rows, const int32_t* ptr,
   return hipGetLastError();
 }
 
-bool row_gemm_supported(int K, int M) {
-  return (K == 48 || K == 96 || K == 192 || K == 256) && (M == 16 || M == 32 || M == 64 || M == 256);
-}
-
 hipError_t launch_row_gemm_t(const float* in, int64_t n, int K, const float* Ap, int M, float* out, int accumulate,
                              int act, const float* aprev, hipStream_t st) {
   if (n == 0) return hipSuccess;
@@ -1673,11 +1662,6 @@ hipError_t launch_partials_reduce_add(float* part, int64_t nchunks, int M, int N
 
 hipError_t launch_colsum_add(const float* B, int ldb, int64_t n_rows, int N, float* part, float* C, hipStream_t st) {
   return launch_tsgemm_add(nullptr, 0, B, ldb, n_rows, 0, N, part, nullptr, C, st);
-}
-
-bool dense_fwd_supported(int K, int M) {
-  return (K == 16 || K == 32 || K == 48 || K == 64 || K == 96 || K == 128 || K == 256) &&
-         (M == 16 || M == 32 || M == 64 || M == 128 || M == 256);
 }
 
 hipError_t launch_dense_fwd(const float* x, int64_t n, int K, int x_stride, const float* Wp, const float* W,
