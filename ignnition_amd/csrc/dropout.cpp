@@ -3,7 +3,7 @@
 // (ign_dropout_keep).  The reference builds every layer with getattr(tf.keras.layers, type_layer)
 // (AUX:869-1003) and calls the readout networks with training=(mode == TRAIN) (GM:612-629): a
 // Dropout is tf.nn.dropout in training and the identity otherwise.  The kernels are
-// dropout_kernels.hip; train.cpp and readout.cpp run them.
+// dropout_kernels.hip; dense_stack.cpp runs them.
 #include <climits>
 #include <cmath>
 

@@ -37,6 +37,7 @@
 
 #include "engine_internal.h"
 #include "batch_lower.h"
+#include "dense_stack.h"
 #include "train_kernels.h"
 
 namespace ign {
@@ -784,19 +785,8 @@ int message_net_fwd(ign_plan* p, const MsgNN& nn, const MPB& mb, int s, const fl
     col += g.width[q];
   }
   HIP_TRY(launch_msg_gather(g, st));
-  const float* in = mb.d_msg_in[s];
-  int stride = nn.din_pad;
-  for (size_t l = 0; l < nn.layers.size(); ++l) {
-    const DenseP& dp = nn.layers[l];
-    const bool mfma = dp.pk_w >= 0;
-    const int K = l == 0 ? (mfma ? nn.din_pad : nn.din) : dp.in;
-    HIP_TRY(launch_dense_fwd(in, mb.n_edges[s], K, stride, mfma ? p->d_packed + dp.pk_w : nullptr,
-                             p->d_params + dp.off_w, dp.use_bias ? p->d_params + dp.off_b : nullptr, dp.out, dp.act,
-                             mb.d_msg_layer[s][l], st));
-    in = mb.d_msg_layer[s][l];
-    stride = dp.out;
-  }
-  return IGN_OK;
+  return dense_stack_forward(p, {nn.layers.data(), (int)nn.layers.size(), mb.n_edges[s], mb.d_msg_in[s], nn.din_pad,
+                                 mb.d_msg_layer[s].data(), mb.d_msg_layer[s].back()}, st);
 }
 
 int check_pb(ign_plan* p, ign_batch* b) {

@@ -3,7 +3,10 @@
 // GM:660-675).
 //
 //   neural_network       Readout_nn (AUX:1188-1211): Dense stack on the axis-1 concatenation of
-//                        its inputs; weights readout_model_<op index> (GM:352-358)
+//                        its inputs; weights readout_model_<op index> (GM:352-358).  The stack
+//                        itself, with its Dropout sites in training, is dense_stack.cpp's walk
+//                        (the one predict and the message networks take); its backward and the
+//                        other operations' are train.cpp's readout_ops_backward
 //   pooling              Pooling_operation (AUX:1136-1185): sum / mean / max over axis 0 of one
 //                        graph's rows -> [1, F]
 //   product              Product_operation element_wise (AUX:1054-1094): tf.multiply
@@ -22,7 +25,7 @@
 #include <algorithm>
 #include <cstring>
 
-#include "engine_internal.h"
+#include "dense_stack.h"
 #include "readout_kernels.h"
 #include "train_kernels.h"
 
@@ -135,7 +138,6 @@ int readout_batch(ign_plan* p, ign_batch* b, const ign_batch_desc* d) {
 }
 
 int readout_ops_run(ign_plan* p, ign_batch* b, hipStream_t st, const float* const* ent, const DropRun* drop) {
-  const float* prm = p->d_params;
   const int NE = (int)p->ents.size();
   auto readout_tensor = [&](const ign_plan* pp, const ign_batch* bb, int id) -> const float* {
     return ent && id < NE ? ent[id] : ign::readout_tensor(pp, bb, id);
@@ -156,25 +158,9 @@ int readout_ops_run(ign_plan* p, ign_batch* b, hipStream_t st, const float* cons
           }
           x = bo.cat;
         }
-        int stride = op.in_width;
-        const int NL = (int)op.layers.size();
-        // Dropout sites (training only): in front of a layer each masks into its own buffer, never
-        // the tensor another operation reads; after the last layer the output goes to the first
-        // site's buffer and the masked result to the op's tensor
-        int tail0 = 0;
-        const int tail = drop ? drop_range(p, (int)k, NL, &tail0) : 0;
-        for (int l = 0; l < NL; ++l) {
-          const DenseP& dl = op.layers[l];
-          int s0 = 0;
-          if (const int ns = drop ? drop_range(p, (int)k, l, &s0) : 0)
-            HIP_TRY(drop_fwd_chain(p, *drop, s0, ns, x, n * dl.in, st, &x));
-          float* y = l + 1 < NL ? bo.tmp[l] : tail ? drop->buf[tail0] : bo.out[0];
-          HIP_TRY(launch_dense_fwd(x, n, dl.in, stride, dl.pk_w >= 0 ? p->d_packed + dl.pk_w : nullptr,
-                                   prm + dl.off_w, dl.use_bias ? prm + dl.off_b : nullptr, dl.out, dl.act, y, st));
-          x = y;
-          stride = dl.out;
-        }
-        if (tail) HIP_TRY(drop_fwd_tail(p, *drop, tail0, tail, bo.out[0], n * op.layers.back().out, st));
+        const DenseStackRun r{op.layers.data(), (int)op.layers.size(), n, x, op.in_width, bo.tmp.data(), bo.out[0],
+                              drop, (int)k};
+        if (int rc = dense_stack_forward(p, r, st)) return rc;
         break;
       }
       case IGN_RO_POOLING:            // GM:632-637

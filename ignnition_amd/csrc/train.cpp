@@ -22,7 +22,7 @@
 #include <memory>
 #include <vector>
 
-#include "engine_internal.h"
+#include "dense_stack.h"
 #include "readout_kernels.h"
 #include "train_kernels.h"
 #include "train_lower.h"
@@ -246,13 +246,6 @@ int check_train(ign_plan* p, ign_batch* b) {
   return set_device(p->device);
 }
 
-// the l2 kernel regularizer's gradient (AUX:833-834) of Dense layer d with K inputs:
-// grads[W] += 2 l2 scale W; nothing where the layer has none
-int add_l2_grad(const ign_plan* p, const DenseP& d, float* grads, float scale, int K, hipStream_t st) {
-  if (d.l2 != 0.f) HIP_TRY(launch_axpy(grads + d.off_w, p->d_params + d.off_w, 2.f * d.l2 * scale, (int64_t)K * d.out, st));
-  return IGN_OK;
-}
-
 // project every source of sorted MP mb into its table, from the given source states
 int build_table(ign_plan* p, const MPP& mp, const MPB& mb, const CellP& cp, const float* const* src) {
   const int W3 = 3 * cp.H;
@@ -277,25 +270,14 @@ int build_table(ign_plan* p, const MPP& mp, const MPB& mb, const CellP& cp, cons
 int msg_net_backward(ign_plan* p, ign_batch* b, TrainState* t, const MPP& mp, const MPB& mb, const MPTrain& mt,
                      int s, float* dsrc, float* ddst, float* grads, hipStream_t st) {
   const MsgNN& nn = mp.nn[s];
-  const int64_t ne = mb.n_edges[s];
-  const int L = (int)nn.layers.size();
-  int zi = 0;
-  HIP_TRY(launch_act_bwd(t->dmsg, mb.d_msg_layer[s][L - 1], ne * nn.layers[L - 1].out, nn.layers[L - 1].act,
-                         t->mz[0], st));
-  for (int l = L - 1; l >= 0; --l) {
-    const DenseP& d = nn.layers[l];
-    const int K = l == 0 ? nn.din : nn.layers[l - 1].out;
-    const float* A = l == 0 ? mb.d_msg_in[s] : mb.d_msg_layer[s][l - 1];
-    const int lda = l == 0 ? nn.din_pad : nn.layers[l - 1].out;
-    HIP_TRY(launch_tsgemm_add(A, lda, t->mz[zi], d.out, ne, K, d.out, t->part, grads + d.off_w,
-                              d.use_bias ? grads + d.off_b : nullptr, st));
-    if (l > 0)
-      HIP_TRY(launch_row_gemm_t_generic(t->mz[zi], ne, d.out, p->d_params + d.off_w, K, t->mz[1 - zi], 0,
-                                        nn.layers[l - 1].act, mb.d_msg_layer[s][l - 1], st));
-    else
-      HIP_TRY(launch_row_gemm_t_generic(t->mz[zi], ne, d.out, p->d_params + d.off_w, K, t->mdin, 0, -1, nullptr, st));
-    zi = 1 - zi;
-  }
+  DenseStackRun r{nn.layers.data(), (int)nn.layers.size(), mb.n_edges[s], mb.d_msg_in[s], nn.din_pad,
+                  mb.d_msg_layer[s].data(), mb.d_msg_layer[s].back()};
+  r.dy = t->dmsg;
+  r.gz = t->mz;
+  r.part = t->part;
+  r.grads = grads;
+  r.dx = t->mdin;   // overwritten: gathered below
+  if (int rc = dense_stack_backward(p, r, st)) return rc;
   int col = 0;
   for (size_t q = 0; q < nn.inputs.size(); ++q) {
     const int w = nn.widths[q];
@@ -307,6 +289,84 @@ int msg_net_backward(ign_plan* p, ign_batch* b, TrainState* t, const MPP& mp, co
       HIP_TRY(launch_csr_gather_cols_add(ddst, b->rows[mp.dst], mt.ndst_ptr[s], mt.ndst_idx[s], t->mdin, nn.din,
                                          col, w, 1, st));
     col += w;   // edge_params: input data, no gradient
+  }
+  return IGN_OK;
+}
+
+// readout tensor id (GM:660-675): an entity's final states or an operation's output, and its gradient
+const float* ro_tensor(const ign_batch* b, const TrainState* t, int id) {
+  return id < (int)t->ver.size() ? t->ver[id][t->cur[id]] : b->ro_buf[id];
+}
+float* ro_grad(TrainState* t, int id) { return id < (int)t->ver.size() ? t->dS[0][id] : t->dT[id]; }
+
+// Backward of a readout Dense stack r (predict's, an operation's) from d(y) in dy: d(x) is added to
+// the one input's gradient, or written to cat_grad and split by columns over the inputs (concat axis 1)
+int ro_stack_backward(ign_plan* p, TrainState* t, DenseStackRun r, const float* dy, float* const* gz,
+                      const std::vector<int>& in, float* cat_grad, hipStream_t st) {
+  r.dy = dy;
+  r.gz = gz;
+  r.part = t->part;
+  r.grads = t->grads;
+  r.l2_scale = &t->l2_scale;
+  r.dx_acc = in.size() == 1;
+  r.dx = r.dx_acc ? ro_grad(t, in[0]) : cat_grad;
+  if (int rc = dense_stack_backward(p, r, st)) return rc;
+  int col = 0;
+  for (size_t q = 0; !r.dx_acc && q < in.size(); ++q) {
+    const int w = p->ro_t[in[q]].width;
+    HIP_TRY(launch_split_cols_add(ro_grad(t, in[q]), r.n, w, cat_grad, r.ldx, col, st));
+    col += w;
+  }
+  return IGN_OK;
+}
+
+// predict's Dense stack (p->dense) on input x, for the training forward and its backward
+DenseStackRun predict_stack(const ign_plan* p, const ign_batch* b, TrainState* t, const float* x) {
+  return {p->dense.data(), (int)p->dense.size(), b->n_pred, x, p->ro_width, t->act.data(), b->d_pred, &t->drop, -1};
+}
+
+// Backward of the readout operations before predict (GM:605-655), last first: each turns the
+// gradient of its output tensors (t->dT) into additions to its inputs' gradients
+int readout_ops_backward(ign_plan* p, ign_batch* b, TrainState* t, hipStream_t st) {
+  int rc;
+  int xi = (int)t->rx_ptr.size();   // extend CSRs are stored in op order, two per op
+  for (int k = (int)p->ro_ops.size() - 1; k >= 0; --k) {
+    const RoOp& op = p->ro_ops[k];
+    const RoBatchOp& bo = b->ro[k];
+    const RoTensor& t0 = p->ro_t[op.in[0]];
+    const int64_t n = space_rows(p, b, t0);
+    switch (op.type) {
+      case IGN_RO_NEURAL_NETWORK: {   // Readout_nn (AUX:1188-1211): Dense stack on concat(inputs)
+        const float* x = op.in.size() > 1 ? bo.cat : ro_tensor(b, t, op.in[0]);
+        const DenseStackRun r{op.layers.data(), (int)op.layers.size(), n, x, op.in_width, bo.tmp.data(), bo.out[0],
+                              &t->drop, k};
+        if ((rc = ro_stack_backward(p, t, r, t->dT[op.out], t->rz, op.in, t->rcat, st))) return rc;
+        break;
+      }
+      case IGN_RO_POOLING:   // Pooling_operation (AUX:1165-1185)
+        HIP_TRY(launch_pool_bwd(ro_tensor(b, t, op.in[0]), bo.out[0], t->dT[op.out], t->rties, t0.width, bo.d_inoff, b->G,
+                                op.mode, n, ro_grad(t, op.in[0]), st));
+        break;
+      case IGN_RO_PRODUCT: {   // element_wise (AUX:1081-1088)
+        const RoTensor& t1 = p->ro_t[op.in[1]];
+        const RoTensor& to = p->ro_t[op.out];
+        const int ag = t0.space == RS_GRAPH && to.space != RS_GRAPH, bg = t1.space == RS_GRAPH && to.space != RS_GRAPH;
+        HIP_TRY(launch_product_bwd(t->dT[op.out], ro_tensor(b, t, op.in[1]), t0.width, t1.width, to.width, ag, bg, bo.d_seg,
+                                   b->G, n, ro_grad(t, op.in[0]), st));
+        HIP_TRY(launch_product_bwd(t->dT[op.out], ro_tensor(b, t, op.in[0]), t1.width, t0.width, to.width, bg, ag, bo.d_seg,
+                                   b->G, space_rows(p, b, t1), ro_grad(t, op.in[1]), st));
+        break;
+      }
+      case IGN_RO_EXTEND: {   // Extend_adjacencies (AUX:1236-1265): gathers, so scatter back per row
+        xi -= 2;
+        for (int j = 0; j < 2; ++j) {
+          const RoTensor& tj = p->ro_t[op.in[j]];
+          HIP_TRY(launch_csr_gather_cols_add(ro_grad(t, op.in[j]), space_rows(p, b, tj), t->rx_ptr[xi + j],
+                                             t->rx_idx[xi + j], t->dT[op.out + j], tj.width, 0, tj.width, 1, st));
+        }
+        break;
+      }
+    }
   }
   return IGN_OK;
 }
@@ -794,31 +854,26 @@ int ign_forward_train_end(ign_plan* p, ign_batch* b, float* pred_out) {
   // this forward's Dropout masks (ign_batch_set_dropout), kept for the backward that regenerates them
   t->drop = DropRun{b->drop_seed, b->drop_step, t->dbuf.data()};
   if (!p->ro_ops.empty() && (rc = readout_ops_run(p, b, st, ent.data(), &t->drop))) return rc;
-  auto tensor = [&](int id) -> const float* { return id < E ? ent[id] : b->ro_buf[id]; };
   const int64_t P = b->n_pred;
-  const float* x = tensor(p->ro_in[0]);
+  const float* x = ro_tensor(b, t, p->ro_in[0]);
   if (p->ro_in.size() > 1) {
     int col = 0;
     for (int id : p->ro_in) {
-      HIP_TRY(launch_concat_cols(t->ro_x, P, p->ro_width, col, tensor(id), p->ro_t[id].width, st));
+      HIP_TRY(launch_concat_cols(t->ro_x, P, p->ro_width, col, ro_tensor(b, t, id), p->ro_t[id].width, st));
       col += p->ro_t[id].width;
     }
     x = t->ro_x;
   }
-  const float* in = x;
-  int in_stride = p->ro_width;
   // the inference readout kernel (readout_h16) with its activations written out: one launch, no
   // re-read of layer 1's output (readout.cpp's fused-readout conditions, variant 4)
   // (a stack with a Dropout site runs layer by layer: the mask sits between two of its launches)
   const bool fused = p->train_fused_readout && p->fused_readout && p->readout_variant >= 4 && p->dense.size() == 3 &&
                      p->dense[1].pk_h >= 0 && p->dense[0].pk_bf >= 0 && p->dense[1].pk_bf >= 0 &&
                      p->dense[0].use_bias && p->dense[1].use_bias && !stack_has_dropout(p, -1);
-  const int L = (int)p->dense.size();
-  int tail0 = 0;
-  const int tail = drop_range(p, -1, L, &tail0);   // sites after the last layer mask the predictions
+  if (!fused && (rc = dense_stack_forward(p, predict_stack(p, b, t, x), st))) return rc;
   if (fused) {
     const DenseP &l1 = p->dense[0], &l2 = p->dense[1], &l3 = p->dense[2];
-    Readout3Args a{x, P, in_stride,
+    Readout3Args a{x, P, p->ro_width,
                    nullptr, p->d_params + l1.off_b,   // readout_h16 reads its pieces from pk_h only
                    nullptr, p->d_params + l2.off_b,
                    p->d_params + l3.off_w, l3.use_bias ? p->d_params + l3.off_b : nullptr,
@@ -828,25 +883,6 @@ int ign_forward_train_end(ign_plan* p, ign_batch* b, float* pred_out) {
     else
       HIP_TRY(launch_readout_h16(a, p->d_packed + l2.pk_h, l1.in, st));
   }
-  for (size_t l = 0; !fused && l < p->dense.size(); ++l) {
-    const DenseP& d = p->dense[l];
-    int s0 = 0;
-    if (const int ns = drop_range(p, -1, (int)l, &s0))   // masks a copy of the layer's input
-      HIP_TRY(drop_fwd_chain(p, t->drop, s0, ns, in, P * d.in, st, &in));
-    float* o = l + 1 < p->dense.size() ? t->act[l] : tail ? t->dbuf[tail0] : b->d_pred;
-    if (p->train_dense_bf && p->train_dense_h16 && d.pk_hn >= 0 && in_stride % 4 == 0)   // split-fp16 (x3)
-      HIP_TRY(launch_dense_h16(in, P, d.in, in_stride, p->d_packed + d.pk_hn, d.use_bias ? p->d_params + d.off_b : nullptr,
-                               d.out, d.act, o, st));
-    else if (p->train_dense_bf && d.pk_bfn >= 0 && in_stride % 4 == 0)   // split-bf16, fp32-exact operands
-      HIP_TRY(launch_dense_bf(in, P, d.in, in_stride, p->d_packed + d.pk_bfn, d.use_bias ? p->d_params + d.off_b : nullptr,
-                              d.out, d.act, o, st));
-    else
-      HIP_TRY(launch_dense_fwd(in, P, d.in, in_stride, d.pk_w >= 0 ? p->d_packed + d.pk_w : nullptr,
-                               p->d_params + d.off_w, d.use_bias ? p->d_params + d.off_b : nullptr, d.out, d.act, o, st));
-    in = o;
-    in_stride = d.out;
-  }
-  if (tail) HIP_TRY(drop_fwd_tail(p, t->drop, tail0, tail, b->d_pred, P * b->out_units, st));
   if (pred_out) {
     HIP_TRY(hipMemcpyAsync(pred_out, b->d_pred, P * b->out_units * sizeof(float), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -943,7 +979,6 @@ int ign_backward_begin(ign_plan* p, ign_batch* b, const float* dpred, float* gra
   t->forward_done = false;
   hipStream_t st = p->stream;
   const int E = (int)p->ents.size();
-  const int64_t P = b->n_pred;
   set_tsgemm_bf(p->tsgemm_bf);
   HIP_TRY(hipMemsetAsync(grads, 0, p->n_params * sizeof(float), st));
   t->grads = grads;
@@ -953,182 +988,15 @@ int ign_backward_begin(ign_plan* p, ign_batch* b, const float* dpred, float* gra
   t->dcur.assign(E, 0);
   for (int e = 0; e < E; ++e)   // owned and halo rows (edge-cut: peers' gradients arrive in the owned rows)
     HIP_TRY(hipMemsetAsync(t->dS[0][e], 0, (b->rows[e] + b->halo[e]) * p->ents[e].hidden_dim * sizeof(float), st));
-
-  // ---- readout (GM:605-629) in reverse: predict, then the operations before it
   for (size_t id = 0; id < t->dT.size(); ++id)
     if (t->dT[id])
       HIP_TRY(hipMemsetAsync(t->dT[id], 0, space_rows(p, b, p->ro_t[id]) * p->ro_t[id].width * sizeof(float), st));
-  auto tensor = [&](int id) -> const float* { return id < E ? t->ver[id][t->cur[id]] : b->ro_buf[id]; };
-  auto grad_of = [&](int id) -> float* { return id < E ? t->dS[0][id] : t->dT[id]; };
-  const int L = (int)p->dense.size();
-  const float* X = p->ro_in.size() > 1 ? t->ro_x : tensor(p->ro_in[0]);
-  int zi = 0;
-  // Dropout sites (ign_plan_add_dropout): the masks of this forward, regenerated.  A site in front
-  // of layer l sits between act[l - 1] = y (the layer below's activation derivative reads it) and
-  // its own buffer z (layer l's input: its weight gradient reads it); the fusions below that form a
-  // layer's gradient rows from the layer above's decline across one
-  int s0 = 0, ns = drop_range(p, -1, L, &s0);
-  if (ns) {   // after the last layer: d(pred) -> d(y), y in the first site's buffer
-    HIP_TRY(drop_bwd_chain(p, t->drop, s0, ns, dpred, t->dz[1], P * p->dense[L - 1].out, st));
-    HIP_TRY(launch_act_bwd(t->dz[1], t->dbuf[s0], P * p->dense[L - 1].out, p->dense[L - 1].act, t->dz[0], st));
-  } else
-  HIP_TRY(launch_act_bwd(dpred, b->d_pred, P * p->dense[L - 1].out, p->dense[L - 1].act, t->dz[0], st));
-  // a 1-unit output layer's backward rows, dz[r][k] = dz_out[r] w[k] act'(a[r][k]), are formed by
-  // the layer below's input-gradient kernel (dense_bf) as it loads a, and written over a in place
-  // for that layer's weight gradient: row_outer_t's separate read of a is gone
-  OuterRows xo{};
-  auto dense_t_bf = [&](const DenseP& d) { return p->train_dense_bf && (p->train_dense_h16 ? d.pk_ht >= 0 : d.pk_bft >= 0); };
-  for (int l = L - 1; l >= 0; --l) {
-    const DenseP& d = p->dense[l];
-    ns = drop_range(p, -1, l, &s0);   // sites in front of this layer: its input is the last one's z
-    const float* A = ns ? t->dbuf[s0 + ns - 1] : l == 0 ? X : t->act[l - 1];
-    const bool outer = xo.s != nullptr;   // this layer's dz is formed by its dense_t from act[l]
-    if (!outer)
-      HIP_TRY(launch_tsgemm_add(A, d.in, t->dz[zi], d.out, P, d.in, d.out, t->part, grads + d.off_w,
-                                d.use_bias ? grads + d.off_b : nullptr, st));
-    if (l > 0 && d.out == 1 && d.in % 4 == 0 && p->fuse_outer_bwd && dense_t_bf(p->dense[l - 1]) && !ns) {
-      if ((rc = add_l2_grad(p, d, grads, l2_scale, d.in, st))) return rc;
-      xo = OuterRows{t->dz[zi], p->d_params + d.off_w, p->dense[l - 1].act, t->act[l - 1]};
-      continue;   // zi stays: dz[zi] holds dz_out for the layer below
-    }
-    if (!outer && (rc = add_l2_grad(p, d, grads, l2_scale, d.in, st))) return rc;
-    float* out;
-    int act = -1, acc = 0;
-    const float* aprev = nullptr;
-    if (l > 0) {
-      out = t->dz[1 - zi];
-      if (!ns) {   // (across a site: d(z) here, the mask and the activation derivative below)
-        act = p->dense[l - 1].act;
-        aprev = t->act[l - 1];
-      }
-    } else if (p->ro_in.size() > 1) {
-      out = t->dro;
-    } else if (ns) {
-      out = t->dz[1 - zi];   // d(masked copy of the input): masked below, then added to the input's gradient
-    } else {
-      out = grad_of(p->ro_in[0]);
-      acc = 1;
-    }
-    const float* dzin = outer ? xo.out : t->dz[zi];
-    if (p->train_dense_bf && p->train_dense_h16 && d.pk_ht >= 0)   // split-fp16 (x3)
-      HIP_TRY(launch_dense_h16_t(dzin, P, d.out, p->d_packed + d.pk_ht, d.in, out, acc, act, aprev, st, xo));
-    else if (p->train_dense_bf && d.pk_bft >= 0)   // split-bf16, fp32-exact operands
-      HIP_TRY(launch_dense_bf_t(dzin, P, d.out, p->d_packed + d.pk_bft, d.in, out, acc, act, aprev, st, xo));
-    else if (outer)
-      return fail(IGN_ERR_RUNTIME, "on-the-fly output-layer gradient without a dense_bf backward");
-    else if (d.pk_wt >= 0)
-      HIP_TRY(launch_row_gemm_t(t->dz[zi], P, d.out, p->d_packed + d.pk_wt, d.in, out, acc, act, aprev, st));
-    else
-      HIP_TRY(launch_row_gemm_t_generic(t->dz[zi], P, d.out, p->d_params + d.off_w, d.in, out, acc, act, aprev, st));
-    if (outer) {   // the weight gradient on the rows dense_t just wrote over act[l], then its l2 term
-      HIP_TRY(launch_tsgemm_add(A, d.in, xo.out, d.out, P, d.in, d.out, t->part, grads + d.off_w,
-                                d.use_bias ? grads + d.off_b : nullptr, st));
-      if ((rc = add_l2_grad(p, d, grads, l2_scale, d.in, st))) return rc;
-    }
-    xo = OuterRows{};
-    if (ns) {   // d(z) -> d(y) through the sites, last first
-      HIP_TRY(drop_bwd_chain(p, t->drop, s0, ns, out, out, P * d.in, st));
-      if (l > 0) {
-        HIP_TRY(launch_act_bwd(out, t->act[l - 1], P * d.in, p->dense[l - 1].act, t->dz[zi], st));
-        continue;   // the layer below's dz is in dz[zi]: zi stays
-      }
-      if (p->ro_in.size() == 1) HIP_TRY(launch_split_cols_add(grad_of(p->ro_in[0]), P, d.in, out, d.in, 0, st));
-    }
-    zi = 1 - zi;
-  }
-  if (p->ro_in.size() > 1) {   // split dX by columns into the input tensors (concat axis 1)
-    int col = 0;
-    for (int id : p->ro_in) {
-      const int w = p->ro_t[id].width;
-      HIP_TRY(launch_split_cols_add(grad_of(id), P, w, t->dro, p->ro_width, col, st));
-      col += w;
-    }
-  }
-  int xi = (int)t->rx_ptr.size();   // extend CSRs are stored in op order, two per op
-  for (int k = (int)p->ro_ops.size() - 1; k >= 0; --k) {
-    const RoOp& op = p->ro_ops[k];
-    const RoBatchOp& bo = b->ro[k];
-    const RoTensor& t0 = p->ro_t[op.in[0]];
-    const int64_t n = space_rows(p, b, t0);
-    switch (op.type) {
-      case IGN_RO_NEURAL_NETWORK: {   // Readout_nn (AUX:1188-1211): Dense stack on concat(inputs)
-        const int NL = (int)op.layers.size();
-        int rz = 0;
-        ns = drop_range(p, k, NL, &s0);   // Dropout sites, as in the predict stack above
-        if (ns) {
-          HIP_TRY(drop_bwd_chain(p, t->drop, s0, ns, t->dT[op.out], t->rz[1], n * op.layers[NL - 1].out, st));
-          HIP_TRY(launch_act_bwd(t->rz[1], t->dbuf[s0], n * op.layers[NL - 1].out, op.layers[NL - 1].act, t->rz[0], st));
-        } else
-        HIP_TRY(launch_act_bwd(t->dT[op.out], bo.out[0], n * op.layers[NL - 1].out, op.layers[NL - 1].act, t->rz[0], st));
-        for (int l = NL - 1; l >= 0; --l) {
-          const DenseP& d = op.layers[l];
-          const int K = l == 0 ? op.in_width : op.layers[l - 1].out;
-          ns = drop_range(p, k, l, &s0);
-          const float* A = ns ? t->dbuf[s0 + ns - 1] : l > 0 ? bo.tmp[l - 1] : op.in.size() > 1 ? bo.cat : tensor(op.in[0]);
-          HIP_TRY(launch_tsgemm_add(A, K, t->rz[rz], d.out, n, K, d.out, t->part, grads + d.off_w,
-                                    d.use_bias ? grads + d.off_b : nullptr, st));
-          if ((rc = add_l2_grad(p, d, grads, l2_scale, K, st))) return rc;
-          if (ns) {   // d(z), the masks last first, then the layer below's activation derivative or the input's gradient
-            float* g = l == 0 && op.in.size() > 1 ? t->rcat : t->rz[1 - rz];
-            HIP_TRY(launch_row_gemm_t_generic(t->rz[rz], n, d.out, p->d_params + d.off_w, K, g, 0, -1, nullptr, st));
-            HIP_TRY(drop_bwd_chain(p, t->drop, s0, ns, g, g, n * K, st));
-            if (l > 0) {
-              HIP_TRY(launch_act_bwd(g, bo.tmp[l - 1], n * K, op.layers[l - 1].act, t->rz[rz], st));
-            } else if (op.in.size() > 1) {
-              int col = 0;
-              for (int id : op.in) {
-                const int w = p->ro_t[id].width;
-                HIP_TRY(launch_split_cols_add(grad_of(id), n, w, t->rcat, op.in_width, col, st));
-                col += w;
-              }
-            } else {
-              HIP_TRY(launch_split_cols_add(grad_of(op.in[0]), n, K, g, K, 0, st));
-            }
-          } else
-          if (l > 0) {
-            HIP_TRY(launch_row_gemm_t_generic(t->rz[rz], n, d.out, p->d_params + d.off_w, K, t->rz[1 - rz], 0,
-                                              op.layers[l - 1].act, bo.tmp[l - 1], st));
-            rz = 1 - rz;
-          } else if (op.in.size() > 1) {
-            HIP_TRY(launch_row_gemm_t_generic(t->rz[rz], n, d.out, p->d_params + d.off_w, K, t->rcat, 0, -1, nullptr, st));
-            int col = 0;
-            for (int id : op.in) {
-              const int w = p->ro_t[id].width;
-              HIP_TRY(launch_split_cols_add(grad_of(id), n, w, t->rcat, op.in_width, col, st));
-              col += w;
-            }
-          } else {
-            HIP_TRY(launch_row_gemm_t_generic(t->rz[rz], n, d.out, p->d_params + d.off_w, K, grad_of(op.in[0]), 1, -1,
-                                              nullptr, st));
-          }
-        }
-        break;
-      }
-      case IGN_RO_POOLING:   // Pooling_operation (AUX:1165-1185)
-        HIP_TRY(launch_pool_bwd(tensor(op.in[0]), bo.out[0], t->dT[op.out], t->rties, t0.width, bo.d_inoff, b->G, op.mode,
-                                n, grad_of(op.in[0]), st));
-        break;
-      case IGN_RO_PRODUCT: {   // element_wise (AUX:1081-1088)
-        const RoTensor& t1 = p->ro_t[op.in[1]];
-        const RoTensor& to = p->ro_t[op.out];
-        const int ag = t0.space == RS_GRAPH && to.space != RS_GRAPH, bg = t1.space == RS_GRAPH && to.space != RS_GRAPH;
-        HIP_TRY(launch_product_bwd(t->dT[op.out], tensor(op.in[1]), t0.width, t1.width, to.width, ag, bg, bo.d_seg, b->G,
-                                   n, grad_of(op.in[0]), st));
-        HIP_TRY(launch_product_bwd(t->dT[op.out], tensor(op.in[0]), t1.width, t0.width, to.width, bg, ag, bo.d_seg, b->G,
-                                   space_rows(p, b, t1), grad_of(op.in[1]), st));
-        break;
-      }
-      case IGN_RO_EXTEND: {   // Extend_adjacencies (AUX:1236-1265): gathers, so scatter back per row
-        xi -= 2;
-        for (int j = 0; j < 2; ++j) {
-          const RoTensor& tj = p->ro_t[op.in[j]];
-          HIP_TRY(launch_csr_gather_cols_add(grad_of(op.in[j]), space_rows(p, b, tj), t->rx_ptr[xi + j], t->rx_idx[xi + j],
-                                             t->dT[op.out + j], tj.width, 0, tj.width, 1, st));
-        }
-        break;
-      }
-    }
-  }
+
+  // ---- readout (GM:605-629) in reverse: predict, then the operations before it
+  const float* x = p->ro_in.size() > 1 ? t->ro_x : ro_tensor(b, t, p->ro_in[0]);
+  if ((rc = ro_stack_backward(p, t, predict_stack(p, b, t, x), dpred, t->dz, p->ro_in, t->dro, st)) ||
+      (rc = readout_ops_backward(p, b, t, st)))
+    return rc;
   t->b_ri = (int)t->recs.size() - 1;
   t->b_open = true;
   return IGN_OK;
@@ -1314,11 +1182,8 @@ int ign_backward_end(ign_plan* p, ign_batch* b) {
   if ((rc = tsgemm_deferred_flush(p, t, st))) return rc;
   for (auto& mp : p->mps)   // message-network l2 terms (AUX:833-834), once per step
     for (auto& nn : mp.nn)
-      for (size_t l = 0; l < nn.layers.size(); ++l) {
-        const DenseP& d = nn.layers[l];
-        const int K = l == 0 ? nn.din : nn.layers[l - 1].out;
-        if ((rc = add_l2_grad(p, d, grads, t->l2_scale, K, st))) return rc;
-      }
+      for (auto& d : nn.layers)
+        if ((rc = add_l2_grad(p, d, grads, t->l2_scale, st))) return rc;
   return IGN_OK;
 }
 

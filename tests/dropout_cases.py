@@ -75,6 +75,25 @@ def readout_op_model(rate=0.5):
     return desc
 
 
+def nn_two_inputs_first_model():
+    """A Dropout in front of layer 0 of a readout neural_network operation with two inputs: the stack's
+    input gradient is written to the concat scratch, masked in place, then split by columns."""
+    desc = predict_model("two_layer", ops=[dict(_EMB, input=["path", "path"]), _POOL], predict_input=("g",))
+    desc["neural_networks"].append({"nn_name": "emb", "nn_type": "feed_forward", "nn_architecture": [
+        {"type_layer": "Dropout", "rate": 0.25},
+        {"type_layer": "Dense", "units": 24, "activation": "tanh"},
+        {"type_layer": "Dense", "units": 16, "activation": "selu"}]})
+    return desc
+
+
+def predict_two_inputs_first_model():
+    """The same in predict (odd_widths), reading the operation's output beside the path states."""
+    desc = predict_model("odd_widths", ops=[_EMB], predict_input=("pe", "path"))
+    desc["neural_networks"].append({"nn_name": "emb", "nn_type": "feed_forward", "nn_architecture": [
+        {"type_layer": "Dense", "units": 16, "activation": "tanh"}]})
+    return insert_dropout(desc, [(0, 0.25, {})])
+
+
 def inputs(desc, n_graphs=2, seed=SEED):
     """(dims, plan, graphs, labels, parameters) for NSFNET samples 0 .. n_graphs - 1, as
     predict_cases.predict_inputs; labels shaped like the predictions when they are per graph."""

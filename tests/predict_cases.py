@@ -2,8 +2,9 @@
 the forward parity, the gradient and the plan-lowering tests:
 {name: [(units, activation, extra Dense options), ...]}.
 
-Which kernels a case reaches (readout.cpp's fused-readout conditions, engine.cpp's readout(),
-train.cpp's ign_forward_train_end / ign_backward_begin):
+Which kernels a case reaches (readout.cpp's fused-readout conditions, engine.cpp's readout() in
+inference; in training train.cpp's ign_forward_train_end for the fused SAVE launch, else
+dense_stack.cpp's dense_stack_forward, and its dense_stack_backward called by ign_backward_begin):
 
   relu tanh sigmoid linear selu   256 a, 256 a, 1: the fused kernels' five ACT instantiations (readout3,
                                   readout_bf, readout_h16 with and without SAVE, readout_h32); act' of the layer

@@ -180,6 +180,8 @@ GRAD_CASES = {
     "four_layer": lambda: dc.dropout_model("four_layer", [(1, 0.5, {}), (3, 0.5, {})]),
     "odd_widths": lambda: dc.dropout_model("odd_widths", [(0, 0.25, {}), (2, 0.25, {})]),
     "readout_op": dc.readout_op_model,
+    "nn_two_inputs_first": dc.nn_two_inputs_first_model,
+    "predict_two_inputs_first": dc.predict_two_inputs_first_model,
 }
 _RUNS = {}
 
