@@ -10,18 +10,70 @@ int add_l2_grad(const ign_plan* p, const DenseP& d, float* grads, float scale, h
   return IGN_OK;
 }
 
+namespace {
+
+// the Dropout and LayerNormalization layers of run r in front of layer `before`, with their buffers
+struct Site {
+  bool norm;
+  int idx;
+  float* buf;
+};
+void sites_at(const ign_plan* p, const DenseStackRun& r, int before, std::vector<StackSite>* tmp, std::vector<Site>* out) {
+  out->clear();
+  if ((!r.drop || p->drops.empty()) && (!r.norm || p->norms.empty())) return;
+  stack_sites(p, r.stack, before, r.drop != nullptr, r.norm != nullptr, tmp);
+  for (const StackSite& s : *tmp) out->push_back({s.norm, s.idx, s.norm ? r.norm->buf[s.idx] : r.drop->buf[s.idx]});
+}
+
+// one layer forward: n rows of `units` from x (ldx apart) into y (contiguous)
+int site_forward(const ign_plan* p, const DenseStackRun& r, const Site& s, const float* x, int ldx, float* y, int units,
+                 hipStream_t st) {
+  if (s.norm) {
+    HIP_TRY(norm_fwd(p, s.idx, x, ldx, r.n, y, r.norm->stats ? r.norm->stats[s.idx] : nullptr, st));
+    return IGN_OK;
+  }
+  if (ldx != units) return fail(IGN_ERR_RUNTIME, "Dropout on rows that are not contiguous");
+  const DropSite& d = p->drops[s.idx];
+  HIP_TRY(launch_dropout_fwd(x, y, r.n * units, d.rate, d.scale, r.drop->seed ^ d.seed, (uint32_t)s.idx, r.drop->step, st));
+  return IGN_OK;
+}
+
+// and back: g = d(its output) -> gx = d(its input) (gx may be g; acc: added to gx, LayerNormalization
+// only); x = the layer's input rows.  A LayerNormalization adds its gamma / beta gradients to grads.
+int site_backward(const ign_plan* p, const DenseStackRun& r, const Site& s, const float* x, const float* g, float* gx,
+                  int units, int acc, hipStream_t st) {
+  if (s.norm) {
+    const NormSite& ns = p->norms[s.idx];
+    const float* stats = r.norm->stats[s.idx];
+    HIP_TRY(launch_layernorm_bwd_params(g, x, stats, r.n, units, r.part, ns.off_gamma >= 0 ? r.grads + ns.off_gamma : nullptr,
+                                        ns.off_beta >= 0 ? r.grads + ns.off_beta : nullptr, st));
+    HIP_TRY(launch_layernorm_bwd_dx(g, x, stats, ns.off_gamma >= 0 ? p->d_params + ns.off_gamma : nullptr, r.n, units, gx,
+                                    acc, st));
+    return IGN_OK;
+  }
+  const DropSite& d = p->drops[s.idx];
+  HIP_TRY(launch_dropout_bwd(g, gx, r.n * units, d.rate, d.scale, r.drop->seed ^ d.seed, (uint32_t)s.idx, r.drop->step, st));
+  return IGN_OK;
+}
+
+}  // namespace
+
 int dense_stack_forward(const ign_plan* p, const DenseStackRun& r, hipStream_t st) {
   const float* in = r.x;
-  int stride = r.ldx;
-  int tail0 = 0;
-  const int tail = r.drop ? drop_range(p, r.stack, r.L, &tail0) : 0;   // sites after the last layer mask y
+  int stride = r.ldx, rc;
+  std::vector<StackSite> tmp;
+  std::vector<Site> sites, tail;
+  sites_at(p, r, r.L, &tmp, &tail);   // the layers after the last Dense layer turn its output into y
   for (int l = 0; l < r.L; ++l) {
     const DenseP& d = r.layers[l];
-    int s0 = 0;
-    // in front of a layer each site masks into its own buffer, never the tensor another operation reads
-    if (const int ns = r.drop ? drop_range(p, r.stack, l, &s0) : 0)
-      HIP_TRY(drop_fwd_chain(p, *r.drop, s0, ns, in, r.n * d.in, st, &in));
-    float* o = l + 1 < r.L ? r.hid[l] : tail ? r.drop->buf[tail0] : r.y;
+    // in front of a layer each one writes its own buffer, never the tensor another operation reads
+    sites_at(p, r, l, &tmp, &sites);
+    for (const Site& s : sites) {
+      if ((rc = site_forward(p, r, s, in, stride, s.buf, d.in, st))) return rc;
+      in = s.buf;
+      stride = d.in;
+    }
+    float* o = l + 1 < r.L ? r.hid[l] : !tail.empty() ? tail[0].buf : r.y;
     const float* bias = d.use_bias ? p->d_params + d.off_b : nullptr;
     if (p->train_dense_bf && p->train_dense_h16 && d.pk_hn >= 0 && stride % 4 == 0)   // split-fp16 (x3)
       HIP_TRY(launch_dense_h16(in, r.n, d.in, stride, p->d_packed + d.pk_hn, bias, d.out, d.act, o, st));
@@ -33,8 +85,10 @@ int dense_stack_forward(const ign_plan* p, const DenseStackRun& r, hipStream_t s
     in = o;
     stride = d.out;
   }
-  // the last layer wrote the first site's buffer; the masked result goes to y
-  if (tail) HIP_TRY(drop_fwd_tail(p, *r.drop, tail0, tail, r.y, r.n * r.layers[r.L - 1].out, st));
+  // the last Dense layer wrote the first one's buffer; each reads its own and writes the next, the last y
+  for (size_t i = 0; i < tail.size(); ++i)
+    if ((rc = site_forward(p, r, tail[i], tail[i].buf, stride, i + 1 < tail.size() ? tail[i + 1].buf : r.y, stride, st)))
+      return rc;
   return IGN_OK;
 }
 
@@ -43,17 +97,21 @@ int dense_stack_backward(const ign_plan* p, const DenseStackRun& r, hipStream_t 
   const int64_t n = r.n;
   float* const* gz = r.gz;
   int rc, zi = 0;
-  // Dropout sites: the masks of this forward, regenerated.  A site in front of layer l sits between
-  // hid[l - 1] = y (the layer below's activation derivative reads it) and its own buffer z (layer
-  // l's input: its weight gradient reads it); the fusions below that form a layer's gradient rows
-  // from the layer above's decline across one
-  int s0 = 0, ns = r.drop ? drop_range(p, r.stack, L, &s0) : 0;
+  // Dropout and LayerNormalization layers: the masks and statistics of this forward.  One in front
+  // of layer l sits between hid[l - 1] = y (the layer below's activation derivative reads it) and
+  // its own buffer z (layer l's input: its weight gradient reads it); the fusions below that form a
+  // layer's gradient rows from the layer above's decline across one
+  std::vector<StackSite> tmp;
+  std::vector<Site> sites;
+  sites_at(p, r, L, &tmp, &sites);
   const DenseP& top = r.layers[L - 1];
   const float *dy = r.dy, *y = r.y;
-  if (ns) {   // after the last layer: d(masked y) -> d(y), y in the first site's buffer
-    HIP_TRY(drop_bwd_chain(p, *r.drop, s0, ns, dy, gz[1], n * top.out, st));
-    dy = gz[1];
-    y = r.drop->buf[s0];
+  if (!sites.empty()) {   // after the last layer: d(y behind them) -> d(y), y in the first one's buffer
+    for (int i = (int)sites.size() - 1; i >= 0; --i) {
+      if ((rc = site_backward(p, r, sites[i], sites[i].buf, dy, gz[1], top.out, 0, st))) return rc;
+      dy = gz[1];
+    }
+    y = sites[0].buf;
   }
   HIP_TRY(launch_act_bwd(dy, y, n * top.out, top.act, gz[0], st));
   // a 1-unit output layer's backward rows, dz[r][k] = dz_out[r] w[k] act'(a[r][k]), are formed by
@@ -63,8 +121,10 @@ int dense_stack_backward(const ign_plan* p, const DenseStackRun& r, hipStream_t 
   auto dense_t_bf = [&](const DenseP& d) { return p->train_dense_bf && (p->train_dense_h16 ? d.pk_ht >= 0 : d.pk_bft >= 0); };
   for (int l = L - 1; l >= 0; --l) {
     const DenseP& d = r.layers[l];
-    ns = r.drop ? drop_range(p, r.stack, l, &s0) : 0;   // sites in front of this layer: its input is the last one's z
-    const float* A = ns ? r.drop->buf[s0 + ns - 1] : l == 0 ? r.x : r.hid[l - 1];
+    sites_at(p, r, l, &tmp, &sites);   // in front of this layer: its input is the last one's z
+    const bool ns = !sites.empty();
+    if (ns && l == 0 && r.ldx != d.in) return fail(IGN_ERR_RUNTIME, "a layer in front of a padded Dense input");
+    const float* A = ns ? sites.back().buf : l == 0 ? r.x : r.hid[l - 1];
     auto wgrad = [&](const float* dz) {   // the layer's weight / bias gradient from its dz rows, then its l2 term
       HIP_TRY(launch_tsgemm_add(A, ns || l > 0 ? d.in : r.ldx, dz, d.out, n, d.in, d.out, r.part, r.grads + d.off_w,
                                 d.use_bias ? r.grads + d.off_b : nullptr, st));
@@ -77,10 +137,10 @@ int dense_stack_backward(const ign_plan* p, const DenseStackRun& r, hipStream_t 
       continue;   // zi stays: gz[zi] holds dz_out for the layer below
     }
     // the layer below's activation derivative rides on the input-gradient kernel, except across a
-    // site: d(z) there, the mask and the derivative below
+    // Dropout or LayerNormalization: d(z) there, its backward and the derivative below
     const int act = l > 0 && !ns ? r.layers[l - 1].act : -1;
     const float* aprev = l > 0 && !ns ? r.hid[l - 1] : nullptr;
-    // d(x) of layer 0 goes to dx; behind a site, a dx that is added to takes the masked rows below
+    // d(x) of layer 0 goes to dx; behind such a layer, a dx that is added to takes the rows below
     const bool to_dx = l == 0 && !(r.dx_acc && ns);
     float* out = to_dx ? r.dx : gz[1 - zi];
     const int acc = to_dx ? r.dx_acc : 0;
@@ -97,13 +157,19 @@ int dense_stack_backward(const ign_plan* p, const DenseStackRun& r, hipStream_t 
       HIP_TRY(launch_row_gemm_t_generic(gz[zi], n, d.out, p->d_params + d.off_w, d.in, out, acc, act, aprev, st));
     if (outer && (rc = wgrad(xo.out))) return rc;   // on the rows dense_t just wrote over hid[l]
     xo = OuterRows{};
-    if (ns) {   // d(z) -> d(y) through the sites, last first
-      HIP_TRY(drop_bwd_chain(p, *r.drop, s0, ns, out, out, n * d.in, st));
+    if (ns) {   // d(z) -> d(y) through them, last first, in place
+      // a LayerNormalization that stands first in front of layer 0 adds its rows to an added-to dx itself
+      const bool norm_to_dx = l == 0 && r.dx_acc && sites[0].norm;
+      for (int i = (int)sites.size() - 1; i >= 0; --i) {
+        const float* xin = i > 0 ? sites[i - 1].buf : l == 0 ? r.x : r.hid[l - 1];
+        const bool last = i == 0 && norm_to_dx;
+        if ((rc = site_backward(p, r, sites[i], xin, out, last ? r.dx : out, d.in, last, st))) return rc;
+      }
       if (l > 0) {
         HIP_TRY(launch_act_bwd(out, r.hid[l - 1], n * d.in, r.layers[l - 1].act, gz[zi], st));
         continue;   // the layer below's dz is in gz[zi]: zi stays
       }
-      if (r.dx_acc) HIP_TRY(launch_split_cols_add(r.dx, n, d.in, out, d.in, 0, st));
+      if (r.dx_acc && !norm_to_dx) HIP_TRY(launch_split_cols_add(r.dx, n, d.in, out, d.in, 0, st));
     }
     zi = 1 - zi;
   }

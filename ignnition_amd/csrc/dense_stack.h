@@ -1,4 +1,5 @@
-// dense_stack.h — one walk over a Dense stack (gemm, bias, activation, Dropout sites) and its
+// dense_stack.h — one walk over a Dense stack (gemm, bias, activation, Dropout and
+// LayerNormalization layers) and its
 // reverse, for every stack of the training step: predict (p->dense), a readout neural_network
 // operation (RoOp::layers), a message-creation network (MsgNN::layers).  Each layer's kernels
 // follow from its pk_* slots (plan_lower.cpp's layout_packed): only predict's layers have more
@@ -18,7 +19,8 @@ struct DenseStackRun {
   float* const* hid = nullptr;      // outputs of layers 0 .. L-2
   float* y = nullptr;               // the last layer's output, behind the sites after it
   const DropRun* drop = nullptr;    // Dropout: the forward's mask stream; null = no sites run (inference,
-  int stack = -1;                   // message networks).  stack: drop_range's id, -1 predict, k readout op k
+  int stack = -1;                   // message networks).  stack: the sites' stack id, -1 predict, k readout op k
+  const NormRun* norm = nullptr;    // LayerNormalization: the run's buffers; null = none run (message networks)
   // backward
   const float* dy = nullptr;        // d(y)
   float* const* gz = nullptr;       // two layer-gradient buffers (ping-pong) [n][widest]

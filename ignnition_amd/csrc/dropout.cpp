@@ -37,6 +37,7 @@ int plan_add_dropout(ign_plan* p, int stack, int before_layer, float rate, uint6
   d.rate = rate;
   d.scale = dropout_scale(rate);
   d.seed = layer_seed;
+  d.order = sites_in_front(p, stack, before_layer);
   auto key = [](const DropSite& s) { return std::make_pair(s.stack < 0 ? INT_MAX : s.stack, s.before); };
   size_t at = 0;
   while (at < p->drops.size() && key(p->drops[at]) <= key(d)) ++at;

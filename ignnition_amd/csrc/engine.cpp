@@ -656,6 +656,11 @@ int ign_batch_create(ign_plan* p, const ign_batch_desc* d, ign_batch** out) {
     }
   }
   if ((rc = dev_alloc(b.get(), &b->d_pred, P * b->out_units))) return rc;
+  for (size_t s = 0; s < p->norms.size(); ++s) {   // one buffer per LayerNormalization layer (readout ops and predict)
+    float* t = nullptr;
+    if ((rc = dev_alloc(b.get(), &t, std::max<int64_t>(1, norm_site_floats(p, b.get(), (int)s))))) return rc;
+    b->d_norm.push_back(t);
+  }
   // the resident tables here, on the building thread, not at the first forward: a training loop's
   // builders run ahead of the step, and the step's thread would otherwise build them inside the step
   // (fresh 512 x synth50 batches: 28 -> 56 ms per step once the training forward went resident)
@@ -1091,9 +1096,26 @@ int readout(ign_plan* p, ign_batch* b) {
   } else {
     const float* in = x;
     int in_stride = xs;
+    // predict's LayerNormalization layers, as dense_stack_forward runs them: each in front of a
+    // Dense layer writes its own buffer; after the last one, that layer writes the first's buffer
+    std::vector<StackSite> sites, tail;
+    if (!p->norms.empty()) stack_sites(p, -1, (int)p->dense.size(), false, true, &tail);
+    auto norm = [&](int s, const float* from, int ld, float* to) {
+      const double bytes = (double)P * 4.0 * p->norms[s].units;
+      tm.begin(K_READOUT, 8.0 * P * p->norms[s].units, 2.0 * bytes);
+      const hipError_t e = norm_fwd(p, s, from, ld, P, to, nullptr, st);
+      tm.end();
+      return e;
+    };
     for (size_t l = 0; l < p->dense.size(); ++l) {
       const DenseP& dl = p->dense[l];
-      float* o = (l + 1 == p->dense.size()) ? b->d_pred : b->d_ro_tmp[l];
+      if (!p->norms.empty()) stack_sites(p, -1, (int)l, false, true, &sites);
+      for (const StackSite& s : sites) {
+        HIP_TRY(norm(s.idx, in, in_stride, b->d_norm[s.idx]));
+        in = b->d_norm[s.idx];
+        in_stride = dl.in;
+      }
+      float* o = l + 1 < p->dense.size() ? b->d_ro_tmp[l] : tail.empty() ? b->d_pred : b->d_norm[tail[0].idx];
       tm.begin(K_READOUT, 2.0 * P * dl.in * dl.out, (double)P * 4.0 * (dl.in + dl.out));
       HIP_TRY(launch_dense_generic(in, P, dl.in, in_stride, prm + dl.off_w, dl.use_bias ? prm + dl.off_b : nullptr,
                                    dl.out, dl.act, o, st));
@@ -1101,6 +1123,8 @@ int readout(ign_plan* p, ign_batch* b) {
       in = o;
       in_stride = dl.out;
     }
+    for (size_t i = 0; i < tail.size(); ++i)
+      HIP_TRY(norm(tail[i].idx, b->d_norm[tail[i].idx], in_stride, i + 1 < tail.size() ? b->d_norm[tail[i + 1].idx] : b->d_pred));
   }
   return IGN_OK;
 }

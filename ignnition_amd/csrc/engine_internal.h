@@ -17,6 +17,7 @@
 #include "../../include/ignmp.h"
 #include "kernels.h"
 #include "dropout_kernels.h"
+#include "layernorm_kernels.h"
 #include "host_types.h"   // the host-only types (MPP, hvec, IdxArr, ...), shared with batch_lower.h
 #include "plan_lower.h"   // PlanModel: the lowered plan without the device
 
@@ -128,6 +129,12 @@ struct DropRun {
   uint32_t step = 0;
   float* const* buf = nullptr;   // per site: its output (a site before a layer) or its input (after the last)
 };
+// the LayerNormalization layers' buffers of a batch, per site of ign_plan::norms: buf as DropRun's;
+// stats [rows][2] = (mean, rstd) of the training forward for its backward, null in inference
+struct NormRun {
+  float* const* buf = nullptr;
+  float* const* stats = nullptr;
+};
 
 }  // namespace ign
 
@@ -153,62 +160,37 @@ struct ign_plan : PlanModel {
   ign_stats_t stats{};
   std::shared_ptr<DevPool> pool;  // batch / training buffers (created with the stream, ensure_device)
   std::string describe;           // ign_plan_create_json: ign_plan_describe_json's document
-  bool batch_made = false;        // ign_plan_add_dropout is refused from the first batch on
+  bool batch_made = false;        // ign_plan_add_dropout / _layernorm are refused from the first batch on
 };
 
 namespace ign {
-// the sites of `stack` in front of Dense layer `before`: [*first, *first + count)
-inline int drop_range(const ign_plan* p, int stack, int before, int* first) {
-  int n = 0;
-  *first = 0;
-  for (size_t s = 0; s < p->drops.size(); ++s)
-    if (p->drops[s].stack == stack && p->drops[s].before == before) {
-      if (!n) *first = (int)s;
-      ++n;
-    }
-  return n;
-}
 inline bool stack_has_dropout(const ign_plan* p, int stack) {
   for (auto& d : p->drops)
     if (d.stack == stack) return true;
   return false;
 }
-// x through the sites [first, first + count) in front of a layer: each writes its own buffer;
-// *out = the last one (x itself when count is 0)
-inline hipError_t drop_fwd_chain(const ign_plan* p, const DropRun& dr, int first, int count, const float* x, int64_t n,
-                                 hipStream_t st, const float** out) {
-  for (int s = first; s < first + count; ++s) {
-    const DropSite& d = p->drops[s];
-    hipError_t e = launch_dropout_fwd(x, dr.buf[s], n, d.rate, d.scale, dr.seed ^ d.seed, (uint32_t)s, dr.step, st);
-    if (e != hipSuccess) return e;
-    x = dr.buf[s];
-  }
-  *out = x;
-  return hipSuccess;
+// One Dropout or LayerNormalization layer in front of a Dense layer (or after the last one): which
+// list it is in, and its index there.
+struct StackSite {
+  bool norm;
+  int idx, order;
+};
+// the layers of `stack` in front of Dense layer `before`, in the architecture's order; the Dropout
+// sites only where `drops` (a training run), the LayerNormalization ones only where `norms`
+inline void stack_sites(const ign_plan* p, int stack, int before, bool drops, bool norms, std::vector<StackSite>* out) {
+  out->clear();
+  for (size_t s = 0; drops && s < p->drops.size(); ++s)
+    if (p->drops[s].stack == stack && p->drops[s].before == before) out->push_back({false, (int)s, p->drops[s].order});
+  for (size_t s = 0; norms && s < p->norms.size(); ++s)
+    if (p->norms[s].stack == stack && p->norms[s].before == before) out->push_back({true, (int)s, p->norms[s].order});
+  std::sort(out->begin(), out->end(), [](const StackSite& a, const StackSite& b) { return a.order < b.order; });
 }
-// the sites after a stack's last layer, which wrote its output y to buf[first]: each site reads
-// its buffer and writes the next one, the last writes `final`
-inline hipError_t drop_fwd_tail(const ign_plan* p, const DropRun& dr, int first, int count, float* final, int64_t n,
-                                hipStream_t st) {
-  for (int s = first; s < first + count; ++s) {
-    const DropSite& d = p->drops[s];
-    hipError_t e = launch_dropout_fwd(dr.buf[s], s + 1 < first + count ? dr.buf[s + 1] : final, n, d.rate, d.scale,
-                                      dr.seed ^ d.seed, (uint32_t)s, dr.step, st);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
-// the gradient back through the sites [first, first + count), last site first: g_in -> g_out,
-// the later launches in place on g_out (g_out may be g_in)
-inline hipError_t drop_bwd_chain(const ign_plan* p, const DropRun& dr, int first, int count, const float* g_in,
-                                 float* g_out, int64_t n, hipStream_t st) {
-  for (int s = first + count - 1; s >= first; --s) {
-    const DropSite& d = p->drops[s];
-    hipError_t e = launch_dropout_bwd(g_in, g_out, n, d.rate, d.scale, dr.seed ^ d.seed, (uint32_t)s, dr.step, st);
-    if (e != hipSuccess) return e;
-    g_in = g_out;
-  }
-  return hipSuccess;
+// LayerNormalization site s on n rows of x (ldx floats apart) into y; stats: NormRun's, or null
+inline hipError_t norm_fwd(const ign_plan* p, int s, const float* x, int ldx, int64_t n, float* y, float* stats,
+                           hipStream_t st) {
+  const NormSite& ns = p->norms[s];
+  return launch_layernorm_fwd(x, ldx, n, ns.units, ns.off_gamma >= 0 ? p->d_params + ns.off_gamma : nullptr,
+                              ns.off_beta >= 0 ? p->d_params + ns.off_beta : nullptr, ns.epsilon, y, stats, st);
 }
 }  // namespace ign
 
@@ -257,6 +239,7 @@ struct ign_batch {
   std::vector<float*> ro_buf;                   // per readout tensor: op output buffer (null for states)
   std::vector<int64_t> adj_rows;                // per adjacency: edges in the batch
   std::vector<std::vector<int64_t>> adj_off;    // [adjacency][graph + 1] edge offsets
+  std::vector<float*> d_norm;                   // per LayerNormalization site: its buffer in ign_forward (NormRun::buf)
   float* d_pred = nullptr;
   int64_t n_pred = 0, out_units = 1;
   int64_t edges_per_forward = 0, gru_steps = 0;
@@ -299,10 +282,15 @@ int attention_weights(ign_plan* p, ign_batch* b, const MPP& mp, const MPB& mb, c
 int readout_batch(ign_plan* p, ign_batch* b, const ign_batch_desc* d);
 // ent: entity-state tensors to read (training keeps every version); null = the batch's current states
 // drop: the training forward's Dropout stream and buffers; null = inference (Dropout is identity)
+// norm: the LayerNormalization buffers of the run; null = the batch's own (inference)
 int readout_ops_run(ign_plan* p, ign_batch* b, hipStream_t st, const float* const* ent = nullptr,
-                    const DropRun* drop = nullptr);
+                    const DropRun* drop = nullptr, const NormRun* norm = nullptr);
+// rows x units of LayerNormalization site s in batch b
+int64_t norm_site_floats(const ign_plan* p, const ign_batch* b, int s);
 // ign_plan_add_dropout's routine (also called by ign_plan_create_json's lowering)
 int plan_add_dropout(ign_plan* p, int stack, int before_layer, float rate, uint64_t layer_seed);
+// ign_plan_add_layernorm's routine (likewise)
+int plan_add_layernorm(ign_plan* p, int stack, int before_layer, float epsilon, int center, int scale);
 const float* readout_tensor(const ign_plan* p, const ign_batch* b, int id);
 int64_t space_rows(const ign_plan* p, const ign_batch* b, const RoTensor& t);
 // Batch construction (ign_batch_create, ign_batch_enable_training) copies and clears on a

@@ -105,15 +105,24 @@ struct Drop {   // a Dropout layer of a readout stack (engine.py MPPlan: (before
   int before;
   double rate;
   uint64_t seed;
+  int order = 0;   // its place among the Dropout (rate > 0) and LayerNormalization layers in front of `before`
+};
+
+struct Norm {   // a LayerNormalization layer of a readout stack (engine.py MPPlan's layernorm records)
+  int before, order;
+  double epsilon;
+  bool center, scale;
+  std::string name;
 };
 
 // Feed_forward_model (AUX:869-1003) + MPPlan._dense_layers.  drops: where the stack's Dropout
 // layers go (a readout stack); null for a message-creation network, which takes none.  The
-// default-name counter counts every layer, Dropout included.
+// default-name counter counts every layer, Dropout included.  norms: likewise the stack's
+// LayerNormalization layers.
 std::vector<Layer> dense_layers(const JVal& architecture, const std::string& role, const char* what,
-                                std::vector<Drop>* drops) {
+                                std::vector<Drop>* drops, std::vector<Norm>* norms = nullptr) {
   std::vector<Layer> out;
-  int counter = 0;
+  int counter = 0, in_front = 0;   // in_front: Dropout / LayerNormalization layers since the last Dense
   for (const JVal& l : arr(architecture, std::string(what) + " nn_architecture")) {
     const std::string type = str(need(l, "type_layer", what), std::string(what) + " type_layer");
     if (type == "Dropout") {
@@ -127,12 +136,36 @@ std::vector<Layer> dense_layers(const JVal& architecture, const std::string& rol
       if (!(rate >= 0.0 && rate < 1.0)) invalid("Dropout rate must be in [0, 1), got " + std::to_string(rate));
       const JVal* sd = opt(l, "seed");
       const uint64_t seed = sd && sd->t != JVal::Null ? (uint64_t)(int64_t)number(*sd, "Dropout seed") : 0;
-      if (rate > 0.0) drops->push_back({(int)out.size(), rate, seed});   // rate 0: no layer (TF returns x)
+      if (rate > 0.0) drops->push_back({(int)out.size(), rate, seed, in_front++});   // rate 0: no layer (TF returns x)
+      ++counter;
+      continue;
+    }
+    if (type == "LayerNormalization" && norms) {
+      Norm n{(int)out.size(), in_front++, 1e-3, true, true, ""};
+      for (auto& kv : l.obj) {
+        const std::string& k = kv.first;
+        if (k == "type_layer") continue;
+        if (k == "name") n.name = str(kv.second, "layer name");
+        else if (k == "epsilon") n.epsilon = number(kv.second, "LayerNormalization epsilon");
+        else if (k == "center") n.center = truthy(kv.second);
+        else if (k == "scale") n.scale = truthy(kv.second);
+        else if (k == "axis" && kv.second.t == JVal::Num && kv.second.num == std::floor(kv.second.num)) {
+          if (kv.second.num != -1 && kv.second.num != 1)   // the stacks' tensors are [rows, units]
+            unsupported("LayerNormalization axis " + std::to_string((long long)kv.second.num) +
+                        " is not lowered (the last axis only: -1 or 1)");
+        } else {
+          unsupported("LayerNormalization option '" + k + "' is not lowered");
+        }
+      }
+      if (!(n.epsilon >= 0.0)) invalid("LayerNormalization epsilon must be >= 0, got " + std::to_string(n.epsilon));
+      if (n.name.empty()) n.name = "layer_" + std::to_string(counter) + "_" + type + "_" + role;
+      norms->push_back(n);
       ++counter;
       continue;
     }
     if (type != "Dense")
-      unsupported(std::string(what) + " layer type " + type + " is not lowered (" + (drops ? "Dense and Dropout" : "Dense") + " only)");
+      unsupported(std::string(what) + " layer type " + type + " is not lowered (" +
+                  (drops ? "Dense, Dropout and LayerNormalization" : "Dense") + " only)");
     for (auto& kv : l.obj)
       if (kv.first != "type_layer" && kv.first != "units" && kv.first != "activation" &&
           kv.first != "kernel_regularizer" && kv.first != "name" && kv.first != "use_bias")
@@ -148,8 +181,11 @@ std::vector<Layer> dense_layers(const JVal& architecture, const std::string& rol
     y.d.l2 = kr && truthy(*kr) ? (float)number(*kr, "kernel_regularizer") : 0.f;
     out.push_back(y);
     ++counter;
+    in_front = 0;
   }
   if (drops && !drops->empty() && out.empty()) invalid(std::string(what) + " network has a Dropout but no Dense layer");
+  if (norms && !norms->empty() && out.empty())
+    invalid(std::string(what) + " network has a LayerNormalization but no Dense layer");
   return out;
 }
 
@@ -189,6 +225,7 @@ struct Lowered {
     std::vector<int32_t> inputs;
     std::vector<Layer> layers;
     std::vector<Drop> drops;
+    std::vector<Norm> norms;
   };
   std::vector<RoOp> ro_ops;
   std::vector<int32_t> ro_inputs;
@@ -197,6 +234,7 @@ struct Lowered {
   std::string label;
   std::vector<Layer> dense;
   std::vector<Drop> drops;   // the predict network's
+  std::vector<Norm> norms;
 
   std::vector<std::pair<std::string, std::vector<int64_t>>> param_specs() const {
     std::vector<std::pair<std::string, std::vector<int64_t>>> s;
@@ -222,24 +260,26 @@ struct Lowered {
       s.push_back({"attention/kernel2", {attn_dim, attn_dim}});
       s.push_back({"attention/attn_kernel", {2 * attn_dim, 1}});
     }
-    for (auto& op : ro_ops) {
-      int fan = op.in_width;
-      for (size_t li = 0; li < op.layers.size(); ++li) {
-        const auto& l = op.layers[li];
-        const std::string pre = "readout_model_" + std::to_string(op.counter) + "/" + l.name;
-        s.push_back({pre + "/kernel", {fan, l.d.units}});
-        if (l.d.use_bias) s.push_back({pre + "/bias", {l.d.units}});
+    // a stack's tensors: each LayerNormalization's gamma / beta in front of the Dense layer it precedes
+    auto stack = [&](int counter, int fan, const std::vector<Layer>& layers, const std::vector<Norm>& norms) {
+      const std::string model = "readout_model_" + std::to_string(counter) + "/";
+      for (size_t li = 0; li <= layers.size(); ++li) {
+        for (const Norm& n : norms) {   // (in the architecture's order)
+          if (n.before != (int)li) continue;
+          if (n.scale) s.push_back({model + n.name + "/gamma", {fan}});
+          if (n.center) s.push_back({model + n.name + "/beta", {fan}});
+        }
+        if (li == layers.size()) break;
+        const auto& l = layers[li];
+        s.push_back({model + l.name + "/kernel", {fan, l.d.units}});
+        if (l.d.use_bias) s.push_back({model + l.name + "/bias", {l.d.units}});
         fan = l.d.units;
       }
-    }
+    };
+    for (auto& op : ro_ops) stack(op.counter, op.in_width, op.layers, op.norms);
     int fan = 0;
     for (int i : ro_inputs) fan += ro_widths[i];
-    for (auto& l : dense) {
-      const std::string pre = "readout_model_" + std::to_string(predict_counter) + "/" + l.name;
-      s.push_back({pre + "/kernel", {fan, l.d.units}});
-      if (l.d.use_bias) s.push_back({pre + "/bias", {l.d.units}});
-      fan = l.d.units;
-    }
+    stack(predict_counter, fan, dense, norms);
     return s;
   }
 };
@@ -484,7 +524,8 @@ Lowered lower(const JVal& data, const JVal& dims) {
       d.type = IGN_RO_NEURAL_NETWORK;
       const std::string nn = str(need(op, "nn_name", "readout neural_network"), "nn_name");
       if (!nets.count(nn)) invalid("readout nn_name '" + nn + "' is not defined");
-      d.layers = dense_layers(need(*nets[nn], "nn_architecture", "readout network"), "readout", "readout", &d.drops);
+      d.layers = dense_layers(need(*nets[nn], "nn_architecture", "readout network"), "readout", "readout", &d.drops,
+                              &d.norms);
       for (int i : d.inputs) d.in_width += p.ro_widths[i];
       const JVal* on = opt(op, "output_name");
       add(on ? str(*on, "output_name") : "None", d.layers.back().d.units, first);
@@ -525,7 +566,7 @@ Lowered lower(const JVal& data, const JVal& dims) {
   p.label = str(need(*pred, "label", "predict"), "label");
   for (const JVal& i : arr(need(*pred, "input", "predict"), "input")) p.ro_inputs.push_back(resolve(i));
   const std::string nn = pred->get("nn_name")->str;
-  p.dense = dense_layers(need(*nets[nn], "nn_architecture", "predict network"), "readout", "readout", &p.drops);
+  p.dense = dense_layers(need(*nets[nn], "nn_architecture", "predict network"), "readout", "readout", &p.drops, &p.norms);
   return p;
 }
 
@@ -570,6 +611,28 @@ std::string describe(const Lowered& p) {
   };
   for (size_t k = 0; k < p.ro_ops.size(); ++k) sites((int)k, p.ro_ops[k].drops);
   sites(-1, p.drops);
+  // LayerNormalization layers in the same order, numbered on their own; order = the layer's place
+  // among the Dropout sites and LayerNormalization layers in front of the same Dense layer
+  s += "], \"layernorm\": [";
+  int nsite = 0;
+  auto layers = [&](int stack, int fan, const std::vector<Layer>& dense, const std::vector<Norm>& norms) {
+    std::vector<Norm> d = norms;
+    std::stable_sort(d.begin(), d.end(), [](const Norm& a, const Norm& b) { return a.before < b.before; });
+    for (const Norm& x : d) {
+      char eps[32];
+      snprintf(eps, sizeof eps, "%.9g", (double)(float)x.epsilon);
+      const int units = x.before == 0 ? fan : dense[x.before - 1].d.units;
+      s += (nsite ? ", " : "") + std::string("{\"site\": ") + std::to_string(nsite) + ", \"stack\": " + std::to_string(stack) +
+           ", \"before_layer\": " + std::to_string(x.before) + ", \"order\": " + std::to_string(x.order) +
+           ", \"epsilon\": " + eps + ", \"center\": " + (x.center ? "true" : "false") + ", \"scale\": " +
+           (x.scale ? "true" : "false") + ", \"units\": " + std::to_string(units) + ", \"name\": " + quote(x.name) + "}";
+      ++nsite;
+    }
+  };
+  for (size_t k = 0; k < p.ro_ops.size(); ++k) layers((int)k, p.ro_ops[k].in_width, p.ro_ops[k].layers, p.ro_ops[k].norms);
+  int fan = 0;
+  for (int i : p.ro_inputs) fan += p.ro_widths[i];
+  layers(-1, fan, p.dense, p.norms);
   return s + "]}";
 }
 
@@ -654,22 +717,35 @@ int ign_plan_create_json(const char* model_json, const char* dims_json, int32_t 
   ign_plan* plan = nullptr;
   int rc = ign_plan_create(&d, device, &plan);
   if (rc) return rc;
+  // the Dropout and LayerNormalization layers (ign_plan_add_dropout's and ign_plan_add_layernorm's
+  // routines), each stack's in the architecture's order: the two lists hold them in that order
+  auto add_sites = [&](int stack, const std::vector<Drop>& drops, const std::vector<Norm>& norms) {
+    size_t di = 0, ni = 0;
+    while (!rc && (di < drops.size() || ni < norms.size())) {
+      const bool drop = ni == norms.size() ||
+                        (di < drops.size() && std::make_pair(drops[di].before, drops[di].order) <
+                                                  std::make_pair(norms[ni].before, norms[ni].order));
+      if (drop) {
+        rc = plan_add_dropout(plan, stack, drops[di].before, (float)drops[di].rate, drops[di].seed);
+        ++di;
+      } else {
+        rc = plan_add_layernorm(plan, stack, norms[ni].before, (float)norms[ni].epsilon, norms[ni].center, norms[ni].scale);
+        ++ni;
+      }
+    }
+  };
+  for (size_t k = 0; k < p.ro_ops.size(); ++k) add_sites((int)k, p.ro_ops[k].drops, p.ro_ops[k].norms);
+  add_sites(-1, p.drops, p.norms);
+  if (rc) {
+    ign_plan_destroy(plan);
+    return rc;
+  }
   const auto specs = p.param_specs();
   int32_t nt = 0;
   ign_plan_num_param_tensors(plan, &nt);
   if ((size_t)nt != specs.size()) {
     ign_plan_destroy(plan);
     return fail(IGN_ERR_INVALID, "internal: %zu parameter names for %d tensors", specs.size(), nt);
-  }
-  // the Dropout layers (ign_plan_add_dropout's routine)
-  for (size_t k = 0; k < p.ro_ops.size() && !rc; ++k)
-    for (const Drop& x : p.ro_ops[k].drops)
-      if ((rc = plan_add_dropout(plan, (int)k, x.before, (float)x.rate, x.seed))) break;
-  for (size_t i = 0; i < p.drops.size() && !rc; ++i)
-    rc = plan_add_dropout(plan, -1, p.drops[i].before, (float)p.drops[i].rate, p.drops[i].seed);
-  if (rc) {
-    ign_plan_destroy(plan);
-    return rc;
   }
   plan->describe = describe(p);
   *out = plan;

@@ -4,6 +4,8 @@
 // (layout_packed).  No HIP, no environment: the switches arrive as a PlanSwitches.
 #include "plan_lower.h"
 
+#include <climits>
+
 namespace ign {
 
 namespace {
@@ -278,6 +280,7 @@ int lower_readout(const ign_plan_desc* d, PlanModel* p) {
 // convolution, attention, readout ops, predict.
 void layout_params(PlanModel* p) {
   int64_t off = 0;
+  p->tensors.clear();
   auto put = [&](int kind, int owner, int rows, int cols) {
     const int64_t at = off;
     p->tensors.push_back({kind, owner, at, rows, cols});
@@ -305,9 +308,29 @@ void layout_params(PlanModel* p) {
     p->off_k2 = put(7, -1, F, F);
     p->off_att = put(8, -1, 2 * F, 1);
   }
-  for (size_t k = 0; k < p->ro_ops.size(); ++k)
-    for (size_t l = 0; l < p->ro_ops[k].layers.size(); ++l) put_dense(p->ro_ops[k].layers[l], 11, 12, (int)(k * 64 + l));
-  for (size_t l = 0; l < p->dense.size(); ++l) put_dense(p->dense[l], 3, 4, (int)l);
+  // a stack's LayerNormalization tensors stand where Keras creates them: in front of the Dense
+  // layer they precede (after the last one: at the stack's end), gamma then beta; owner = the site
+  auto put_norms = [&](int stack, int before) {
+    for (size_t s = 0; s < p->norms.size(); ++s) {
+      NormSite& ns = p->norms[s];
+      if (ns.stack != stack || ns.before != before) continue;
+      ns.off_gamma = ns.scale ? put(13, (int)s, 1, ns.units) : -1;
+      ns.off_beta = ns.center ? put(14, (int)s, 1, ns.units) : -1;
+    }
+  };
+  for (size_t k = 0; k < p->ro_ops.size(); ++k) {
+    const size_t L = p->ro_ops[k].layers.size();
+    for (size_t l = 0; l < L; ++l) {
+      put_norms((int)k, (int)l);
+      put_dense(p->ro_ops[k].layers[l], 11, 12, (int)(k * 64 + l));
+    }
+    if (L) put_norms((int)k, (int)L);
+  }
+  for (size_t l = 0; l < p->dense.size(); ++l) {
+    put_norms(-1, (int)l);
+    put_dense(p->dense[l], 3, 4, (int)l);
+  }
+  put_norms(-1, (int)p->dense.size());
   p->n_params = off;
 }
 
@@ -319,6 +342,28 @@ void layout_packed(PlanModel* p) {
   enum { AT_CELL, AT_SLICE, AT_MSG, AT_CONV, AT_ATTN, AT_RO_H16, AT_DENSE, AT_DENSE_WT, AT_RO_OPS };
   std::vector<std::pair<int64_t, PackJob>> jobs;
   int64_t pk = 0;
+  // from clean slots: every pk_* offset below is assigned here or stays unset (the layouts run again
+  // when ign_plan_add_layernorm changes the stacks)
+  p->packs.clear();
+  for (CellP& c : p->cells) {   // (a fresh struct carries every slot's default)
+    CellP z{c.din, c.H, c.off_k, c.off_rk, c.off_b, -1, -1, -1};
+    z.used = c.used;
+    c = z;
+  }
+  auto unpacked = [](DenseP& d) {
+    DenseP z{d.in, d.out, d.act, d.use_bias, d.l2};
+    z.off_w = d.off_w;
+    z.off_b = d.off_b;
+    d = z;
+  };
+  for (auto& d : p->dense) unpacked(d);
+  for (auto& op : p->ro_ops)
+    for (auto& d : op.layers) unpacked(d);
+  for (auto& mp : p->mps) {
+    mp.pk_slice.clear();
+    for (auto& nn : mp.nn)
+      for (auto& d : nn.layers) unpacked(d);
+  }
   // reserves `floats` and records the launch that fills them; (at, idx, sub) orders the launches
   auto slot = [&](int at, size_t idx, int sub, int kind, int64_t floats, int64_t s0, int64_t s1, int64_t s2, int a,
                   int b = 0, int c = 0) {
@@ -419,6 +464,34 @@ void layout_packed(PlanModel* p) {
 }
 
 }  // namespace
+
+int add_layernorm(PlanModel* p, int stack, int before_layer, float epsilon, int center, int scale) {
+  const std::vector<DenseP>* layers = stack_layers(p, stack);
+  if (!layers)
+    return fail(IGN_ERR_INVALID, "ign_plan_add_layernorm: stack %d is neither -1 (predict) nor a readout "
+                "neural_network operation", stack);
+  const int L = (int)layers->size();
+  if (before_layer < 0 || before_layer > L)
+    return fail(IGN_ERR_INVALID, "ign_plan_add_layernorm: before_layer %d outside 0..%d", before_layer, L);
+  if (!(epsilon >= 0.f))   // Keras raises ValueError
+    return fail(IGN_ERR_INVALID, "LayerNormalization epsilon must be >= 0, got %g", (double)epsilon);
+  NormSite n;
+  n.stack = stack;
+  n.before = before_layer;
+  n.order = sites_in_front(p, stack, before_layer);
+  n.epsilon = epsilon;
+  n.center = center != 0;
+  n.scale = scale != 0;
+  n.units = before_layer < L ? (*layers)[before_layer].in : layers->back().out;
+  auto key = [](const NormSite& s) { return std::make_pair(s.stack < 0 ? INT_MAX : s.stack, s.before); };
+  size_t at = 0;
+  while (at < p->norms.size() && key(p->norms[at]) <= key(n)) ++at;
+  p->norms.insert(p->norms.begin() + at, n);
+  if (stack == -1) p->fused_readout = false;   // the fused 256-256-1 kernel has no place for the layer
+  layout_params(p);   // both layouts again
+  layout_packed(p);
+  return IGN_OK;
+}
 
 int lower_plan(const ign_plan_desc* d, const PlanSwitches& sw, PlanModel* m) {
   static_cast<PlanSwitches&>(*m) = sw;

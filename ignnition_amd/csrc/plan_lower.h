@@ -38,6 +38,22 @@ struct DropSite {
   int before = 0;        // Dense layer it precedes; the stack's layer count = after the last one
   float rate = 0.f, scale = 1.f;
   uint64_t seed = 0;     // the layer's own seed option, xor-mixed into the batch's stream seed
+  int order = 0;         // position among the Dropout and LayerNormalization layers in front of `before`
+};
+
+// A LayerNormalization layer of a readout Dense stack (ign_plan_add_layernorm): live in inference and
+// in training.  Kept like the Dropout sites (readout ops in order, then predict; by position, then
+// by insertion), numbered on their own: a Dropout site's number, its Philox counter word, counts
+// Dropout layers only.  `order` places the two kinds of layer in front of one Dense layer in the
+// order the architecture lists them.
+struct NormSite {
+  int stack = -1;        // readout-op index, or -1 for predict
+  int before = 0;        // Dense layer it precedes; the stack's layer count = after the last one
+  int order = 0;
+  float epsilon = 1e-3f;
+  int64_t off_gamma = -1, off_beta = -1;   // [units] each; -1: scale / center false, no tensor
+  bool center = true, scale = true;
+  int units = 0;         // the width it normalises: the input width of `before`, or the stack's output width
 };
 
 // The plan-level switches.  engine.cpp's switches_from_env fills them from the IGN_* environment
@@ -135,7 +151,26 @@ struct PlanModel : PlanSwitches {
   bool fused_readout = false;
   int ro_width = 0;
   std::vector<DropSite> drops;    // Dropout sites of the readout stacks, in site order (rate > 0 only)
+  std::vector<NormSite> norms;    // LayerNormalization layers of the readout stacks, in the same order
 };
+
+// the Dense layers of `stack` (-1 predict, k readout neural_network operation k), or null
+inline const std::vector<DenseP>* stack_layers(const PlanModel* p, int stack) {
+  if (stack == -1) return &p->dense;
+  if (stack < 0 || stack >= (int)p->ro_ops.size() || p->ro_ops[stack].type != IGN_RO_NEURAL_NETWORK) return nullptr;
+  return &p->ro_ops[stack].layers;
+}
+// the Dropout and LayerNormalization layers already in front of Dense layer `before` of `stack`
+inline int sites_in_front(const PlanModel* p, int stack, int before) {
+  int n = 0;
+  for (auto& d : p->drops) n += d.stack == stack && d.before == before;
+  for (auto& d : p->norms) n += d.stack == stack && d.before == before;
+  return n;
+}
+// ign_plan_add_layernorm on the model: the site, its gamma / beta tensors (kinds 13 / 14, in front of
+// the Dense layer it precedes) and both layouts again; predict's stack leaves the fused readout.
+// Only before the parameters exist on a device (the caller checks).
+int add_layernorm(PlanModel* p, int stack, int before_layer, float epsilon, int center, int scale);
 
 // d + sw -> *m (a fresh PlanModel); IGN_OK or the refusal's code, its text in ign_last_error
 int lower_plan(const ign_plan_desc* d, const PlanSwitches& sw, PlanModel* m);

@@ -49,6 +49,12 @@ static std::vector<int64_t> space_offsets(const ign_batch* b, const RoTensor& t)
   return off;
 }
 
+int64_t norm_site_floats(const ign_plan* p, const ign_batch* b, int s) {
+  const NormSite& ns = p->norms[s];
+  const int first = ns.stack < 0 ? p->ro_in[0] : p->ro_ops[ns.stack].in[0];
+  return space_rows(p, b, p->ro_t[first]) * ns.units;
+}
+
 const float* readout_tensor(const ign_plan* p, const ign_batch* b, int id) {
   const int NE = (int)p->ents.size();
   if (id < NE) return b->d_state[b->cur[id]][id];
@@ -137,8 +143,11 @@ int readout_batch(ign_plan* p, ign_batch* b, const ign_batch_desc* d) {
   return IGN_OK;
 }
 
-int readout_ops_run(ign_plan* p, ign_batch* b, hipStream_t st, const float* const* ent, const DropRun* drop) {
+int readout_ops_run(ign_plan* p, ign_batch* b, hipStream_t st, const float* const* ent, const DropRun* drop,
+                    const NormRun* norm) {
   const int NE = (int)p->ents.size();
+  const NormRun own{b->d_norm.data(), nullptr};   // inference: the batch's buffers, no statistics kept
+  if (!norm) norm = &own;
   auto readout_tensor = [&](const ign_plan* pp, const ign_batch* bb, int id) -> const float* {
     return ent && id < NE ? ent[id] : ign::readout_tensor(pp, bb, id);
   };
@@ -159,7 +168,7 @@ int readout_ops_run(ign_plan* p, ign_batch* b, hipStream_t st, const float* cons
           x = bo.cat;
         }
         const DenseStackRun r{op.layers.data(), (int)op.layers.size(), n, x, op.in_width, bo.tmp.data(), bo.out[0],
-                              drop, (int)k};
+                              drop, (int)k, norm};
         if (int rc = dense_stack_forward(p, r, st)) return rc;
         break;
       }

@@ -86,6 +86,10 @@ struct TrainState {
   // wrote it, for its activation derivative), or, after a stack's last layer, that layer's output y
   std::vector<float*> dbuf;
   DropRun drop;                           // the forward's mask stream: its backward regenerates the masks
+  // LayerNormalization layers of the readout stacks, per site: its output [rows][units] (after a
+  // stack's last layer: its input), apart from the batch's inference buffers, and its rows' (mean, rstd)
+  std::vector<float*> nbuf, nstats;
+  NormRun norm;
   bool forward_done = false;
   // stepped forward / backward (ign_forward_train_begin .. _end, ign_backward_begin .. _end): the
   // edge-cut driver exchanges halo rows between the steps
@@ -322,7 +326,8 @@ int ro_stack_backward(ign_plan* p, TrainState* t, DenseStackRun r, const float* 
 
 // predict's Dense stack (p->dense) on input x, for the training forward and its backward
 DenseStackRun predict_stack(const ign_plan* p, const ign_batch* b, TrainState* t, const float* x) {
-  return {p->dense.data(), (int)p->dense.size(), b->n_pred, x, p->ro_width, t->act.data(), b->d_pred, &t->drop, -1};
+  return {p->dense.data(), (int)p->dense.size(), b->n_pred, x, p->ro_width, t->act.data(), b->d_pred, &t->drop, -1,
+          &t->norm};
 }
 
 // Backward of the readout operations before predict (GM:605-655), last first: each turns the
@@ -339,7 +344,7 @@ int readout_ops_backward(ign_plan* p, ign_batch* b, TrainState* t, hipStream_t s
       case IGN_RO_NEURAL_NETWORK: {   // Readout_nn (AUX:1188-1211): Dense stack on concat(inputs)
         const float* x = op.in.size() > 1 ? bo.cat : ro_tensor(b, t, op.in[0]);
         const DenseStackRun r{op.layers.data(), (int)op.layers.size(), n, x, op.in_width, bo.tmp.data(), bo.out[0],
-                              &t->drop, k};
+                              &t->drop, k, &t->norm};
         if ((rc = ro_stack_backward(p, t, r, t->dT[op.out], t->rz, op.in, t->rcat, st))) return rc;
         break;
       }
@@ -527,6 +532,7 @@ struct TrainScratch {
   int64_t amsg = 0, arows = 0;                   // attention
   int64_t dz = 0, rz = 0, rcat = 0, ties = 0;    // readout
   std::vector<int64_t> drop;                     // per Dropout site: rows x units
+  std::vector<int64_t> norm, norm_rows;          // per LayerNormalization site: rows x units, rows
 };
 TrainScratch train_scratch(const ign_plan* p, const ign_batch* b) {
   TrainScratch z;
@@ -607,6 +613,12 @@ TrainScratch train_scratch(const ign_plan* p, const ign_batch* b) {
     const int64_t rows = d.stack < 0 ? P : space_rows(p, b, p->ro_t[p->ro_ops[d.stack].in[0]]);
     z.drop.push_back(rows * (d.before < (int)layers.size() ? layers[d.before].in : layers.back().out));
   }
+  for (size_t s = 0; s < p->norms.size(); ++s) {
+    const int64_t fl = norm_site_floats(p, b, (int)s), rows = fl / p->norms[s].units;
+    z.norm.push_back(fl);
+    z.norm_rows.push_back(rows);
+    z.part = std::max(z.part, layernorm_partial_floats(rows, p->norms[s].units));
+  }
   return z;
 }
 
@@ -665,6 +677,12 @@ int alloc_readout(const ign_plan* p, const ign_batch* b, TrainState* t, const Tr
     float* f = nullptr;
     if ((rc = talloc(t, &f, n))) return rc;
     t->dbuf.push_back(f);
+  }
+  for (size_t s = 0; s < z.norm.size(); ++s) {
+    float *f = nullptr, *m = nullptr;
+    if ((rc = talloc(t, &f, z.norm[s])) || (rc = talloc(t, &m, 2 * z.norm_rows[s]))) return rc;
+    t->nbuf.push_back(f);
+    t->nstats.push_back(m);
   }
   return IGN_OK;
 }
@@ -853,7 +871,8 @@ int ign_forward_train_end(ign_plan* p, ign_batch* b, float* pred_out) {
   for (int e = 0; e < E; ++e) ent[e] = t->ver[e][t->cur[e]];
   // this forward's Dropout masks (ign_batch_set_dropout), kept for the backward that regenerates them
   t->drop = DropRun{b->drop_seed, b->drop_step, t->dbuf.data()};
-  if (!p->ro_ops.empty() && (rc = readout_ops_run(p, b, st, ent.data(), &t->drop))) return rc;
+  t->norm = NormRun{t->nbuf.data(), t->nstats.data()};
+  if (!p->ro_ops.empty() && (rc = readout_ops_run(p, b, st, ent.data(), &t->drop, &t->norm))) return rc;
   const int64_t P = b->n_pred;
   const float* x = ro_tensor(b, t, p->ro_in[0]);
   if (p->ro_in.size() > 1) {

@@ -110,6 +110,10 @@ class MPPlan:
     predict_counter: int = 0                           # readout_model_<index of predict in the readout list>
     dense: list = field(default_factory=list)          # [(name, units, act, use_bias, l2)]
     dropout: list = field(default_factory=list)        # predict's Dropout layers: [(before_layer, rate, seed)]
+    layernorm: list = field(default_factory=list)      # predict's LayerNormalization layers:
+                                                       # [(before_layer, order, epsilon, center, scale, name)]
+    sites: list = field(default_factory=list)          # predict's layers of both kinds in the architecture's order:
+                                                       # the ign_plan_add_* calls without their stack (stack_sites)
     iterations: int = 0
     readout_label: str = ""
     convolution_dim: int = 0                           # F of convolution/kernel [F, F] (0: none)
@@ -186,10 +190,16 @@ class MPPlan:
 
     @staticmethod
     def _dense_layers(arch, what):
-        """(Dense layers, Dropout records) of a readout stack.  A Dropout layer (tf.nn.dropout in
-        training, the identity otherwise) is recorded as (before_layer, rate, seed): the Dense layer
-        it precedes, len(layers) after the last one.  rate 0 is no layer, as TF returns x."""
-        out, drops = [], []
+        """(Dense layers, Dropout records, LayerNormalization records) of a readout stack.  A Dropout
+        layer (tf.nn.dropout in training, the identity otherwise) is recorded as (before_layer, rate,
+        seed): the Dense layer it precedes, len(layers) after the last one.  rate 0 is no layer, as TF
+        returns x.  A LayerNormalization is (before_layer, order, epsilon, center, scale, name);
+        order = its place among the Dropout records and LayerNormalization layers in front of that
+        Dense layer, in the architecture's order.  The fourth list holds both kinds in that order,
+        as the calls that add them: ("dropout", before_layer, rate, seed) or ("layernorm", before_layer,
+        epsilon, center, scale)."""
+        out, drops, norms, sites = [], [], [], []
+        in_front = 0
         for l in arch.layers:
             if l.type == "Dropout":
                 prm = dict(l.parameters)
@@ -202,9 +212,31 @@ class MPPlan:
                     raise ValueError("Dropout rate must be in [0, 1), got %r" % rate)
                 if rate > 0.0:
                     drops.append((len(out), rate, int(prm.get("seed") or 0) & 0xFFFFFFFFFFFFFFFF))
+                    sites.append(("dropout",) + drops[-1])
+                    in_front += 1
+                continue
+            if l.type == "LayerNormalization":
+                prm = dict(l.parameters)
+                for k, v in prm.items():
+                    if k in ("name", "epsilon", "center", "scale"):
+                        continue
+                    if k == "axis" and isinstance(v, (int, float)) and not isinstance(v, bool) and v == int(v):
+                        if v not in (-1, 1):   # the stacks' tensors are [rows, units]
+                            raise UnsupportedModel("LayerNormalization axis %d is not lowered (the last axis only: "
+                                                   "-1 or 1)" % v)
+                        continue
+                    raise UnsupportedModel("LayerNormalization option '%s' is not lowered" % k)
+                eps = float(prm.get("epsilon", 1e-3))
+                if not eps >= 0.0:   # Keras raises ValueError
+                    raise ValueError("LayerNormalization epsilon must be >= 0, got %r" % eps)
+                norms.append((len(out), in_front, eps, bool(prm.get("center", True)), bool(prm.get("scale", True)),
+                              prm.get("name")))
+                sites.append(("layernorm", len(out), eps, int(norms[-1][3]), int(norms[-1][4])))
+                in_front += 1
                 continue
             if l.type != "Dense":
-                raise UnsupportedModel("%s layer type %s is not lowered (Dense and Dropout only)" % (what, l.type))
+                raise UnsupportedModel("%s layer type %s is not lowered (Dense, Dropout and LayerNormalization only)"
+                                       % (what, l.type))
             prm = dict(l.parameters)
             act = prm.get("activation", None)
             if act not in _lib.ACT:
@@ -214,9 +246,12 @@ class MPPlan:
                 raise UnsupportedModel("Dense options %s are not lowered" % sorted(set(prm) - known))
             out.append((prm.get("name"), int(prm["units"]), _lib.ACT[act], int(bool(prm.get("use_bias", True))),
                         float(prm.get("kernel_regularizer", 0.0) or 0.0)))
+            in_front = 0
         if drops and not out:
             raise ValueError("%s network has a Dropout but no Dense layer" % what)
-        return out, drops
+        if norms and not out:
+            raise ValueError("%s network has a LayerNormalization but no Dense layer" % what)
+        return out, drops, norms, sites
 
     def _lower_readout(self, mi):
         """The readout list (GM:605-655) up to the first predict, which returns (GM:629); names
@@ -246,7 +281,7 @@ class MPPlan:
             first = self.ro_spaces[ids[0]]
             d = {"type": op.type, "inputs": ids, "mode": 0, "adj": -1, "layers": [], "counter": counter}
             if op.type == "neural_network":
-                d["layers"], d["dropout"] = self._dense_layers(op.architecture, "readout")
+                d["layers"], d["dropout"], d["layernorm"], d["sites"] = self._dense_layers(op.architecture, "readout")
                 d["in_width"] = sum(self.ro_widths[i] for i in ids)
                 add(op.output_name, d["layers"][-1][1], first)
             elif op.type == "pooling":
@@ -278,7 +313,7 @@ class MPPlan:
         self.predict_counter, op = pred
         self.readout_label = op.label
         self.readout_inputs = [resolve(n) for n in op.input]
-        self.dense, self.dropout = self._dense_layers(op.architecture, "readout")
+        self.dense, self.dropout, self.layernorm, self.sites = self._dense_layers(op.architecture, "readout")
 
     @property
     def predict_space(self):
@@ -290,6 +325,31 @@ class MPPlan:
         recs = [(k, d) for k, op in enumerate(self.readout_ops) for d in sorted(op.get("dropout", []), key=lambda d: d[0])]
         recs += [(-1, d) for d in sorted(self.dropout, key=lambda d: d[0])]
         return [(site, stack) + tuple(d) for site, (stack, d) in enumerate(recs)]
+
+    def _stacks(self):
+        """[(stack, input width, Dense layers, Dropout records, LayerNormalization records)]: the readout
+        neural_network operations in order, then predict (stack -1)."""
+        out = [(k, op.get("in_width", 0), op["layers"], op.get("dropout", []), op.get("layernorm", []))
+               for k, op in enumerate(self.readout_ops) if op["type"] == "neural_network"]
+        return out + [(-1, sum(self.ro_widths[i] for i in self.readout_inputs), self.dense, self.dropout, self.layernorm)]
+
+    def layernorm_sites(self):
+        """[(site, stack, before_layer, order, epsilon, center, scale, units, name)] in the engine's order
+        (ign_plan_add_layernorm): stacks as dropout_sites, by position within a stack.  units = the
+        width it normalises: the input width of the Dense layer it precedes, or the stack's output width."""
+        recs = []
+        for stack, fan, layers, _, norms in self._stacks():
+            for before, order, eps, center, scale, name in sorted(norms, key=lambda n: n[0]):
+                units = layers[before - 1][1] if before else fan
+                recs.append((len(recs), stack, before, order, eps, center, scale, units, name))
+        return recs
+
+    def stack_sites(self):
+        """The ign_plan_add_dropout / ign_plan_add_layernorm calls that build the plan's layers, each
+        stack's in the architecture's order: [("dropout", stack, before, rate, seed) |
+        ("layernorm", stack, before, epsilon, center, scale)]."""
+        calls = [(c[0], k) + c[1:] for k, op in enumerate(self.readout_ops) for c in op.get("sites", [])]
+        return calls + [(c[0], -1) + c[1:] for c in self.sites]
 
     # ------------------------------------------------------------------ C structures
     def to_desc(self):
@@ -352,26 +412,31 @@ class MPPlan:
         if self.attention_dim:
             F = self.attention_dim
             specs += [("attention/kernel1", (F, F)), ("attention/kernel2", (F, F)), ("attention/attn_kernel", (2 * F, 1))]
-        for op in self.readout_ops:
-            fan_in = op.get("in_width", 0)
-            for li, (name, units, _, use_bias, _) in enumerate(op["layers"]):
-                pre = "readout_model_%d/%s" % (op["counter"], name or ("layer_%d" % li))
+        def stack(counter, fan_in, layers, norms):
+            # a LayerNormalization's gamma / beta stand in front of the Dense layer it precedes
+            for li in range(len(layers) + 1):
+                for before, _, _, center, scale, name in norms:
+                    if before == li:
+                        pre = "readout_model_%d/%s" % (counter, name)
+                        specs.extend([(pre + "/gamma", (fan_in,))] * scale + [(pre + "/beta", (fan_in,))] * center)
+                if li == len(layers):
+                    break
+                name, units, _, use_bias, _ = layers[li]
+                pre = "readout_model_%d/%s" % (counter, name or ("layer_%d" % li))
                 specs.append((pre + "/kernel", (fan_in, units)))
                 if use_bias:
                     specs.append((pre + "/bias", (units,)))
                 fan_in = units
-        fan_in = sum(self.ro_widths[i] for i in self.readout_inputs)
-        for li, (name, units, _, use_bias, _) in enumerate(self.dense):
-            pre = "readout_model_%d/%s" % (self.predict_counter, name or ("layer_%d" % li))
-            specs.append((pre + "/kernel", (fan_in, units)))
-            if use_bias:
-                specs.append((pre + "/bias", (units,)))
-            fan_in = units
+
+        for op in self.readout_ops:
+            stack(op["counter"], op.get("in_width", 0), op["layers"], op.get("layernorm", []))
+        stack(self.predict_counter, sum(self.ro_widths[i] for i in self.readout_inputs), self.dense, self.layernorm)
         return specs
 
     def init_params(self, seed: int = 0, bias_scale: float = 0.0) -> dict:
         """Keras default initialisers: glorot_uniform kernels, orthogonal recurrent kernels, zero
-        biases (``bias_scale`` > 0 draws biases uniformly instead, for tests)."""
+        biases, LayerNormalization gamma ones and beta zeros (``bias_scale`` > 0 draws biases and
+        beta uniformly instead, and gamma around one, for tests)."""
         rng = np.random.default_rng(seed)
         out = {}
         for name, shape in self.param_specs():
@@ -383,6 +448,9 @@ class MPPlan:
             elif name.endswith("kernel") or name.endswith("kernel1") or name.endswith("kernel2"):
                 lim = np.sqrt(6.0 / (shape[0] + shape[1]))
                 out[name] = rng.uniform(-lim, lim, shape).astype(np.float32)
+            elif name.endswith("/gamma"):
+                out[name] = ((1.0 + rng.uniform(-bias_scale, bias_scale, shape)).astype(np.float32) if bias_scale
+                             else np.ones(shape, np.float32))
             else:
                 out[name] = (rng.uniform(-bias_scale, bias_scale, shape).astype(np.float32) if bias_scale
                              else np.zeros(shape, np.float32))
@@ -399,8 +467,8 @@ class Engine:
         h = C.c_void_p()
         check(lib.ign_plan_create(C.byref(desc), device, C.byref(h)))
         self.handle = h
-        for _, stack, before, rate, seed in plan.dropout_sites():   # ign_dense_desc has no room for them
-            check(lib.ign_plan_add_dropout(h, stack, before, rate, seed))
+        for kind, *args in plan.stack_sites():   # ign_dense_desc has no room for them
+            check((lib.ign_plan_add_dropout if kind == "dropout" else lib.ign_plan_add_layernorm)(h, *args))
         self.params_version = 0   # bumped by every parameter update (SplitBatch re-syncs its replicas)
         self._replicas = []
         _LIVE_ENGINES.add(self)

@@ -135,6 +135,8 @@ def debug(model_description, out_dir: str = "../debug_model/"):
         "readout_inputs": plan.readout_inputs,
         "dense": plan.dense,
         "dropout_sites": [dict(zip(("site", "stack", "before_layer", "rate", "seed"), s)) for s in plan.dropout_sites()],
+        "layernorm_sites": [dict(zip(("site", "stack", "before_layer", "order", "epsilon", "center", "scale", "units",
+                                      "name"), s)) for s in plan.layernorm_sites()],
         "parameters": [[n, list(s)] for n, s in plan.param_specs()],
         "created": str(datetime.datetime.now()),
     }

@@ -238,9 +238,12 @@ int  ign_plan_num_param_tensors(const ign_plan* plan, int32_t* n);
  *           5 convolution kernel [F,F], 6 attention kernel1 [F,F], 7 attention kernel2 [F,F],
  *           8 attention attn_kernel [2F,1] (one set per plan, GM:288-300; owner -1);
  *           9 message-network Dense kernel [in,out], 10 its bias [1,out] (owner = mp * 4 + source);
- *           11 readout neural_network op Dense kernel [in,out], 12 its bias [1,out] (owner = op * 64 + layer).
+ *           11 readout neural_network op Dense kernel [in,out], 12 its bias [1,out] (owner = op * 64 + layer);
+ *           13 LayerNormalization gamma [1,units], 14 its beta [1,units] (ign_plan_add_layernorm;
+ *           owner = the layer's index among the plan's LayerNormalization layers).
  * Order: cells, message networks (MP order, source order, layer order), convolution, attention,
- * readout neural_network ops (op order, layer order), predict Dense layers. */
+ * readout neural_network ops (op order, layer order), predict Dense layers; a LayerNormalization's
+ * tensors in front of the Dense layer it precedes. */
 int  ign_plan_param_tensor(const ign_plan* plan, int32_t i, int32_t* kind, int32_t* owner,
                            int64_t* offset, int32_t* rows, int32_t* cols);
 int  ign_plan_set_params(ign_plan* plan, const float* params, int32_t on_device);
@@ -374,6 +377,23 @@ int  ign_batch_train_buffers(const ign_batch* batch, int32_t entity, float** sta
  * predict, by position within a stack.  ign_plan_create_json adds the sites of its description
  * itself.  noise_shape and Dropout in a message-creation network are IGN_ERR_UNSUPPORTED. */
 int  ign_plan_add_dropout(ign_plan* plan, int32_t stack, int32_t before_layer, float rate, uint64_t layer_seed);
+/* ---- LayerNormalization layers of the readout's Dense stacks (ABI 13 addition) ------------------
+ * Keras LayerNormalization over the last axis of the stack's [rows, units] tensor at that position,
+ * per row: mean = sum(x) / units, var = sum((x - mean)^2) / units (biased, over the centred values),
+ * y = (x - mean) * (1 / sqrt(var + epsilon)) * gamma + beta.  It keeps no moving statistics:
+ * ign_forward and ign_forward_train compute the same.  Added like a Dropout layer, after
+ * ign_plan_create and before the plan's parameters are set or its first batch is created (else
+ * IGN_ERR_INVALID): stack and before_layer as above; layers of both kinds added at one position
+ * apply in the order they were added.  epsilon < 0 is IGN_ERR_INVALID.  scale != 0 adds a gamma
+ * tensor [units] (kind 13), center != 0 a beta tensor [units] (kind 14) to the parameter layout, in
+ * front of the Dense layer's tensors (after the last layer: at the stack's end); their owner is the
+ * layer's index among the plan's LayerNormalization layers (readout operations in order, then
+ * predict, by position).  The call lays the parameters out again: read ign_plan_num_params and
+ * ign_plan_param_tensor after the last one.  A predict stack that holds one does not take the fused
+ * 256-256-1 readout kernel.  ign_plan_create_json adds the layers of its description itself; in a
+ * message-creation network the layer is IGN_ERR_UNSUPPORTED. */
+int  ign_plan_add_layernorm(ign_plan* plan, int32_t stack, int32_t before_layer, float epsilon, int32_t center,
+                            int32_t scale);
 /* The mask stream of the batch's next ign_forward_train (and the backward that follows it): site s
  * draws the mask ign_dropout_keep(seed ^ layer_seed(s), s, step, rows, units, rate(s)).  A batch
  * on which this was never called uses (0, 0): the same mask every step.  A trainer passes its seed
