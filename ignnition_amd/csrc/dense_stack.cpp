@@ -12,23 +12,34 @@ int add_l2_grad(const ign_plan* p, const DenseP& d, float* grads, float scale, h
 
 namespace {
 
-// the Dropout and LayerNormalization layers of run r in front of layer `before`, with their buffers
-struct Site {
-  bool norm;
-  int idx;
-  float* buf;
-};
-void sites_at(const ign_plan* p, const DenseStackRun& r, int before, std::vector<StackSite>* tmp, std::vector<Site>* out) {
-  out->clear();
-  if ((!r.drop || p->drops.empty()) && (!r.norm || p->norms.empty())) return;
-  stack_sites(p, r.stack, before, r.drop != nullptr, r.norm != nullptr, tmp);
-  for (const StackSite& s : *tmp) out->push_back({s.norm, s.idx, s.norm ? r.norm->buf[s.idx] : r.drop->buf[s.idx]});
+// Run r's Dropout and LayerNormalization layers are the entries of r.seq it takes: a Dropout only
+// with a mask stream (r.drop), a LayerNormalization only with buffers (r.norm).  A group of them
+// stands between two Dense entries (or after the last); the walks step through a group with these.
+bool taken(const DenseStackRun& r, const StackLayer& e) {
+  return e.kind == SL_DROPOUT ? r.drop != nullptr : e.kind == SL_LAYERNORM && r.norm != nullptr;
+}
+// the first taken entry at or after i, short of the next Dense entry; -1: none
+int site_from(const DenseStackRun& r, int i) {
+  for (const int n = r.seq ? (int)r.seq->size() : 0; i < n && (*r.seq)[i].kind != SL_DENSE; ++i)
+    if (taken(r, (*r.seq)[i])) return i;
+  return -1;
+}
+// the last taken entry before i, short of the Dense entry below; -1: none
+int site_before(const DenseStackRun& r, int i) {
+  while (r.seq && i > 0 && (*r.seq)[--i].kind != SL_DENSE)
+    if (taken(r, (*r.seq)[i])) return i;
+  return -1;
+}
+// entry i's buffer (DropRun::buf, NormRun::buf)
+float* site_buf(const DenseStackRun& r, int i) {
+  const StackLayer& e = (*r.seq)[i];
+  return e.kind == SL_LAYERNORM ? r.norm->buf[e.idx] : r.drop->buf[e.idx];
 }
 
 // one layer forward: n rows of `units` from x (ldx apart) into y (contiguous)
-int site_forward(const ign_plan* p, const DenseStackRun& r, const Site& s, const float* x, int ldx, float* y, int units,
+int site_forward(const ign_plan* p, const DenseStackRun& r, const StackLayer& s, const float* x, int ldx, float* y, int units,
                  hipStream_t st) {
-  if (s.norm) {
+  if (s.kind == SL_LAYERNORM) {
     HIP_TRY(norm_fwd(p, s.idx, x, ldx, r.n, y, r.norm->stats ? r.norm->stats[s.idx] : nullptr, st));
     return IGN_OK;
   }
@@ -40,9 +51,9 @@ int site_forward(const ign_plan* p, const DenseStackRun& r, const Site& s, const
 
 // and back: g = d(its output) -> gx = d(its input) (gx may be g; acc: added to gx, LayerNormalization
 // only); x = the layer's input rows.  A LayerNormalization adds its gamma / beta gradients to grads.
-int site_backward(const ign_plan* p, const DenseStackRun& r, const Site& s, const float* x, const float* g, float* gx,
+int site_backward(const ign_plan* p, const DenseStackRun& r, const StackLayer& s, const float* x, const float* g, float* gx,
                   int units, int acc, hipStream_t st) {
-  if (s.norm) {
+  if (s.kind == SL_LAYERNORM) {
     const NormSite& ns = p->norms[s.idx];
     const float* stats = r.norm->stats[s.idx];
     HIP_TRY(launch_layernorm_bwd_params(g, x, stats, r.n, units, r.part, ns.off_gamma >= 0 ? r.grads + ns.off_gamma : nullptr,
@@ -61,19 +72,19 @@ int site_backward(const ign_plan* p, const DenseStackRun& r, const Site& s, cons
 int dense_stack_forward(const ign_plan* p, const DenseStackRun& r, hipStream_t st) {
   const float* in = r.x;
   int stride = r.ldx, rc;
-  std::vector<StackSite> tmp;
-  std::vector<Site> sites, tail;
-  sites_at(p, r, r.L, &tmp, &tail);   // the layers after the last Dense layer turn its output into y
+  int at = 0;   // into r.seq: where the entries in front of layer l begin
   for (int l = 0; l < r.L; ++l) {
     const DenseP& d = r.layers[l];
     // in front of a layer each one writes its own buffer, never the tensor another operation reads
-    sites_at(p, r, l, &tmp, &sites);
-    for (const Site& s : sites) {
-      if ((rc = site_forward(p, r, s, in, stride, s.buf, d.in, st))) return rc;
-      in = s.buf;
+    for (int s = site_from(r, at); s >= 0; s = site_from(r, s + 1)) {
+      if ((rc = site_forward(p, r, (*r.seq)[s], in, stride, site_buf(r, s), d.in, st))) return rc;
+      in = site_buf(r, s);
       stride = d.in;
     }
-    float* o = l + 1 < r.L ? r.hid[l] : !tail.empty() ? tail[0].buf : r.y;
+    while (r.seq && (*r.seq)[at++].kind != SL_DENSE) {}   // past this layer's own entry
+    // the layers after the last Dense layer turn its output into y: it writes the first one's buffer
+    const int tail = l + 1 < r.L ? -1 : site_from(r, at);
+    float* o = l + 1 < r.L ? r.hid[l] : tail >= 0 ? site_buf(r, tail) : r.y;
     const float* bias = d.use_bias ? p->d_params + d.off_b : nullptr;
     if (p->train_dense_bf && p->train_dense_h16 && d.pk_hn >= 0 && stride % 4 == 0)   // split-fp16 (x3)
       HIP_TRY(launch_dense_h16(in, r.n, d.in, stride, p->d_packed + d.pk_hn, bias, d.out, d.act, o, st));
@@ -85,10 +96,11 @@ int dense_stack_forward(const ign_plan* p, const DenseStackRun& r, hipStream_t s
     in = o;
     stride = d.out;
   }
-  // the last Dense layer wrote the first one's buffer; each reads its own and writes the next, the last y
-  for (size_t i = 0; i < tail.size(); ++i)
-    if ((rc = site_forward(p, r, tail[i], tail[i].buf, stride, i + 1 < tail.size() ? tail[i + 1].buf : r.y, stride, st)))
-      return rc;
+  // ... each of them reads its own and writes the next one's, the last y
+  for (int s = site_from(r, at), nx; s >= 0; s = nx) {
+    nx = site_from(r, s + 1);
+    if ((rc = site_forward(p, r, (*r.seq)[s], site_buf(r, s), stride, nx >= 0 ? site_buf(r, nx) : r.y, stride, st))) return rc;
+  }
   return IGN_OK;
 }
 
@@ -101,17 +113,14 @@ int dense_stack_backward(const ign_plan* p, const DenseStackRun& r, hipStream_t 
   // of layer l sits between hid[l - 1] = y (the layer below's activation derivative reads it) and
   // its own buffer z (layer l's input: its weight gradient reads it); the fusions below that form a
   // layer's gradient rows from the layer above's decline across one
-  std::vector<StackSite> tmp;
-  std::vector<Site> sites;
-  sites_at(p, r, L, &tmp, &sites);
+  int at = r.seq ? (int)r.seq->size() : 0;   // into r.seq, walked down: where the entries in front of layer l end
   const DenseP& top = r.layers[L - 1];
   const float *dy = r.dy, *y = r.y;
-  if (!sites.empty()) {   // after the last layer: d(y behind them) -> d(y), y in the first one's buffer
-    for (int i = (int)sites.size() - 1; i >= 0; --i) {
-      if ((rc = site_backward(p, r, sites[i], sites[i].buf, dy, gz[1], top.out, 0, st))) return rc;
-      dy = gz[1];
-    }
-    y = sites[0].buf;
+  // after the last layer: d(y behind them) -> d(y), last first; y ends as the first one's buffer
+  for (int s = site_before(r, at); s >= 0; s = site_before(r, s)) {
+    if ((rc = site_backward(p, r, (*r.seq)[s], site_buf(r, s), dy, gz[1], top.out, 0, st))) return rc;
+    dy = gz[1];
+    y = site_buf(r, s);
   }
   HIP_TRY(launch_act_bwd(dy, y, n * top.out, top.act, gz[0], st));
   // a 1-unit output layer's backward rows, dz[r][k] = dz_out[r] w[k] act'(a[r][k]), are formed by
@@ -121,10 +130,11 @@ int dense_stack_backward(const ign_plan* p, const DenseStackRun& r, hipStream_t 
   auto dense_t_bf = [&](const DenseP& d) { return p->train_dense_bf && (p->train_dense_h16 ? d.pk_ht >= 0 : d.pk_bft >= 0); };
   for (int l = L - 1; l >= 0; --l) {
     const DenseP& d = r.layers[l];
-    sites_at(p, r, l, &tmp, &sites);   // in front of this layer: its input is the last one's z
-    const bool ns = !sites.empty();
+    while (r.seq && (*r.seq)[--at].kind != SL_DENSE) {}   // down to this layer's own entry
+    const int last = site_before(r, at);   // in front of this layer: its input is the last one's z
+    const bool ns = last >= 0;
     if (ns && l == 0 && r.ldx != d.in) return fail(IGN_ERR_RUNTIME, "a layer in front of a padded Dense input");
-    const float* A = ns ? sites.back().buf : l == 0 ? r.x : r.hid[l - 1];
+    const float* A = ns ? site_buf(r, last) : l == 0 ? r.x : r.hid[l - 1];
     auto wgrad = [&](const float* dz) {   // the layer's weight / bias gradient from its dz rows, then its l2 term
       HIP_TRY(launch_tsgemm_add(A, ns || l > 0 ? d.in : r.ldx, dz, d.out, n, d.in, d.out, r.part, r.grads + d.off_w,
                                 d.use_bias ? r.grads + d.off_b : nullptr, st));
@@ -159,11 +169,12 @@ int dense_stack_backward(const ign_plan* p, const DenseStackRun& r, hipStream_t 
     xo = OuterRows{};
     if (ns) {   // d(z) -> d(y) through them, last first, in place
       // a LayerNormalization that stands first in front of layer 0 adds its rows to an added-to dx itself
-      const bool norm_to_dx = l == 0 && r.dx_acc && sites[0].norm;
-      for (int i = (int)sites.size() - 1; i >= 0; --i) {
-        const float* xin = i > 0 ? sites[i - 1].buf : l == 0 ? r.x : r.hid[l - 1];
-        const bool last = i == 0 && norm_to_dx;
-        if ((rc = site_backward(p, r, sites[i], xin, out, last ? r.dx : out, d.in, last, st))) return rc;
+      bool norm_to_dx = false;
+      for (int s = last, below; s >= 0; s = below) {
+        below = site_before(r, s);
+        const float* xin = below >= 0 ? site_buf(r, below) : l == 0 ? r.x : r.hid[l - 1];
+        norm_to_dx = below < 0 && l == 0 && r.dx_acc && (*r.seq)[s].kind == SL_LAYERNORM;
+        if ((rc = site_backward(p, r, (*r.seq)[s], xin, out, norm_to_dx ? r.dx : out, d.in, norm_to_dx, st))) return rc;
       }
       if (l > 0) {
         HIP_TRY(launch_act_bwd(out, r.hid[l - 1], n * d.in, r.layers[l - 1].act, gz[zi], st));

@@ -1,7 +1,9 @@
 // dense_stack.h — one walk over a Dense stack (gemm, bias, activation, Dropout and
 // LayerNormalization layers) and its
 // reverse, for every stack of the training step: predict (p->dense), a readout neural_network
-// operation (RoOp::layers), a message-creation network (MsgNN::layers).  Each layer's kernels
+// operation (RoOp::layers), a message-creation network (MsgNN::layers).  Which Dropout and
+// LayerNormalization layers stand in front of which Dense layer, and in what order, is the stack's
+// seq (plan_lower.h), written at plan time: the walks index into it.  Each layer's kernels
 // follow from its pk_* slots (plan_lower.cpp's layout_packed): only predict's layers have more
 // than pk_w, so the other two end in launch_dense_fwd and launch_row_gemm_t_generic.
 #pragma once
@@ -18,9 +20,9 @@ struct DenseStackRun {
   int ldx = 0;                      // padded with zero columns to a multiple of 16; else layers[0].in)
   float* const* hid = nullptr;      // outputs of layers 0 .. L-2
   float* y = nullptr;               // the last layer's output, behind the sites after it
-  const DropRun* drop = nullptr;    // Dropout: the forward's mask stream; null = no sites run (inference,
-  int stack = -1;                   // message networks).  stack: the sites' stack id, -1 predict, k readout op k
-  const NormRun* norm = nullptr;    // LayerNormalization: the run's buffers; null = none run (message networks)
+  const DropRun* drop = nullptr;    // Dropout: the forward's mask stream; null = seq's Dropout layers do not run (inference)
+  const std::vector<StackLayer>* seq = nullptr;   // the stack's layers in order; null = Dense layers only (message networks)
+  const NormRun* norm = nullptr;    // LayerNormalization: the run's buffers; null = seq's do not run
   // backward
   const float* dy = nullptr;        // d(y)
   float* const* gz = nullptr;       // two layer-gradient buffers (ping-pong) [n][widest]

@@ -658,7 +658,8 @@ int ign_batch_create(ign_plan* p, const ign_batch_desc* d, ign_batch** out) {
   if ((rc = dev_alloc(b.get(), &b->d_pred, P * b->out_units))) return rc;
   for (size_t s = 0; s < p->norms.size(); ++s) {   // one buffer per LayerNormalization layer (readout ops and predict)
     float* t = nullptr;
-    if ((rc = dev_alloc(b.get(), &t, std::max<int64_t>(1, norm_site_floats(p, b.get(), (int)s))))) return rc;
+    if ((rc = dev_alloc(b.get(), &t, std::max<int64_t>(1, stack_rows(p, b.get(), p->norms[s].stack) * p->norms[s].units))))
+      return rc;
     b->d_norm.push_back(t);
   }
   // the resident tables here, on the building thread, not at the first forward: a training loop's
@@ -1096,35 +1097,35 @@ int readout(ign_plan* p, ign_batch* b) {
   } else {
     const float* in = x;
     int in_stride = xs;
-    // predict's LayerNormalization layers, as dense_stack_forward runs them: each in front of a
-    // Dense layer writes its own buffer; after the last one, that layer writes the first's buffer
-    std::vector<StackSite> sites, tail;
-    if (!p->norms.empty()) stack_sites(p, -1, (int)p->dense.size(), false, true, &tail);
-    auto norm = [&](int s, const float* from, int ld, float* to) {
-      const double bytes = (double)P * 4.0 * p->norms[s].units;
-      tm.begin(K_READOUT, 8.0 * P * p->norms[s].units, 2.0 * bytes);
-      const hipError_t e = norm_fwd(p, s, from, ld, P, to, nullptr, st);
-      tm.end();
-      return e;
-    };
-    for (size_t l = 0; l < p->dense.size(); ++l) {
-      const DenseP& dl = p->dense[l];
-      if (!p->norms.empty()) stack_sites(p, -1, (int)l, false, true, &sites);
-      for (const StackSite& s : sites) {
-        HIP_TRY(norm(s.idx, in, in_stride, b->d_norm[s.idx]));
-        in = b->d_norm[s.idx];
-        in_stride = dl.in;
+    // predict's layers in order, a Dropout being the identity here; the LayerNormalization layers
+    // as dense_stack_forward runs them: each in front of a Dense layer writes its own buffer, and from
+    // the last Dense layer on each layer writes the next one's buffer, the last d_pred
+    const std::vector<StackLayer>& seq = p->seq;
+    bool tail = false;
+    for (size_t i = 0; i < seq.size(); ++i) {
+      const StackLayer& e = seq[i];
+      if (e.kind == SL_DROPOUT) continue;
+      tail = tail || (e.kind == SL_DENSE && e.idx + 1 == (int)p->dense.size());
+      size_t nx = i + 1;   // (tail) the next LayerNormalization
+      while (tail && nx < seq.size() && seq[nx].kind != SL_LAYERNORM) ++nx;
+      float* o = !tail ? (e.kind == SL_DENSE ? b->d_ro_tmp[e.idx] : b->d_norm[e.idx])
+                       : nx < seq.size() ? b->d_norm[seq[nx].idx] : b->d_pred;
+      if (e.kind == SL_DENSE) {
+        const DenseP& dl = p->dense[e.idx];
+        tm.begin(K_READOUT, 2.0 * P * dl.in * dl.out, (double)P * 4.0 * (dl.in + dl.out));
+        HIP_TRY(launch_dense_generic(in, P, dl.in, in_stride, prm + dl.off_w, dl.use_bias ? prm + dl.off_b : nullptr,
+                                     dl.out, dl.act, o, st));
+        tm.end();
+        in_stride = dl.out;
+      } else {
+        const int units = p->norms[e.idx].units;
+        tm.begin(K_READOUT, 8.0 * P * units, 2.0 * (double)P * 4.0 * units);
+        HIP_TRY(norm_fwd(p, e.idx, in, in_stride, P, o, nullptr, st));
+        tm.end();
+        in_stride = units;
       }
-      float* o = l + 1 < p->dense.size() ? b->d_ro_tmp[l] : tail.empty() ? b->d_pred : b->d_norm[tail[0].idx];
-      tm.begin(K_READOUT, 2.0 * P * dl.in * dl.out, (double)P * 4.0 * (dl.in + dl.out));
-      HIP_TRY(launch_dense_generic(in, P, dl.in, in_stride, prm + dl.off_w, dl.use_bias ? prm + dl.off_b : nullptr,
-                                   dl.out, dl.act, o, st));
-      tm.end();
       in = o;
-      in_stride = dl.out;
     }
-    for (size_t i = 0; i < tail.size(); ++i)
-      HIP_TRY(norm(tail[i].idx, b->d_norm[tail[i].idx], in_stride, i + 1 < tail.size() ? b->d_norm[tail[i + 1].idx] : b->d_pred));
   }
   return IGN_OK;
 }

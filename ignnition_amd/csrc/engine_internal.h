@@ -164,27 +164,6 @@ struct ign_plan : PlanModel {
 };
 
 namespace ign {
-inline bool stack_has_dropout(const ign_plan* p, int stack) {
-  for (auto& d : p->drops)
-    if (d.stack == stack) return true;
-  return false;
-}
-// One Dropout or LayerNormalization layer in front of a Dense layer (or after the last one): which
-// list it is in, and its index there.
-struct StackSite {
-  bool norm;
-  int idx, order;
-};
-// the layers of `stack` in front of Dense layer `before`, in the architecture's order; the Dropout
-// sites only where `drops` (a training run), the LayerNormalization ones only where `norms`
-inline void stack_sites(const ign_plan* p, int stack, int before, bool drops, bool norms, std::vector<StackSite>* out) {
-  out->clear();
-  for (size_t s = 0; drops && s < p->drops.size(); ++s)
-    if (p->drops[s].stack == stack && p->drops[s].before == before) out->push_back({false, (int)s, p->drops[s].order});
-  for (size_t s = 0; norms && s < p->norms.size(); ++s)
-    if (p->norms[s].stack == stack && p->norms[s].before == before) out->push_back({true, (int)s, p->norms[s].order});
-  std::sort(out->begin(), out->end(), [](const StackSite& a, const StackSite& b) { return a.order < b.order; });
-}
 // LayerNormalization site s on n rows of x (ldx floats apart) into y; stats: NormRun's, or null
 inline hipError_t norm_fwd(const ign_plan* p, int s, const float* x, int ldx, int64_t n, float* y, float* stats,
                            hipStream_t st) {
@@ -285,8 +264,9 @@ int readout_batch(ign_plan* p, ign_batch* b, const ign_batch_desc* d);
 // norm: the LayerNormalization buffers of the run; null = the batch's own (inference)
 int readout_ops_run(ign_plan* p, ign_batch* b, hipStream_t st, const float* const* ent = nullptr,
                     const DropRun* drop = nullptr, const NormRun* norm = nullptr);
-// rows x units of LayerNormalization site s in batch b
-int64_t norm_site_floats(const ign_plan* p, const ign_batch* b, int s);
+// the rows of readout stack `stack` (-1 predict, k readout operation k) in batch b: a site's buffer
+// has that many rows of its units
+int64_t stack_rows(const ign_plan* p, const ign_batch* b, int stack);
 // ign_plan_add_dropout's routine (also called by ign_plan_create_json's lowering)
 int plan_add_dropout(ign_plan* p, int stack, int before_layer, float rate, uint64_t layer_seed);
 // ign_plan_add_layernorm's routine (likewise)

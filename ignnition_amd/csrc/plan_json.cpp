@@ -101,32 +101,29 @@ struct Layer {
   ign_dense_desc d;
 };
 
-struct Drop {   // a Dropout layer of a readout stack (engine.py MPPlan: (before_layer, rate, seed))
-  int before;
-  double rate;
-  uint64_t seed;
-  int order = 0;   // its place among the Dropout (rate > 0) and LayerNormalization layers in front of `before`
-};
-
-struct Norm {   // a LayerNormalization layer of a readout stack (engine.py MPPlan's layernorm records)
-  int before, order;
-  double epsilon;
-  bool center, scale;
+// A Dropout (rate > 0) or LayerNormalization layer of a readout stack (engine.py MPPlan's `extra`
+// records); a stack's list holds them in the architecture's order
+struct Extra {
+  bool norm;
+  int before;                  // the Dense layer it precedes; the stack's layer count = after the last one
+  double rate = 0.0;           // Dropout
+  uint64_t seed = 0;
+  double epsilon = 1e-3;       // LayerNormalization
+  bool center = true, scale = true;
   std::string name;
 };
 
-// Feed_forward_model (AUX:869-1003) + MPPlan._dense_layers.  drops: where the stack's Dropout
-// layers go (a readout stack); null for a message-creation network, which takes none.  The
-// default-name counter counts every layer, Dropout included.  norms: likewise the stack's
-// LayerNormalization layers.
+// Feed_forward_model (AUX:869-1003) + MPPlan._dense_layers.  extra: where the stack's Dropout and
+// LayerNormalization layers go (a readout stack); null for a message-creation network, which takes
+// none.  The default-name counter counts every layer, Dropout included.
 std::vector<Layer> dense_layers(const JVal& architecture, const std::string& role, const char* what,
-                                std::vector<Drop>* drops, std::vector<Norm>* norms = nullptr) {
+                                std::vector<Extra>* extra) {
   std::vector<Layer> out;
-  int counter = 0, in_front = 0;   // in_front: Dropout / LayerNormalization layers since the last Dense
+  int counter = 0;
   for (const JVal& l : arr(architecture, std::string(what) + " nn_architecture")) {
     const std::string type = str(need(l, "type_layer", what), std::string(what) + " type_layer");
     if (type == "Dropout") {
-      if (!drops)
+      if (!extra)
         unsupported("message layer type Dropout is not lowered: a message-creation network would need a fresh mask "
                     "per iteration (Dropout is lowered in the readout's Dense stacks only)");
       for (auto& kv : l.obj)
@@ -136,12 +133,16 @@ std::vector<Layer> dense_layers(const JVal& architecture, const std::string& rol
       if (!(rate >= 0.0 && rate < 1.0)) invalid("Dropout rate must be in [0, 1), got " + std::to_string(rate));
       const JVal* sd = opt(l, "seed");
       const uint64_t seed = sd && sd->t != JVal::Null ? (uint64_t)(int64_t)number(*sd, "Dropout seed") : 0;
-      if (rate > 0.0) drops->push_back({(int)out.size(), rate, seed, in_front++});   // rate 0: no layer (TF returns x)
+      if (rate > 0.0) {   // rate 0: no layer (TF returns x)
+        extra->push_back({false, (int)out.size()});
+        extra->back().rate = rate;
+        extra->back().seed = seed;
+      }
       ++counter;
       continue;
     }
-    if (type == "LayerNormalization" && norms) {
-      Norm n{(int)out.size(), in_front++, 1e-3, true, true, ""};
+    if (type == "LayerNormalization" && extra) {
+      Extra n{true, (int)out.size()};
       for (auto& kv : l.obj) {
         const std::string& k = kv.first;
         if (k == "type_layer") continue;
@@ -159,13 +160,13 @@ std::vector<Layer> dense_layers(const JVal& architecture, const std::string& rol
       }
       if (!(n.epsilon >= 0.0)) invalid("LayerNormalization epsilon must be >= 0, got " + std::to_string(n.epsilon));
       if (n.name.empty()) n.name = "layer_" + std::to_string(counter) + "_" + type + "_" + role;
-      norms->push_back(n);
+      extra->push_back(n);
       ++counter;
       continue;
     }
     if (type != "Dense")
       unsupported(std::string(what) + " layer type " + type + " is not lowered (" +
-                  (drops ? "Dense, Dropout and LayerNormalization" : "Dense") + " only)");
+                  (extra ? "Dense, Dropout and LayerNormalization" : "Dense") + " only)");
     for (auto& kv : l.obj)
       if (kv.first != "type_layer" && kv.first != "units" && kv.first != "activation" &&
           kv.first != "kernel_regularizer" && kv.first != "name" && kv.first != "use_bias")
@@ -181,11 +182,11 @@ std::vector<Layer> dense_layers(const JVal& architecture, const std::string& rol
     y.d.l2 = kr && truthy(*kr) ? (float)number(*kr, "kernel_regularizer") : 0.f;
     out.push_back(y);
     ++counter;
-    in_front = 0;
   }
-  if (drops && !drops->empty() && out.empty()) invalid(std::string(what) + " network has a Dropout but no Dense layer");
-  if (norms && !norms->empty() && out.empty())
-    invalid(std::string(what) + " network has a LayerNormalization but no Dense layer");
+  for (bool norm : {false, true})
+    for (size_t i = 0; extra && out.empty() && i < extra->size(); ++i)
+      if ((*extra)[i].norm == norm)
+        invalid(std::string(what) + " network has a " + (norm ? "LayerNormalization" : "Dropout") + " but no Dense layer");
   return out;
 }
 
@@ -224,8 +225,7 @@ struct Lowered {
     int type, mode = 0, adj = -1, counter = 0, in_width = 0;
     std::vector<int32_t> inputs;
     std::vector<Layer> layers;
-    std::vector<Drop> drops;
-    std::vector<Norm> norms;
+    std::vector<Extra> extra;
   };
   std::vector<RoOp> ro_ops;
   std::vector<int32_t> ro_inputs;
@@ -233,8 +233,7 @@ struct Lowered {
   int predict_counter = 0;
   std::string label;
   std::vector<Layer> dense;
-  std::vector<Drop> drops;   // the predict network's
-  std::vector<Norm> norms;
+  std::vector<Extra> extra;   // the predict network's
 
   std::vector<std::pair<std::string, std::vector<int64_t>>> param_specs() const {
     std::vector<std::pair<std::string, std::vector<int64_t>>> s;
@@ -261,11 +260,11 @@ struct Lowered {
       s.push_back({"attention/attn_kernel", {2 * attn_dim, 1}});
     }
     // a stack's tensors: each LayerNormalization's gamma / beta in front of the Dense layer it precedes
-    auto stack = [&](int counter, int fan, const std::vector<Layer>& layers, const std::vector<Norm>& norms) {
+    auto stack = [&](int counter, int fan, const std::vector<Layer>& layers, const std::vector<Extra>& extra) {
       const std::string model = "readout_model_" + std::to_string(counter) + "/";
       for (size_t li = 0; li <= layers.size(); ++li) {
-        for (const Norm& n : norms) {   // (in the architecture's order)
-          if (n.before != (int)li) continue;
+        for (const Extra& n : extra) {   // (in the architecture's order)
+          if (!n.norm || n.before != (int)li) continue;
           if (n.scale) s.push_back({model + n.name + "/gamma", {fan}});
           if (n.center) s.push_back({model + n.name + "/beta", {fan}});
         }
@@ -276,10 +275,10 @@ struct Lowered {
         fan = l.d.units;
       }
     };
-    for (auto& op : ro_ops) stack(op.counter, op.in_width, op.layers, op.norms);
+    for (auto& op : ro_ops) stack(op.counter, op.in_width, op.layers, op.extra);
     int fan = 0;
     for (int i : ro_inputs) fan += ro_widths[i];
-    stack(predict_counter, fan, dense, norms);
+    stack(predict_counter, fan, dense, extra);
     return s;
   }
 };
@@ -524,8 +523,7 @@ Lowered lower(const JVal& data, const JVal& dims) {
       d.type = IGN_RO_NEURAL_NETWORK;
       const std::string nn = str(need(op, "nn_name", "readout neural_network"), "nn_name");
       if (!nets.count(nn)) invalid("readout nn_name '" + nn + "' is not defined");
-      d.layers = dense_layers(need(*nets[nn], "nn_architecture", "readout network"), "readout", "readout", &d.drops,
-                              &d.norms);
+      d.layers = dense_layers(need(*nets[nn], "nn_architecture", "readout network"), "readout", "readout", &d.extra);
       for (int i : d.inputs) d.in_width += p.ro_widths[i];
       const JVal* on = opt(op, "output_name");
       add(on ? str(*on, "output_name") : "None", d.layers.back().d.units, first);
@@ -566,11 +564,12 @@ Lowered lower(const JVal& data, const JVal& dims) {
   p.label = str(need(*pred, "label", "predict"), "label");
   for (const JVal& i : arr(need(*pred, "input", "predict"), "input")) p.ro_inputs.push_back(resolve(i));
   const std::string nn = pred->get("nn_name")->str;
-  p.dense = dense_layers(need(*nets[nn], "nn_architecture", "predict network"), "readout", "readout", &p.drops, &p.norms);
+  p.dense = dense_layers(need(*nets[nn], "nn_architecture", "predict network"), "readout", "readout", &p.extra);
   return p;
 }
 
-std::string describe(const Lowered& p) {
+// m: the plan lowered from p, its Dropout and LayerNormalization layers added
+std::string describe(const Lowered& p, const PlanModel& m) {
   std::string s = "{\"iterations\": " + std::to_string(p.T) + ", \"entities\": [";
   for (size_t e = 0; e < p.ents.size(); ++e) {
     s += (e ? ", " : "") + std::string("{\"name\": ") + quote(p.ents[e]) + ", \"hidden\": " + std::to_string(p.hidden[e]) +
@@ -596,43 +595,35 @@ std::string describe(const Lowered& p) {
   // Dropout sites in site order (readout operations in order, then predict): stack = the
   // operation's index among the lowered operations (ign_plan_add_dropout's), -1 for predict
   s += "], \"dropout\": [";
-  int site = 0;
-  auto sites = [&](int stack, const std::vector<Drop>& drops) {
-    std::vector<Drop> d = drops;
-    std::stable_sort(d.begin(), d.end(), [](const Drop& a, const Drop& b) { return a.before < b.before; });
-    for (const Drop& x : d) {
-      char rate[32];
-      snprintf(rate, sizeof rate, "%.9g", (double)(float)x.rate);
-      s += (site ? ", " : "") + std::string("{\"site\": ") + std::to_string(site) + ", \"stack\": " + std::to_string(stack) +
-           ", \"before_layer\": " + std::to_string(x.before) + ", \"rate\": " + rate + ", \"seed\": " +
-           std::to_string(x.seed) + "}";
-      ++site;
-    }
-  };
-  for (size_t k = 0; k < p.ro_ops.size(); ++k) sites((int)k, p.ro_ops[k].drops);
-  sites(-1, p.drops);
+  for (size_t i = 0; i < m.drops.size(); ++i) {
+    const DropSite& x = m.drops[i];
+    char rate[32];
+    snprintf(rate, sizeof rate, "%.9g", (double)x.rate);
+    s += (i ? ", " : "") + std::string("{\"site\": ") + std::to_string(i) + ", \"stack\": " + std::to_string(x.stack) +
+         ", \"before_layer\": " + std::to_string(x.before) + ", \"rate\": " + rate + ", \"seed\": " +
+         std::to_string(x.seed) + "}";
+  }
   // LayerNormalization layers in the same order, numbered on their own; order = the layer's place
-  // among the Dropout sites and LayerNormalization layers in front of the same Dense layer
-  s += "], \"layernorm\": [";
-  int nsite = 0;
-  auto layers = [&](int stack, int fan, const std::vector<Layer>& dense, const std::vector<Norm>& norms) {
-    std::vector<Norm> d = norms;
-    std::stable_sort(d.begin(), d.end(), [](const Norm& a, const Norm& b) { return a.before < b.before; });
-    for (const Norm& x : d) {
-      char eps[32];
-      snprintf(eps, sizeof eps, "%.9g", (double)(float)x.epsilon);
-      const int units = x.before == 0 ? fan : dense[x.before - 1].d.units;
-      s += (nsite ? ", " : "") + std::string("{\"site\": ") + std::to_string(nsite) + ", \"stack\": " + std::to_string(stack) +
-           ", \"before_layer\": " + std::to_string(x.before) + ", \"order\": " + std::to_string(x.order) +
-           ", \"epsilon\": " + eps + ", \"center\": " + (x.center ? "true" : "false") + ", \"scale\": " +
-           (x.scale ? "true" : "false") + ", \"units\": " + std::to_string(units) + ", \"name\": " + quote(x.name) + "}";
-      ++nsite;
-    }
+  // among the Dropout sites and LayerNormalization layers in front of the same Dense layer.  The
+  // names, in site order: a stack's list already holds its layers by position
+  std::vector<std::string> names;
+  auto name = [&](const std::vector<Extra>& extra) {
+    for (const Extra& e : extra)
+      if (e.norm) names.push_back(e.name);
   };
-  for (size_t k = 0; k < p.ro_ops.size(); ++k) layers((int)k, p.ro_ops[k].in_width, p.ro_ops[k].layers, p.ro_ops[k].norms);
-  int fan = 0;
-  for (int i : p.ro_inputs) fan += p.ro_widths[i];
-  layers(-1, fan, p.dense, p.norms);
+  for (auto& op : p.ro_ops) name(op.extra);
+  name(p.extra);
+  s += "], \"layernorm\": [";
+  for (size_t i = 0; i < m.norms.size(); ++i) {
+    const NormSite& x = m.norms[i];
+    char eps[32];
+    snprintf(eps, sizeof eps, "%.9g", (double)x.epsilon);
+    s += (i ? ", " : "") + std::string("{\"site\": ") + std::to_string(i) + ", \"stack\": " + std::to_string(x.stack) +
+         ", \"before_layer\": " + std::to_string(x.before) + ", \"order\": " +
+         std::to_string(site_order(&m, x.stack, SL_LAYERNORM, (int)i)) + ", \"epsilon\": " + eps + ", \"center\": " +
+         (x.center ? "true" : "false") + ", \"scale\": " + (x.scale ? "true" : "false") + ", \"units\": " +
+         std::to_string(x.units) + ", \"name\": " + quote(names[i]) + "}";
+  }
   return s + "]}";
 }
 
@@ -718,24 +709,16 @@ int ign_plan_create_json(const char* model_json, const char* dims_json, int32_t 
   int rc = ign_plan_create(&d, device, &plan);
   if (rc) return rc;
   // the Dropout and LayerNormalization layers (ign_plan_add_dropout's and ign_plan_add_layernorm's
-  // routines), each stack's in the architecture's order: the two lists hold them in that order
-  auto add_sites = [&](int stack, const std::vector<Drop>& drops, const std::vector<Norm>& norms) {
-    size_t di = 0, ni = 0;
-    while (!rc && (di < drops.size() || ni < norms.size())) {
-      const bool drop = ni == norms.size() ||
-                        (di < drops.size() && std::make_pair(drops[di].before, drops[di].order) <
-                                                  std::make_pair(norms[ni].before, norms[ni].order));
-      if (drop) {
-        rc = plan_add_dropout(plan, stack, drops[di].before, (float)drops[di].rate, drops[di].seed);
-        ++di;
-      } else {
-        rc = plan_add_layernorm(plan, stack, norms[ni].before, (float)norms[ni].epsilon, norms[ni].center, norms[ni].scale);
-        ++ni;
-      }
+  // routines), each stack's in the architecture's order
+  auto add_sites = [&](int stack, const std::vector<Extra>& extra) {
+    for (size_t i = 0; !rc && i < extra.size(); ++i) {
+      const Extra& e = extra[i];
+      rc = e.norm ? plan_add_layernorm(plan, stack, e.before, (float)e.epsilon, e.center, e.scale)
+                  : plan_add_dropout(plan, stack, e.before, (float)e.rate, e.seed);
     }
   };
-  for (size_t k = 0; k < p.ro_ops.size(); ++k) add_sites((int)k, p.ro_ops[k].drops, p.ro_ops[k].norms);
-  add_sites(-1, p.drops, p.norms);
+  for (size_t k = 0; k < p.ro_ops.size(); ++k) add_sites((int)k, p.ro_ops[k].extra);
+  add_sites(-1, p.extra);
   if (rc) {
     ign_plan_destroy(plan);
     return rc;
@@ -747,7 +730,7 @@ int ign_plan_create_json(const char* model_json, const char* dims_json, int32_t 
     ign_plan_destroy(plan);
     return fail(IGN_ERR_INVALID, "internal: %zu parameter names for %d tensors", specs.size(), nt);
   }
-  plan->describe = describe(p);
+  plan->describe = describe(p, *plan);
   *out = plan;
   return IGN_OK;
 }

@@ -6,6 +6,8 @@
 
 #include <climits>
 
+#include "dropout_rng.h"
+
 namespace ign {
 
 namespace {
@@ -209,6 +211,7 @@ int lower_readout(const ign_plan_desc* d, PlanModel* p) {
         }
         if (od.num_dense <= 0 || !od.dense) return fail(IGN_ERR_INVALID, "readout op %d: no Dense layer", k);
         if ((rc = parse_dense(od.dense, od.num_dense, op.in_width, op.layers, "readout op", k))) return rc;
+        for (int l = 0; l < od.num_dense; ++l) op.seq.push_back({SL_DENSE, l});
         p->ro_t.push_back({t0.space, t0.sid, op.layers.back().out});
         break;
       }
@@ -270,6 +273,7 @@ int lower_readout(const ign_plan_desc* d, PlanModel* p) {
   int rc = parse_dense(d->dense, d->num_dense, width, p->dense, "predict", 0);
   if (rc) return rc;
   if (p->dense.empty()) return fail(IGN_ERR_INVALID, "readout has no Dense layer");
+  for (int l = 0; l < d->num_dense; ++l) p->seq.push_back({SL_DENSE, l});
   p->fused_readout = p->dense.size() == 3 &&
                      readout3_supported(width, p->dense[0].out, p->dense[1].out, p->dense[0].act, p->dense[1].act) &&
                      p->dense[2].out == 1 && p->dense[0].use_bias && p->dense[1].use_bias;
@@ -310,27 +314,17 @@ void layout_params(PlanModel* p) {
   }
   // a stack's LayerNormalization tensors stand where Keras creates them: in front of the Dense
   // layer they precede (after the last one: at the stack's end), gamma then beta; owner = the site
-  auto put_norms = [&](int stack, int before) {
-    for (size_t s = 0; s < p->norms.size(); ++s) {
-      NormSite& ns = p->norms[s];
-      if (ns.stack != stack || ns.before != before) continue;
-      ns.off_gamma = ns.scale ? put(13, (int)s, 1, ns.units) : -1;
-      ns.off_beta = ns.center ? put(14, (int)s, 1, ns.units) : -1;
+  auto put_stack = [&](std::vector<DenseP>& layers, const std::vector<StackLayer>& seq, int kind_w, int kind_b, int owner) {
+    for (const StackLayer& e : seq) {
+      if (e.kind == SL_DENSE) put_dense(layers[e.idx], kind_w, kind_b, owner + e.idx);
+      if (e.kind != SL_LAYERNORM) continue;
+      NormSite& ns = p->norms[e.idx];
+      ns.off_gamma = ns.scale ? put(13, e.idx, 1, ns.units) : -1;
+      ns.off_beta = ns.center ? put(14, e.idx, 1, ns.units) : -1;
     }
   };
-  for (size_t k = 0; k < p->ro_ops.size(); ++k) {
-    const size_t L = p->ro_ops[k].layers.size();
-    for (size_t l = 0; l < L; ++l) {
-      put_norms((int)k, (int)l);
-      put_dense(p->ro_ops[k].layers[l], 11, 12, (int)(k * 64 + l));
-    }
-    if (L) put_norms((int)k, (int)L);
-  }
-  for (size_t l = 0; l < p->dense.size(); ++l) {
-    put_norms(-1, (int)l);
-    put_dense(p->dense[l], 3, 4, (int)l);
-  }
-  put_norms(-1, (int)p->dense.size());
+  for (size_t k = 0; k < p->ro_ops.size(); ++k) put_stack(p->ro_ops[k].layers, p->ro_ops[k].seq, 11, 12, (int)(k * 64));
+  put_stack(p->dense, p->seq, 3, 4, 0);
   p->n_params = off;
 }
 
@@ -463,30 +457,66 @@ void layout_packed(PlanModel* p) {
   for (auto& j : jobs) p->packs.push_back(j.second);
 }
 
-}  // namespace
+// s into its array in site order (readout ops in order, then predict; by position; then by
+// insertion); the index it got
+template <class Site>
+int insert_site(std::vector<Site>& sites, const Site& s) {
+  auto key = [](const Site& x) { return std::make_pair(x.stack < 0 ? INT_MAX : x.stack, x.before); };
+  size_t at = 0;
+  while (at < sites.size() && key(sites[at]) <= key(s)) ++at;
+  sites.insert(sites.begin() + at, s);
+  return (int)at;
+}
 
-int add_layernorm(PlanModel* p, int stack, int before_layer, float epsilon, int center, int scale) {
+// The one place a Dropout (d) or LayerNormalization (n) layer enters a stack: the checks of stack and
+// before_layer, the kind's own check, the site array and every seq the insertion touches.
+int add_site(PlanModel* p, int kind, int stack, int before_layer, DropSite d, NormSite n) {
+  const char* api = kind == SL_DROPOUT ? "ign_plan_add_dropout" : "ign_plan_add_layernorm";
   const std::vector<DenseP>* layers = stack_layers(p, stack);
   if (!layers)
-    return fail(IGN_ERR_INVALID, "ign_plan_add_layernorm: stack %d is neither -1 (predict) nor a readout "
-                "neural_network operation", stack);
+    return fail(IGN_ERR_INVALID, "%s: stack %d is neither -1 (predict) nor a readout neural_network operation", api, stack);
   const int L = (int)layers->size();
   if (before_layer < 0 || before_layer > L)
-    return fail(IGN_ERR_INVALID, "ign_plan_add_layernorm: before_layer %d outside 0..%d", before_layer, L);
-  if (!(epsilon >= 0.f))   // Keras raises ValueError
-    return fail(IGN_ERR_INVALID, "LayerNormalization epsilon must be >= 0, got %g", (double)epsilon);
+    return fail(IGN_ERR_INVALID, "%s: before_layer %d outside 0..%d", api, before_layer, L);
+  if (kind == SL_DROPOUT) {
+    if (!(d.rate >= 0.f && d.rate < 1.f))   // tf.nn.dropout raises ValueError
+      return fail(IGN_ERR_INVALID, "Dropout rate must be in [0, 1), got %g", (double)d.rate);
+    if (d.rate == 0.f) return IGN_OK;   // tf.nn.dropout returns x: no layer, no site
+  } else if (!(n.epsilon >= 0.f)) {   // Keras raises ValueError
+    return fail(IGN_ERR_INVALID, "LayerNormalization epsilon must be >= 0, got %g", (double)n.epsilon);
+  }
+  d.stack = n.stack = stack;
+  d.before = n.before = before_layer;
+  d.units = n.units = before_layer < L ? (*layers)[before_layer].in : layers->back().out;
+  const int at = kind == SL_DROPOUT ? insert_site(p->drops, d) : insert_site(p->norms, n);
+  auto shift = [&](std::vector<StackLayer>& seq) {   // the sites behind it moved up by one
+    for (StackLayer& e : seq) e.idx += e.kind == kind && e.idx >= at;
+  };
+  for (RoOp& op : p->ro_ops) shift(op.seq);
+  shift(p->seq);
+  std::vector<StackLayer>& seq = stack == -1 ? p->seq : p->ro_ops[stack].seq;
+  auto pos = seq.begin();   // in front of Dense before_layer, behind what stands there; or at the end
+  while (pos != seq.end() && !(pos->kind == SL_DENSE && pos->idx == before_layer)) ++pos;
+  seq.insert(pos, {kind, at});
+  return IGN_OK;
+}
+
+}  // namespace
+
+int add_dropout(PlanModel* p, int stack, int before_layer, float rate, uint64_t layer_seed) {
+  DropSite d;
+  d.rate = rate;
+  d.scale = dropout_scale(rate);
+  d.seed = layer_seed;
+  return add_site(p, SL_DROPOUT, stack, before_layer, d, NormSite());
+}
+
+int add_layernorm(PlanModel* p, int stack, int before_layer, float epsilon, int center, int scale) {
   NormSite n;
-  n.stack = stack;
-  n.before = before_layer;
-  n.order = sites_in_front(p, stack, before_layer);
   n.epsilon = epsilon;
   n.center = center != 0;
   n.scale = scale != 0;
-  n.units = before_layer < L ? (*layers)[before_layer].in : layers->back().out;
-  auto key = [](const NormSite& s) { return std::make_pair(s.stack < 0 ? INT_MAX : s.stack, s.before); };
-  size_t at = 0;
-  while (at < p->norms.size() && key(p->norms[at]) <= key(n)) ++at;
-  p->norms.insert(p->norms.begin() + at, n);
+  if (int rc = add_site(p, SL_LAYERNORM, stack, before_layer, DropSite(), n)) return rc;
   if (stack == -1) p->fused_readout = false;   // the fused 256-256-1 kernel has no place for the layer
   layout_params(p);   // both layouts again
   layout_packed(p);

@@ -1,6 +1,7 @@
 // plan_lower.h — the plan lowering of ign_plan_create, separate from the device: an ign_plan_desc
-// and the plan-level switches become a PlanModel (the validated model, the raw parameter layout, the
-// packed-fragment layout and the list of pack launches that fills it), plain host data.  No HIP
+// and the plan-level switches become a PlanModel (the validated model, every readout Dense stack's
+// layers as one ordered list, the raw parameter layout, the packed-fragment layout and the list of
+// pack launches that fills it), plain host data.  No HIP
 // header: plan_lower.cpp builds with a plain C++17 compiler (tests/cpp/plan_lower_check.cpp, run
 // under the sanitizers).  engine.cpp's ign_plan derives from PlanModel and adds the device side.
 #pragma once
@@ -22,34 +23,43 @@ struct RoTensor {
   int width = 0;
   bool same_space(const RoTensor& o) const { return space == o.space && (space == RS_GRAPH || sid == o.sid); }
 };
+// One layer of a readout Dense stack, in the architecture's order.  idx: the Dense layer of the
+// stack, or the site in PlanModel::drops / PlanModel::norms.  A stack's list reads: the layers in
+// front of Dense 0, Dense 0, those in front of Dense 1, ..., the last Dense, the layers after it.
+// Everything that needs to know which layer follows which walks this list; nothing else orders them.
+enum { SL_DENSE = 0, SL_DROPOUT = 1, SL_LAYERNORM = 2 };
+struct StackLayer {
+  int kind, idx;
+};
 struct RoOp {
   int type = 0, mode = 0, adj = -1;
   std::vector<int> in;            // tensor ids
   std::vector<DenseP> layers;     // IGN_RO_NEURAL_NETWORK
+  std::vector<StackLayer> seq;    // ... and all its layers in order
   int in_width = 0;               // neural_network: concatenated input width
   int out = -1;                   // first output tensor id
 };
 
 // A Dropout layer of a readout Dense stack (ign_plan_add_dropout): live in training only.  The
 // plan keeps them in site order: readout ops in order, then predict; within a stack by position,
-// then by insertion.  A site's ordinal is its index there.
+// then by insertion.  A site's ordinal is its index there: its Philox counter word and its slot in
+// DropRun::buf.  Where it stands among the LayerNormalization layers is the stack's seq.
 struct DropSite {
   int stack = -1;        // readout-op index, or -1 for predict
   int before = 0;        // Dense layer it precedes; the stack's layer count = after the last one
   float rate = 0.f, scale = 1.f;
   uint64_t seed = 0;     // the layer's own seed option, xor-mixed into the batch's stream seed
-  int order = 0;         // position among the Dropout and LayerNormalization layers in front of `before`
+  int units = 0;         // the width it masks: the input width of `before`, or the stack's output width
 };
 
 // A LayerNormalization layer of a readout Dense stack (ign_plan_add_layernorm): live in inference and
 // in training.  Kept like the Dropout sites (readout ops in order, then predict; by position, then
 // by insertion), numbered on their own: a Dropout site's number, its Philox counter word, counts
-// Dropout layers only.  `order` places the two kinds of layer in front of one Dense layer in the
-// order the architecture lists them.
+// Dropout layers only.  Its index is its slot in NormRun::buf / stats and ign_batch::d_norm, and its
+// tensors' owner.
 struct NormSite {
   int stack = -1;        // readout-op index, or -1 for predict
   int before = 0;        // Dense layer it precedes; the stack's layer count = after the last one
-  int order = 0;
   float epsilon = 1e-3f;
   int64_t off_gamma = -1, off_beta = -1;   // [units] each; -1: scale / center false, no tensor
   bool center = true, scale = true;
@@ -138,6 +148,7 @@ struct PlanModel : PlanSwitches {
   std::vector<CellP> cells;
   std::vector<int> ro_in;         // predict inputs: readout tensor ids
   std::vector<DenseP> dense;
+  std::vector<StackLayer> seq;    // predict's layers in order (dense: its Dense layers)
   std::vector<RoTensor> ro_t;     // readout tensors: entity states, then the op outputs
   std::vector<RoOp> ro_ops;
   std::vector<int> adj_src_ent, adj_dst_ent;   // per adjacency slot (from the MPs that read it)
@@ -160,16 +171,26 @@ inline const std::vector<DenseP>* stack_layers(const PlanModel* p, int stack) {
   if (stack < 0 || stack >= (int)p->ro_ops.size() || p->ro_ops[stack].type != IGN_RO_NEURAL_NETWORK) return nullptr;
   return &p->ro_ops[stack].layers;
 }
-// the Dropout and LayerNormalization layers already in front of Dense layer `before` of `stack`
-inline int sites_in_front(const PlanModel* p, int stack, int before) {
+// ... and all of the stack's layers in order, or null
+inline const std::vector<StackLayer>* stack_seq(const PlanModel* p, int stack) {
+  return !stack_layers(p, stack) ? nullptr : stack == -1 ? &p->seq : &p->ro_ops[stack].seq;
+}
+// a site's place among the Dropout and LayerNormalization layers in front of the same Dense layer
+inline int site_order(const PlanModel* p, int stack, int kind, int idx) {
   int n = 0;
-  for (auto& d : p->drops) n += d.stack == stack && d.before == before;
-  for (auto& d : p->norms) n += d.stack == stack && d.before == before;
+  for (const StackLayer& e : *stack_seq(p, stack)) {
+    if (e.kind == kind && e.idx == idx) break;
+    n = e.kind == SL_DENSE ? 0 : n + 1;
+  }
   return n;
 }
-// ign_plan_add_layernorm on the model: the site, its gamma / beta tensors (kinds 13 / 14, in front of
-// the Dense layer it precedes) and both layouts again; predict's stack leaves the fused readout.
-// Only before the parameters exist on a device (the caller checks).
+// ign_plan_add_dropout / ign_plan_add_layernorm on the model: the site enters drops / norms at its
+// place in site order and the stack's seq in front of Dense layer before_layer, behind the layers
+// already there.  A rate of 0 adds nothing (tf.nn.dropout returns x).  A LayerNormalization brings
+// its gamma / beta tensors (kinds 13 / 14, in front of the Dense layer it precedes) and both layouts
+// again, and predict's stack leaves the fused readout: only before the parameters exist on a device
+// (the caller checks).
+int add_dropout(PlanModel* p, int stack, int before_layer, float rate, uint64_t layer_seed);
 int add_layernorm(PlanModel* p, int stack, int before_layer, float epsilon, int center, int scale);
 
 // d + sw -> *m (a fresh PlanModel); IGN_OK or the refusal's code, its text in ign_last_error

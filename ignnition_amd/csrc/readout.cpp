@@ -49,10 +49,8 @@ static std::vector<int64_t> space_offsets(const ign_batch* b, const RoTensor& t)
   return off;
 }
 
-int64_t norm_site_floats(const ign_plan* p, const ign_batch* b, int s) {
-  const NormSite& ns = p->norms[s];
-  const int first = ns.stack < 0 ? p->ro_in[0] : p->ro_ops[ns.stack].in[0];
-  return space_rows(p, b, p->ro_t[first]) * ns.units;
+int64_t stack_rows(const ign_plan* p, const ign_batch* b, int stack) {
+  return space_rows(p, b, p->ro_t[stack < 0 ? p->ro_in[0] : p->ro_ops[stack].in[0]]);
 }
 
 const float* readout_tensor(const ign_plan* p, const ign_batch* b, int id) {
@@ -168,7 +166,7 @@ int readout_ops_run(ign_plan* p, ign_batch* b, hipStream_t st, const float* cons
           x = bo.cat;
         }
         const DenseStackRun r{op.layers.data(), (int)op.layers.size(), n, x, op.in_width, bo.tmp.data(), bo.out[0],
-                              drop, (int)k, norm};
+                              drop, &op.seq, norm};
         if (int rc = dense_stack_forward(p, r, st)) return rc;
         break;
       }

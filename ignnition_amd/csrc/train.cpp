@@ -326,7 +326,7 @@ int ro_stack_backward(ign_plan* p, TrainState* t, DenseStackRun r, const float* 
 
 // predict's Dense stack (p->dense) on input x, for the training forward and its backward
 DenseStackRun predict_stack(const ign_plan* p, const ign_batch* b, TrainState* t, const float* x) {
-  return {p->dense.data(), (int)p->dense.size(), b->n_pred, x, p->ro_width, t->act.data(), b->d_pred, &t->drop, -1,
+  return {p->dense.data(), (int)p->dense.size(), b->n_pred, x, p->ro_width, t->act.data(), b->d_pred, &t->drop, &p->seq,
           &t->norm};
 }
 
@@ -344,7 +344,7 @@ int readout_ops_backward(ign_plan* p, ign_batch* b, TrainState* t, hipStream_t s
       case IGN_RO_NEURAL_NETWORK: {   // Readout_nn (AUX:1188-1211): Dense stack on concat(inputs)
         const float* x = op.in.size() > 1 ? bo.cat : ro_tensor(b, t, op.in[0]);
         const DenseStackRun r{op.layers.data(), (int)op.layers.size(), n, x, op.in_width, bo.tmp.data(), bo.out[0],
-                              &t->drop, k, &t->norm};
+                              &t->drop, &op.seq, &t->norm};
         if ((rc = ro_stack_backward(p, t, r, t->dT[op.out], t->rz, op.in, t->rcat, st))) return rc;
         break;
       }
@@ -608,16 +608,12 @@ TrainScratch train_scratch(const ign_plan* p, const ign_batch* b) {
       z.ties = std::max(z.ties, (int64_t)b->G * p->ro_t[op.in[0]].width);
     }
   }
-  for (const DropSite& d : p->drops) {
-    const std::vector<DenseP>& layers = d.stack < 0 ? p->dense : p->ro_ops[d.stack].layers;
-    const int64_t rows = d.stack < 0 ? P : space_rows(p, b, p->ro_t[p->ro_ops[d.stack].in[0]]);
-    z.drop.push_back(rows * (d.before < (int)layers.size() ? layers[d.before].in : layers.back().out));
-  }
-  for (size_t s = 0; s < p->norms.size(); ++s) {
-    const int64_t fl = norm_site_floats(p, b, (int)s), rows = fl / p->norms[s].units;
-    z.norm.push_back(fl);
+  for (const DropSite& d : p->drops) z.drop.push_back(stack_rows(p, b, d.stack) * d.units);
+  for (const NormSite& ns : p->norms) {
+    const int64_t rows = stack_rows(p, b, ns.stack);
+    z.norm.push_back(rows * ns.units);
     z.norm_rows.push_back(rows);
-    z.part = std::max(z.part, layernorm_partial_floats(rows, p->norms[s].units));
+    z.part = std::max(z.part, layernorm_partial_floats(rows, ns.units));
   }
   return z;
 }
@@ -888,7 +884,7 @@ int ign_forward_train_end(ign_plan* p, ign_batch* b, float* pred_out) {
   // (a stack with a Dropout site runs layer by layer: the mask sits between two of its launches)
   const bool fused = p->train_fused_readout && p->fused_readout && p->readout_variant >= 4 && p->dense.size() == 3 &&
                      p->dense[1].pk_h >= 0 && p->dense[0].pk_bf >= 0 && p->dense[1].pk_bf >= 0 &&
-                     p->dense[0].use_bias && p->dense[1].use_bias && !stack_has_dropout(p, -1);
+                     p->dense[0].use_bias && p->dense[1].use_bias && p->seq.size() == p->dense.size();
   if (!fused && (rc = dense_stack_forward(p, predict_stack(p, b, t, x), st))) return rc;
   if (fused) {
     const DenseP &l1 = p->dense[0], &l2 = p->dense[1], &l3 = p->dense[2];

@@ -109,11 +109,8 @@ class MPPlan:
     ro_spaces: list = field(default_factory=list)       # row space per tensor: ("entity", e) / ("graph",) / ("adj", slot)
     predict_counter: int = 0                           # readout_model_<index of predict in the readout list>
     dense: list = field(default_factory=list)          # [(name, units, act, use_bias, l2)]
-    dropout: list = field(default_factory=list)        # predict's Dropout layers: [(before_layer, rate, seed)]
-    layernorm: list = field(default_factory=list)      # predict's LayerNormalization layers:
-                                                       # [(before_layer, order, epsilon, center, scale, name)]
-    sites: list = field(default_factory=list)          # predict's layers of both kinds in the architecture's order:
-                                                       # the ign_plan_add_* calls without their stack (stack_sites)
+    extra: list = field(default_factory=list)          # predict's Dropout and LayerNormalization layers in the
+                                                       # architecture's order (_dense_layers)
     iterations: int = 0
     readout_label: str = ""
     convolution_dim: int = 0                           # F of convolution/kernel [F, F] (0: none)
@@ -190,16 +187,13 @@ class MPPlan:
 
     @staticmethod
     def _dense_layers(arch, what):
-        """(Dense layers, Dropout records, LayerNormalization records) of a readout stack.  A Dropout
-        layer (tf.nn.dropout in training, the identity otherwise) is recorded as (before_layer, rate,
-        seed): the Dense layer it precedes, len(layers) after the last one.  rate 0 is no layer, as TF
-        returns x.  A LayerNormalization is (before_layer, order, epsilon, center, scale, name);
-        order = its place among the Dropout records and LayerNormalization layers in front of that
-        Dense layer, in the architecture's order.  The fourth list holds both kinds in that order,
-        as the calls that add them: ("dropout", before_layer, rate, seed) or ("layernorm", before_layer,
-        epsilon, center, scale)."""
-        out, drops, norms, sites = [], [], [], []
-        in_front = 0
+        """(Dense layers, the other layers) of a readout stack.  The second list holds the stack's
+        Dropout and LayerNormalization layers in the architecture's order, the one record of where
+        each stands: ("dropout", before_layer, rate, seed) or ("layernorm", before_layer, epsilon,
+        center, scale, name), before_layer = the Dense layer it precedes, len(layers) after the last
+        one.  A Dropout is tf.nn.dropout in training and the identity otherwise; rate 0 is no layer, as
+        TF returns x."""
+        out, extra = [], []
         for l in arch.layers:
             if l.type == "Dropout":
                 prm = dict(l.parameters)
@@ -211,9 +205,7 @@ class MPPlan:
                 if not 0.0 <= rate < 1.0:   # tf.nn.dropout raises ValueError
                     raise ValueError("Dropout rate must be in [0, 1), got %r" % rate)
                 if rate > 0.0:
-                    drops.append((len(out), rate, int(prm.get("seed") or 0) & 0xFFFFFFFFFFFFFFFF))
-                    sites.append(("dropout",) + drops[-1])
-                    in_front += 1
+                    extra.append(("dropout", len(out), rate, int(prm.get("seed") or 0) & 0xFFFFFFFFFFFFFFFF))
                 continue
             if l.type == "LayerNormalization":
                 prm = dict(l.parameters)
@@ -229,10 +221,8 @@ class MPPlan:
                 eps = float(prm.get("epsilon", 1e-3))
                 if not eps >= 0.0:   # Keras raises ValueError
                     raise ValueError("LayerNormalization epsilon must be >= 0, got %r" % eps)
-                norms.append((len(out), in_front, eps, bool(prm.get("center", True)), bool(prm.get("scale", True)),
+                extra.append(("layernorm", len(out), eps, bool(prm.get("center", True)), bool(prm.get("scale", True)),
                               prm.get("name")))
-                sites.append(("layernorm", len(out), eps, int(norms[-1][3]), int(norms[-1][4])))
-                in_front += 1
                 continue
             if l.type != "Dense":
                 raise UnsupportedModel("%s layer type %s is not lowered (Dense, Dropout and LayerNormalization only)"
@@ -246,12 +236,10 @@ class MPPlan:
                 raise UnsupportedModel("Dense options %s are not lowered" % sorted(set(prm) - known))
             out.append((prm.get("name"), int(prm["units"]), _lib.ACT[act], int(bool(prm.get("use_bias", True))),
                         float(prm.get("kernel_regularizer", 0.0) or 0.0)))
-            in_front = 0
-        if drops and not out:
-            raise ValueError("%s network has a Dropout but no Dense layer" % what)
-        if norms and not out:
-            raise ValueError("%s network has a LayerNormalization but no Dense layer" % what)
-        return out, drops, norms, sites
+        for kind, label in (("dropout", "Dropout"), ("layernorm", "LayerNormalization")):
+            if not out and any(e[0] == kind for e in extra):
+                raise ValueError("%s network has a %s but no Dense layer" % (what, label))
+        return out, extra
 
     def _lower_readout(self, mi):
         """The readout list (GM:605-655) up to the first predict, which returns (GM:629); names
@@ -281,7 +269,7 @@ class MPPlan:
             first = self.ro_spaces[ids[0]]
             d = {"type": op.type, "inputs": ids, "mode": 0, "adj": -1, "layers": [], "counter": counter}
             if op.type == "neural_network":
-                d["layers"], d["dropout"], d["layernorm"], d["sites"] = self._dense_layers(op.architecture, "readout")
+                d["layers"], d["extra"] = self._dense_layers(op.architecture, "readout")
                 d["in_width"] = sum(self.ro_widths[i] for i in ids)
                 add(op.output_name, d["layers"][-1][1], first)
             elif op.type == "pooling":
@@ -313,43 +301,44 @@ class MPPlan:
         self.predict_counter, op = pred
         self.readout_label = op.label
         self.readout_inputs = [resolve(n) for n in op.input]
-        self.dense, self.dropout, self.layernorm, self.sites = self._dense_layers(op.architecture, "readout")
+        self.dense, self.extra = self._dense_layers(op.architecture, "readout")
 
     @property
     def predict_space(self):
         return self.ro_spaces[self.readout_inputs[0]]
 
+    def _stacks(self):
+        """[(stack, input width, Dense layers, the other layers)]: the readout operations in order (only
+        a neural_network has layers), then predict (stack -1)."""
+        out = [(k, op.get("in_width", 0), op["layers"], op.get("extra", [])) for k, op in enumerate(self.readout_ops)]
+        return out + [(-1, sum(self.ro_widths[i] for i in self.readout_inputs), self.dense, self.extra)]
+
+    def _sites(self, kind):
+        """[(stack, fan, Dense layers, order, record)] of the layers of one kind in the engine's site
+        order: stacks as _stacks, and within a stack as listed, which is by position.  order = the
+        layer's place among the layers of both kinds in front of the same Dense layer."""
+        return [(stack, fan, layers, sum(f[1] == e[1] for f in extra[:i]), e)
+                for stack, fan, layers, extra in self._stacks() for i, e in enumerate(extra) if e[0] == kind]
+
     def dropout_sites(self):
         """[(site, stack, before_layer, rate, seed)] in site order: readout operations in order, then
         predict (stack -1), by position within a stack (ign_plan_add_dropout)."""
-        recs = [(k, d) for k, op in enumerate(self.readout_ops) for d in sorted(op.get("dropout", []), key=lambda d: d[0])]
-        recs += [(-1, d) for d in sorted(self.dropout, key=lambda d: d[0])]
-        return [(site, stack) + tuple(d) for site, (stack, d) in enumerate(recs)]
-
-    def _stacks(self):
-        """[(stack, input width, Dense layers, Dropout records, LayerNormalization records)]: the readout
-        neural_network operations in order, then predict (stack -1)."""
-        out = [(k, op.get("in_width", 0), op["layers"], op.get("dropout", []), op.get("layernorm", []))
-               for k, op in enumerate(self.readout_ops) if op["type"] == "neural_network"]
-        return out + [(-1, sum(self.ro_widths[i] for i in self.readout_inputs), self.dense, self.dropout, self.layernorm)]
+        return [(site, r[0]) + r[4][1:] for site, r in enumerate(self._sites("dropout"))]
 
     def layernorm_sites(self):
         """[(site, stack, before_layer, order, epsilon, center, scale, units, name)] in the engine's order
         (ign_plan_add_layernorm): stacks as dropout_sites, by position within a stack.  units = the
         width it normalises: the input width of the Dense layer it precedes, or the stack's output width."""
-        recs = []
-        for stack, fan, layers, _, norms in self._stacks():
-            for before, order, eps, center, scale, name in sorted(norms, key=lambda n: n[0]):
-                units = layers[before - 1][1] if before else fan
-                recs.append((len(recs), stack, before, order, eps, center, scale, units, name))
-        return recs
+        return [(site, stack, before, order, eps, center, scale, layers[before - 1][1] if before else fan, name)
+                for site, (stack, fan, layers, order, (_, before, eps, center, scale, name))
+                in enumerate(self._sites("layernorm"))]
 
     def stack_sites(self):
         """The ign_plan_add_dropout / ign_plan_add_layernorm calls that build the plan's layers, each
         stack's in the architecture's order: [("dropout", stack, before, rate, seed) |
         ("layernorm", stack, before, epsilon, center, scale)]."""
-        calls = [(c[0], k) + c[1:] for k, op in enumerate(self.readout_ops) for c in op.get("sites", [])]
-        return calls + [(c[0], -1) + c[1:] for c in self.sites]
+        return [(e[0], stack) + (e[1:] if e[0] == "dropout" else (e[1], e[2], int(e[3]), int(e[4])))
+                for stack, _, _, extra in self._stacks() for e in extra]
 
     # ------------------------------------------------------------------ C structures
     def to_desc(self):
@@ -412,13 +401,13 @@ class MPPlan:
         if self.attention_dim:
             F = self.attention_dim
             specs += [("attention/kernel1", (F, F)), ("attention/kernel2", (F, F)), ("attention/attn_kernel", (2 * F, 1))]
-        def stack(counter, fan_in, layers, norms):
+        def stack(counter, fan_in, layers, extra):
             # a LayerNormalization's gamma / beta stand in front of the Dense layer it precedes
             for li in range(len(layers) + 1):
-                for before, _, _, center, scale, name in norms:
-                    if before == li:
-                        pre = "readout_model_%d/%s" % (counter, name)
-                        specs.extend([(pre + "/gamma", (fan_in,))] * scale + [(pre + "/beta", (fan_in,))] * center)
+                for e in extra:
+                    if e[0] == "layernorm" and e[1] == li:
+                        pre = "readout_model_%d/%s" % (counter, e[5])
+                        specs.extend([(pre + "/gamma", (fan_in,))] * e[4] + [(pre + "/beta", (fan_in,))] * e[3])
                 if li == len(layers):
                     break
                 name, units, _, use_bias, _ = layers[li]
@@ -429,8 +418,8 @@ class MPPlan:
                 fan_in = units
 
         for op in self.readout_ops:
-            stack(op["counter"], op.get("in_width", 0), op["layers"], op.get("layernorm", []))
-        stack(self.predict_counter, sum(self.ro_widths[i] for i in self.readout_inputs), self.dense, self.layernorm)
+            stack(op["counter"], op.get("in_width", 0), op["layers"], op.get("extra", []))
+        stack(self.predict_counter, sum(self.ro_widths[i] for i in self.readout_inputs), self.dense, self.extra)
         return specs
 
     def init_params(self, seed: int = 0, bias_scale: float = 0.0) -> dict:

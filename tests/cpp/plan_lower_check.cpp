@@ -3,7 +3,9 @@
 // the first two against tables worked out by hand from the 64-float alignment rule; (b) for every plan
 // and readout variant, the invariants that tie the packed layout to its pack list; (c) every refusal
 // of the lowering a C description can reach, by code and text; (d) train_seq_variant over its
-// switches.  tests/test_plan_lower.py builds this with g++, plain and under
+// switches; (e) the Dropout and LayerNormalization layers of the readout stacks: the site arrays, every
+// stack's seq and the gamma / beta tensors after adds in and out of stack order, and the adds'
+// refusals.  tests/test_plan_lower.py builds this with g++, plain and under
 // -fsanitize=address,undefined, and runs it; a non-zero exit is a failure.
 #include "lower_check.h"
 
@@ -452,12 +454,268 @@ static void seq_variants() {
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// (e) Dropout and LayerNormalization layers: add_dropout / add_layernorm keep drops and norms in site
+// order and every stack's seq in the architecture's order
+// RouteNet's MPs; readout op 0: a network 64 -> 16 -> 8 on the path states beside themselves (two
+// inputs, concatenated); predict 8 -> 12 -> 4 -> 1 on its output
+static PD stacks() {
+  PD d = routenet();
+  d.ops = {{IGN_RO_NEURAL_NETWORK, {1, 1}, 0, -1, {{16, IGN_ACT_RELU, 1, 0.f}, {8, IGN_ACT_LINEAR, 0, 0.f}}}};
+  d.ro_in = {2};
+  d.dense = {{12, IGN_ACT_RELU, 1, 0.f}, {4, IGN_ACT_TANH, 0, 0.f}, {1, IGN_ACT_LINEAR, 1, 0.f}};
+  return d;
+}
+// the fused readout behind a one-layer network on the path states
+static PD fused_behind_op() {
+  PD d = routenet();
+  d.ops = {{IGN_RO_NEURAL_NETWORK, {1}, 0, -1, {{32, IGN_ACT_RELU, 1, 0.f}}}};
+  d.ro_in = {2};
+  return d;
+}
+
+// what must hold after every add
+static void site_invariants(const PlanModel& m, int line) {
+  std::vector<int> drop_seen(m.drops.size(), 0), norm_seen(m.norms.size(), 0);
+  for (int stack = -1; stack < (int)m.ro_ops.size(); ++stack) {
+    const std::vector<DenseP>* layers = stack_layers(&m, stack);
+    if (!layers) {
+      CHECK(!stack_seq(&m, stack) && m.ro_ops[stack].seq.empty());
+      continue;
+    }
+    const std::vector<StackLayer>& seq = *stack_seq(&m, stack);
+    const int L = (int)layers->size();
+    int l = 0;   // the Dense layer the next entries stand in front of
+    std::vector<std::pair<int, int64_t>> want;   // the stack's tensors: (kind, offset)
+    for (const StackLayer& e : seq) {
+      const int units = l < L ? (*layers)[l].in : layers->back().out;
+      if (e.kind == SL_DENSE) {
+        CHECK(e.idx == l && l < L);   // each Dense index once, ascending
+        if (l >= L) return;
+        want.push_back({stack < 0 ? 3 : 11, (*layers)[l].off_w});
+        if ((*layers)[l].use_bias) want.push_back({stack < 0 ? 4 : 12, (*layers)[l].off_b});
+        ++l;
+      } else if (e.kind == SL_DROPOUT) {
+        CHECK(e.idx >= 0 && e.idx < (int)m.drops.size());
+        if (e.idx < 0 || e.idx >= (int)m.drops.size()) return;
+        const DropSite& s = m.drops[e.idx];
+        ++drop_seen[e.idx];
+        CHECK(s.stack == stack && s.before == l && s.units == units && s.rate > 0.f && s.scale == 1.f / (1.f - s.rate));
+      } else {
+        CHECK(e.kind == SL_LAYERNORM && e.idx >= 0 && e.idx < (int)m.norms.size());
+        if (e.kind != SL_LAYERNORM || e.idx < 0 || e.idx >= (int)m.norms.size()) return;
+        const NormSite& s = m.norms[e.idx];
+        ++norm_seen[e.idx];
+        CHECK(s.stack == stack && s.before == l && s.units == units);
+        CHECK((s.off_gamma >= 0) == s.scale && (s.off_beta >= 0) == s.center);
+        if (s.scale) want.push_back({13, s.off_gamma});
+        if (s.center) want.push_back({14, s.off_beta});
+      }
+    }
+    CHECK(l == L);
+    // gamma / beta directly in front of the kernel of the Dense layer they precede, in seq order
+    size_t t = 0;
+    while (t < m.tensors.size() && m.tensors[t].offset != want[0].second) ++t;
+    CHECK(t + want.size() <= m.tensors.size());
+    for (size_t i = 0; i < want.size() && t + i < m.tensors.size(); ++i) {
+      const Tensor& x = m.tensors[t + i];
+      CHECK(x.kind == want[i].first && x.offset == want[i].second);
+      if (x.kind == 13 || x.kind == 14) CHECK(x.rows == 1 && x.cols == m.norms[x.owner].units && (x.kind == 13 ? m.norms[x.owner].off_gamma : m.norms[x.owner].off_beta) == x.offset);
+    }
+  }
+  // every site in exactly one seq (of the stack it names: checked above), the arrays in site order
+  for (int n : drop_seen) CHECK(n == 1);
+  for (int n : norm_seen) CHECK(n == 1);
+  auto key = [](int stack, int before) { return std::make_pair(stack < 0 ? 1 << 30 : stack, before); };
+  for (size_t i = 1; i < m.drops.size(); ++i) CHECK(key(m.drops[i - 1].stack, m.drops[i - 1].before) <= key(m.drops[i].stack, m.drops[i].before));
+  for (size_t i = 1; i < m.norms.size(); ++i) CHECK(key(m.norms[i - 1].stack, m.norms[i - 1].before) <= key(m.norms[i].stack, m.norms[i].before));
+  if (g_bad) printf("  (site_invariants called from line %d)\n", line);
+}
+// a Dropout changes neither layout; a LayerNormalization on a readout operation leaves fused_readout alone
+static bool same_layouts(const PlanModel& a, const PlanModel& b) {
+  bool same = a.n_params == b.n_params && a.n_packed == b.n_packed && a.tensors.size() == b.tensors.size() &&
+              a.packs.size() == b.packs.size() && a.fused_readout == b.fused_readout;
+  for (size_t i = 0; same && i < a.tensors.size(); ++i) {
+    const Tensor &x = a.tensors[i], &y = b.tensors[i];
+    same = x.kind == y.kind && x.owner == y.owner && x.offset == y.offset && x.rows == y.rows && x.cols == y.cols;
+  }
+  for (size_t i = 0; same && i < a.packs.size(); ++i) {
+    const PackJob &x = a.packs[i], &y = b.packs[i];
+    same = x.kind == y.kind && x.src[0] == y.src[0] && x.src[1] == y.src[1] && x.src[2] == y.src[2] && x.dst == y.dst &&
+           x.a == y.a && x.b == y.b && x.c == y.c && x.floats == y.floats;
+  }
+  return same;
+}
+static std::vector<int> kinds(const std::vector<StackLayer>& seq) {
+  std::vector<int> k;
+  for (auto& e : seq) k.push_back(e.kind);
+  return k;
+}
+#define DROPOUT(m, stack, before, rate, seed)                  \
+  do {                                                         \
+    const PlanModel was_ = m;                                  \
+    OK(add_dropout(&m, stack, before, rate, seed));            \
+    CHECK(same_layouts(was_, m));                              \
+    site_invariants(m, __LINE__);                              \
+  } while (0)
+#define LAYERNORM(m, stack, before, eps, center, scale)              \
+  do {                                                               \
+    OK(add_layernorm(&m, stack, before, eps, center, scale));        \
+    site_invariants(m, __LINE__);                                    \
+  } while (0)
+
+static void sites_in_call_order() {
+  g_case = "sites: call order";
+  const int D = SL_DENSE, DO = SL_DROPOUT, LN = SL_LAYERNORM;
+  PD d = stacks();
+  PlanModel m;
+  OK(lower(d, &m));
+  site_invariants(m, __LINE__);
+  EQ(kinds(m.seq), D, D, D);
+  EQ(kinds(m.ro_ops[0].seq), D, D);
+  LAYERNORM(m, -1, 1, 1e-3f, 1, 1);
+  DROPOUT(m, -1, 1, 0.5f, 3);
+  EQ(kinds(m.seq), D, LN, DO, D, D);
+  CHECK(site_order(&m, -1, SL_LAYERNORM, 0) == 0 && site_order(&m, -1, SL_DROPOUT, 0) == 1);
+  PlanModel r;
+  OK(lower(d, &r));
+  DROPOUT(r, -1, 1, 0.5f, 3);
+  LAYERNORM(r, -1, 1, 1e-3f, 1, 1);
+  EQ(kinds(r.seq), D, DO, LN, D, D);
+  CHECK(site_order(&r, -1, SL_LAYERNORM, 0) == 1 && site_order(&r, -1, SL_DROPOUT, 0) == 0);
+  // the layouts do not depend on where the Dropout stands
+  CHECK(same_layouts(m, r) && m.norms[0].units == 12 && m.drops[0].units == 12);
+}
+
+static void sites_out_of_stack_order() {
+  g_case = "sites: out of stack order";
+  const int D = SL_DENSE, DO = SL_DROPOUT, LN = SL_LAYERNORM;
+  PD d = stacks();
+  PlanModel m;
+  OK(lower(d, &m));
+  // predict first, then readout op 0, then predict again in front of an earlier layer
+  DROPOUT(m, -1, 2, 0.25f, 7);
+  LAYERNORM(m, -1, 2, 1e-3f, 1, 0);
+  DROPOUT(m, 0, 1, 0.5f, 9);
+  LAYERNORM(m, 0, 0, 1e-5f, 0, 1);   // in front of layer 0 of the two-input operation: the concatenated width
+  DROPOUT(m, -1, 0, 0.125f, 11);
+  LAYERNORM(m, -1, 1, 1e-2f, 1, 1);
+  CHECK(m.drops.size() == 3 && m.norms.size() == 3);
+  if (m.drops.size() != 3 || m.norms.size() != 3) return;
+  // today's site order: readout operations in order, then predict; by position
+  CHECK(m.drops[0].stack == 0 && m.drops[0].before == 1 && m.drops[0].seed == 9 && m.drops[0].rate == 0.5f && m.drops[0].units == 16);
+  CHECK(m.drops[1].stack == -1 && m.drops[1].before == 0 && m.drops[1].seed == 11 && m.drops[1].units == 8);
+  CHECK(m.drops[2].stack == -1 && m.drops[2].before == 2 && m.drops[2].seed == 7 && m.drops[2].units == 4);
+  CHECK(m.norms[0].stack == 0 && m.norms[0].before == 0 && m.norms[0].epsilon == 1e-5f && m.norms[0].units == 64 && !m.norms[0].center);
+  CHECK(m.norms[1].stack == -1 && m.norms[1].before == 1 && m.norms[1].epsilon == 1e-2f && m.norms[1].units == 12);
+  CHECK(m.norms[2].stack == -1 && m.norms[2].before == 2 && !m.norms[2].scale && m.norms[2].units == 4);
+  EQ(kinds(m.ro_ops[0].seq), LN, D, DO, D);
+  EQ(kinds(m.seq), DO, D, LN, D, DO, LN, D);
+  if (m.seq.size() != 7 || m.ro_ops[0].seq.size() != 4) return;
+  CHECK(m.ro_ops[0].seq[0].idx == 0 && m.ro_ops[0].seq[2].idx == 0);
+  CHECK(m.seq[0].idx == 1 && m.seq[2].idx == 1 && m.seq[4].idx == 2 && m.seq[5].idx == 2);
+  // a second layer in front of the same Dense layer goes behind the first, in both lists
+  DROPOUT(m, 0, 1, 0.75f, 13);
+  CHECK(m.drops.size() == 4 && m.drops[1].seed == 13 && m.drops[1].stack == 0);
+  EQ(kinds(m.ro_ops[0].seq), LN, D, DO, DO, D);
+  CHECK(m.ro_ops[0].seq[2].idx == 0 && m.ro_ops[0].seq[3].idx == 1 && m.seq[0].idx == 2 && m.seq[4].idx == 3);
+  // the tensors, by hand: readout op 0 is gamma [1][64] (no beta), W [64][16], b, W [16][8]; predict is
+  // W [8][12], b, gamma and beta [1][12], W [12][4], beta [1][4] (no gamma), W [4][1], b
+  const int64_t base = 2 * 6336;
+  tensors_are(m, {{0, 0, 0, 32, 96}, {1, 0, 3072, 32, 96}, {2, 0, 6144, 2, 96},
+                  {0, 1, 6336, 32, 96}, {1, 1, 9408, 32, 96}, {2, 1, 12480, 2, 96},
+                  {13, 0, base, 1, 64}, {11, 0, base + 64, 64, 16}, {12, 0, base + 1088, 1, 16}, {11, 1, base + 1152, 16, 8},
+                  {3, 0, base + 1280, 8, 12}, {4, 0, base + 1408, 1, 12}, {13, 1, base + 1472, 1, 12}, {14, 1, base + 1536, 1, 12},
+                  {3, 1, base + 1600, 12, 4}, {14, 2, base + 1664, 1, 4}, {3, 2, base + 1728, 4, 1}, {4, 2, base + 1792, 1, 1}});
+  CHECK(m.n_params == base + 1856);
+}
+
+static void sites_after_the_last_layer() {
+  g_case = "sites: after the last layer";
+  const int D = SL_DENSE, DO = SL_DROPOUT, LN = SL_LAYERNORM;
+  PD d = stacks();
+  PlanModel m;
+  OK(lower(d, &m));
+  LAYERNORM(m, -1, 3, 1e-3f, 1, 1);
+  DROPOUT(m, -1, 3, 0.5f, 1);
+  DROPOUT(m, 0, 2, 0.5f, 2);
+  LAYERNORM(m, 0, 2, 1e-3f, 1, 1);
+  EQ(kinds(m.seq), D, D, D, LN, DO);
+  EQ(kinds(m.ro_ops[0].seq), D, D, DO, LN);
+  CHECK(m.norms.size() == 2 && m.drops.size() == 2);
+  if (m.norms.size() != 2 || m.drops.size() != 2) return;
+  // the stack's output width
+  CHECK(m.norms[0].stack == 0 && m.norms[0].units == 8 && m.drops[0].stack == 0 && m.drops[0].units == 8);
+  CHECK(m.norms[1].stack == -1 && m.norms[1].units == 1 && m.drops[1].stack == -1 && m.drops[1].units == 1);
+  // its gamma / beta close the stack's tensors
+  const Tensor& last = m.tensors.back();
+  CHECK(last.kind == 14 && last.owner == 1 && last.offset == m.norms[1].off_beta);
+}
+
+static void sites_and_the_fused_readout() {
+  g_case = "sites: fused readout";
+  PD d = fused_behind_op();
+  PlanModel m;
+  OK(lower(d, &m));
+  CHECK(m.fused_readout);
+  DROPOUT(m, -1, 1, 0.5f, 0);   // (same_layouts: fused_readout stays)
+  DROPOUT(m, 0, 0, 0.5f, 0);
+  const PlanModel was = m;
+  LAYERNORM(m, 0, 1, 1e-3f, 1, 1);   // on a readout operation: left alone
+  CHECK(m.fused_readout && m.n_params == was.n_params + 128 && m.tensors.size() == was.tensors.size() + 2);
+  LAYERNORM(m, -1, 0, 1e-3f, 1, 1);   // on predict: cleared, and the fused fp16 blocks leave the packed layout
+  CHECK(!m.fused_readout && m.dense[1].pk_h == -1 && m.n_packed < was.n_packed);
+}
+
+static void site_refusals() {
+  g_case = "sites: refusals";
+  PD d = attention();   // op 0: a network of two layers, op 1: pooling; predict: two layers
+  PlanModel m;
+  OK(lower(d, &m));
+  const PlanModel was = m;
+#define REFUSES(e, text)                 \
+  do {                                   \
+    FAILS(e, IGN_ERR_INVALID, text);     \
+    CHECK(strcmp(g_msg, text) == 0);     \
+  } while (0)
+  REFUSES(add_dropout(&m, 1, 0, 0.5f, 0),
+          "ign_plan_add_dropout: stack 1 is neither -1 (predict) nor a readout neural_network operation");
+  REFUSES(add_layernorm(&m, 1, 0, 1e-3f, 1, 1),
+          "ign_plan_add_layernorm: stack 1 is neither -1 (predict) nor a readout neural_network operation");
+  REFUSES(add_dropout(&m, 2, 0, 0.5f, 0),
+          "ign_plan_add_dropout: stack 2 is neither -1 (predict) nor a readout neural_network operation");
+  REFUSES(add_layernorm(&m, -2, 0, 1e-3f, 1, 1),
+          "ign_plan_add_layernorm: stack -2 is neither -1 (predict) nor a readout neural_network operation");
+  REFUSES(add_dropout(&m, -1, -1, 0.5f, 0), "ign_plan_add_dropout: before_layer -1 outside 0..2");
+  REFUSES(add_dropout(&m, 0, 3, 0.5f, 0), "ign_plan_add_dropout: before_layer 3 outside 0..2");
+  REFUSES(add_layernorm(&m, 0, -1, 1e-3f, 1, 1), "ign_plan_add_layernorm: before_layer -1 outside 0..2");
+  REFUSES(add_layernorm(&m, -1, 3, 1e-3f, 1, 1), "ign_plan_add_layernorm: before_layer 3 outside 0..2");
+  REFUSES(add_dropout(&m, -1, 0, 1.0f, 0), "Dropout rate must be in [0, 1), got 1");
+  REFUSES(add_dropout(&m, -1, 0, -0.1f, 0), "Dropout rate must be in [0, 1), got -0.1");
+  REFUSES(add_layernorm(&m, -1, 0, -1.f, 1, 1), "LayerNormalization epsilon must be >= 0, got -1");
+  // the checks come in that order: a bad stack is named before a bad rate
+  REFUSES(add_dropout(&m, 1, 9, 2.f, 0),
+          "ign_plan_add_dropout: stack 1 is neither -1 (predict) nor a readout neural_network operation");
+#undef REFUSES
+  // nothing was added by any of them, and a rate of 0 is no layer
+  OK(add_dropout(&m, -1, 0, 0.f, 5));
+  OK(add_dropout(&m, 0, 2, 0.f, 5));
+  CHECK(m.drops.empty() && m.norms.empty() && m.seq.size() == 2 && m.ro_ops[0].seq.size() == 2 && m.ro_ops[1].seq.empty());
+  CHECK(same_layouts(was, m));
+  site_invariants(m, __LINE__);
+}
+
 int main() {
   routenet_tables();
   qsize_tables();
   layout_cases();
   refusals();
   seq_variants();
+  sites_in_call_order();
+  sites_out_of_stack_order();
+  sites_after_the_last_layer();
+  sites_and_the_fused_readout();
+  site_refusals();
   if (g_bad) printf("%d check(s) failed\n", g_bad);
   else printf("plan_lower_check: ok\n");
   return g_bad ? 1 : 0;

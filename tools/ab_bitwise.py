@@ -4,9 +4,10 @@
 fixed seeded vector).
     python tools/ab_bitwise.py base new [--graphs 512] [--model routenet] [--topology synth50] [--train]
 --cases runs the models of the tests' case modules instead (predict_cases, test_gpu_dropout's GRAD_CASES
-with its mask stream, readout_cases, test_gpu_training's message-network parameter sets), all of them in
-one process per library, and compares per case the training forward's predictions and the flat gradient
-of one backward; for the readout-operation and message-network cases the inference forward too.
+with its mask stream, layernorm_cases' GRAD_CASES, readout_cases, test_gpu_training's message-network
+parameter sets), all of them in one process per library, and compares per case the training forward's
+predictions and the flat gradient of one backward; for the LayerNormalization, readout-operation and
+message-network cases the inference forward too.
 (Against a parent commit: tools/build_ab.sh base in a checkout of it, its lib_base.so copied to this ab/.)
     python tools/ab_bitwise.py base new --cases"""
 import argparse
@@ -49,7 +50,8 @@ def cases():
     from ignnition_amd import model_examples, synthetic, workloads
     from ignnition_amd.engine import MPPlan
     from ignnition_amd.json_operations import Model_information
-    from tests import dropout_cases as dc, predict_cases as pc, test_gpu_dropout as td, test_gpu_training as tt
+    from tests import dropout_cases as dc, layernorm_cases as lc, predict_cases as pc
+    from tests import test_gpu_dropout as td, test_gpu_layernorm as tl, test_gpu_training as tt
     from tests.readout_cases import READOUT_CASES
     for c in sorted(pc.PREDICT_CASES):
         desc, dims, _, graphs, _, prm = pc.predict_inputs(c)
@@ -58,6 +60,10 @@ def cases():
         desc = td.GRAD_CASES[c]()
         dims, _, graphs, _, prm = dc.inputs(desc)
         yield "dropout/" + c, desc, dims, graphs, prm, (td.SEED, td.STEP), False
+    for c in sorted(lc.GRAD_CASES):   # (the mask stream where the case has a Dropout)
+        desc = lc.GRAD_CASES[c]()
+        dims, plan, graphs, _, prm = lc.inputs(desc)
+        yield "layernorm/" + c, desc, dims, graphs, prm, (tl.SEED, tl.STEP) if plan.dropout_sites() else None, True
     for c in sorted(READOUT_CASES):   # test_gradients_readout_operations' batch
         ops, pin, nets = READOUT_CASES[c]
         desc = model_examples.routenet_readout(ops, pin, nets, iterations=3)
