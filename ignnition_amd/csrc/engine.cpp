@@ -1,5 +1,7 @@
 // engine.cpp — C ABI (include/ignmp.h), the plan's switches and repack (its lowering: plan_lower.cpp),
-// native batch builder, forward driver.
+// native batch builder, forward driver: which states an MP instance reads and flips, the resident
+// launch, capture and timing statistics.  The MP instance itself is mp_step.cpp's, predict's head
+// readout.cpp's, both shared with the training forward (train.cpp).
 //
 // Reference behaviour restated here (generate_model.py = GM, auxilary_classes.py = AUX):
 //  * hidden-state init per entity                                  GM:396-400, AUX:128-160
@@ -38,6 +40,7 @@
 #include "engine_internal.h"
 #include "batch_lower.h"
 #include "dense_stack.h"
+#include "mp_step.h"
 #include "train_kernels.h"
 
 namespace ign {
@@ -64,6 +67,14 @@ int set_device(int dev) {
   if (dev < 0 || dev >= n) return fail(IGN_ERR_DEVICE, "device %d out of range (%d devices)", dev, n);
   HIP_TRY(hipSetDevice(dev));
   return IGN_OK;
+}
+
+int check_pb(ign_plan* p, ign_batch* b, bool train) {
+  if (!p || !b) return fail(IGN_ERR_INVALID, "null argument");
+  if (b->plan != p) return fail(IGN_ERR_INVALID, "batch was created for another plan");
+  if (train && !b->train) return fail(IGN_ERR_INVALID, "training not enabled on this batch (ign_batch_enable_training)");
+  if (!p->params_set) return fail(IGN_ERR_INVALID, "parameters not set (ign_plan_set_params)");
+  return set_device(p->device);
 }
 
 int ensure_device(ign_plan* p) {
@@ -375,9 +386,6 @@ int ign_plan_set_params(ign_plan* p, const float* params, int32_t on_device) {
 }
 
 namespace {
-// timed launches record event pairs into a ring on the plan; they are resolved lazily
-constexpr int kMaxPendingEvents = 1 << 14;
-int flush_timing(ign_plan* p);
 void drop_timing(ign_plan* p);
 }  // namespace
 
@@ -741,69 +749,6 @@ int ign_batch_predictions(ign_batch* b, const float** ptr) {
 }
 
 // ---------------------------------------------------------------------------------------------
-namespace {
-
-struct Timer {
-  ign_plan* p;
-  bool on = false;
-  void begin(int kind, double flops, double bytes, double mfma_bf16 = 0, double mfma_f32 = 0) {
-    on = p->timing && ((p->timing_kinds >> kind) & 1u);
-    if (!on) return;
-    if (p->ev_slot >= kMaxPendingEvents) flush_timing(p);
-    const int slot = p->ev_slot;
-    size_t need = 2 * (slot + 1);
-    while (p->ev.size() < need) {
-      hipEvent_t e;
-      hipEventCreate(&e);
-      p->ev.push_back(e);
-    }
-    if ((int)p->ev_kind.size() <= slot) {
-      p->ev_kind.resize(slot + 1);
-      p->ev_cost.resize(slot + 1);
-    }
-    p->ev_kind[slot] = kind;
-    p->ev_cost[slot] = EvCost{flops, bytes, mfma_bf16, mfma_f32};
-    hipEventRecord(p->ev[2 * slot], p->stream);
-  }
-  void end() {
-    if (!on) return;
-    hipEventRecord(p->ev[2 * p->ev_slot + 1], p->stream);
-    ++p->ev_slot;
-  }
-};
-
-// message network of one source: per-edge [inputs...] then the Dense stack into d_msg_layer[s]
-int message_net_fwd(ign_plan* p, const MsgNN& nn, const MPB& mb, int s, const float* src_state,
-                    const float* dst_state, hipStream_t st) {
-  MsgGatherArgs g{};
-  g.out = mb.d_msg_in[s];
-  g.n = mb.n_edges[s];
-  g.ld = nn.din_pad;
-  g.nparts = (int)nn.inputs.size();
-  int col = 0;
-  for (int q = 0; q < g.nparts; ++q) {
-    const int kind = nn.inputs[q];
-    g.col[q] = col;
-    g.width[q] = nn.widths[q];
-    if (kind == IGN_MSG_HS_SOURCE) { g.base[q] = src_state; g.rows[q] = mb.d_edge_src[s]; }
-    else if (kind == IGN_MSG_HS_DEST) { g.base[q] = dst_state; g.rows[q] = mb.d_edge_dst[s]; }
-    else { g.base[q] = mb.d_edge_params[s]; g.rows[q] = nullptr; }
-    col += g.width[q];
-  }
-  HIP_TRY(launch_msg_gather(g, st));
-  return dense_stack_forward(p, {nn.layers.data(), (int)nn.layers.size(), mb.n_edges[s], mb.d_msg_in[s], nn.din_pad,
-                                 mb.d_msg_layer[s].data(), mb.d_msg_layer[s].back()}, st);
-}
-
-int check_pb(ign_plan* p, ign_batch* b) {
-  if (!p || !b) return fail(IGN_ERR_INVALID, "null argument");
-  if (b->plan != p) return fail(IGN_ERR_INVALID, "batch was created for another plan");
-  if (!p->params_set) return fail(IGN_ERR_INVALID, "parameters not set (ign_plan_set_params)");
-  return set_device(p->device);
-}
-
-}  // namespace
-
 int ign_forward_begin(ign_plan* p, ign_batch* b) {
   int rc = check_pb(p, b);
   if (rc) return rc;
@@ -818,209 +763,27 @@ int ign_forward_begin(ign_plan* p, ign_batch* b) {
   return IGN_OK;
 }
 
-// f32 MFMA FLOPs of a sum update's GRU step (sum_gru_kernel / sum_gru_lds: 3 gates x H/16 unit tiles x
-// (DIN + H)/4 k-steps per 16-row tile)
-static double sum_mfma_f32(int64_t n, int din, int H) {
-  return (double)((n + 15) / 16) * 3 * (H / 16) * ((din + H) / 4) * kMfmaF32Flops;
-}
-
-// The ordered MP whose input projection sum MP mi can produce in its epilogue (sum_gru_g32), or -1,
-// and in *slot the source of that MP whose table rows it fills: the next MP (cyclically, within this
-// forward) that touches mi's destination entity reads it as exactly one of its sources, with the
-// projection sum_gru_g32 forms (32 -> 3 x 32, no message network, no feature concat), and every row
-// of the entity is one of mi's destinations (no halo rows).  A multi-source reader (Q-size's
-// {link, node} -> path interleave) gets each source's rows from the sum update of that source.
-static int fused_proj_target(const ign_plan* p, const ign_batch* b, int mi, int* slot) {
-  const MPP& mp = p->mps[mi];
-  const int e = mp.dst, n = (int)p->mps.size();
-  if (mp.sorted || mp.aggr != IGN_AGGR_SUM || mp.feature_concat || mp.din != 32 || p->cells[mp.cell].H != 32 ||
-      b->halo[e] > 0)
-    return -1;
-  for (const MsgNN& nn : mp.nn)
-    if (!nn.layers.empty()) return -1;
-  for (int k = 1; k <= n; ++k) {
-    const int m2 = (mi + k) % n;
-    if (m2 <= mi && b->fuse_last_iter) return -1;   // the next reader runs in no later iteration
-    const MPP& q = p->mps[m2];
-    int reads = 0, s_e = -1;
-    for (size_t s = 0; s < q.src.size(); ++s)
-      if (q.src[s].entity == e) {
-        ++reads;
-        s_e = (int)s;
-      }
-    if (!reads && q.dst != e) continue;
-    const CellP& qc = p->cells[q.cell];
-    if (m2 == mi || reads != 1 || !q.sorted || q.src.size() > 8 || q.feature_concat || !q.nn[s_e].layers.empty() ||
-        q.din != 32 || qc.H != 32 || qc.pk_wbf < 0)
-      return -1;
-    *slot = s_e;
-    return m2;
-  }
-  return -1;
-}
-
 int ign_forward_mp(ign_plan* p, ign_batch* b, int32_t mi, int32_t part) {
   int rc = check_pb(p, b);
   if (rc) return rc;
   if (mi < 0 || mi >= (int)p->mps.size()) return fail(IGN_ERR_INVALID, "mp index %d out of range", mi);
   if (part < IGN_PART_ALL || part > IGN_PART_BOUNDARY) return fail(IGN_ERR_INVALID, "part %d", part);
-  hipStream_t st = p->stream;
-  Timer tm{p};
   const MPP& mp = p->mps[mi];
-  const MPB& mb = b->mp[mi];
-  const CellP& cp = p->cells[mp.cell];
-  SrcBases sbases{};
-  for (size_t s = 0; s < mp.src.size(); ++s) {
-    int se = mp.src[s].entity;
-    sbases.base[s] = b->d_state[b->cur[se]][se];
-  }
   const int dst = mp.dst;
-  const float* hin = b->d_state[b->cur[dst]][dst];
-  float* hout = b->d_state[1 - b->cur[dst]][dst];
-  for (size_t s = 0; s < mp.src.size(); ++s) {   // message-creation networks (GM:440-475)
-    const MsgNN& nn = mp.nn[s];
-    if (nn.layers.empty()) continue;
-    // the per-edge network reads halo rows: it must run after the exchange, not beside it
-    if (part != IGN_PART_ALL) return fail(IGN_ERR_UNSUPPORTED, "interior/boundary split with a message network");
-    if ((rc = message_net_fwd(p, nn, mb, (int)s, sbases.base[s], hin, st))) return rc;
+  MpStates s;
+  for (size_t k = 0; k < mp.src.size(); ++k) {
+    const int se = mp.src[k].entity;
+    s.src.base[k] = b->d_state[b->cur[se]][se];
   }
-  for (size_t s = 0; s < mp.src.size(); ++s)
-    if (!mp.nn[s].layers.empty()) sbases.base[s] = mb.d_msg_layer[s].back();
-  if (mp.sorted) {
-    if (part != IGN_PART_ALL) return fail(IGN_ERR_UNSUPPORTED, "interior/boundary split is for sum MPs only");
-    const int W3 = 3 * cp.H;
-    // sources whose table rows the previous sum updates' epilogues already formed (bit s)
-    const int projected = b->fuse_ok ? b->proj_ready[mi] : 0;
-    b->proj_ready[mi] = 0;
-    for (size_t s = 0; s < mp.src.size(); ++s) {
-      if (projected >> s & 1) continue;
-      const int64_t rs = mb.src_rows[s];
-      const int sdin_t = mp.feature_concat ? p->ents[mp.src[s].entity].hidden_dim : mp.din;
-      tm.begin(K_PROJECT, 2.0 * rs * mp.din * W3, (double)rs * (4.0 * mp.din + 4.0 * W3), 0,
-               (double)((rs + 15) / 16) * 3 * (cp.H / 16) * (sdin_t / 4) * kMfmaF32Flops);
-      const int sdin = mp.feature_concat ? p->ents[mp.src[s].entity].hidden_dim : mp.din;
-      const float* wp = mp.feature_concat ? p->d_packed + mp.pk_slice[s] : p->d_packed + cp.pk_w;
-      HIP_TRY(launch_project(sbases.base[s], rs, wp, p->d_packed + cp.pk_b, mb.d_table + mb.src_off[s] * W3,
-                             s == 0 ? mb.d_table + mb.zero_row * W3 : nullptr, sdin, cp.H, st));
-      tm.end();
-    }
-    if (mb.n_multi) {
-      tm.begin(K_OTHER, 0, 0);
-      HIP_TRY(launch_multi_sum(mb.d_table, mb.zero_row + 1, mb.n_multi, mb.d_multi_ptr, mb.d_multi_rows, W3,
-                               mb.d_table + mb.zero_row * W3, st));
-      tm.end();
-    }
-    SeqGruArgs a{hin, hout, mb.d_table, mb.d_order, mb.d_len, mb.d_step_ptr, mb.d_step_code,
-                 p->d_packed + cp.pk_u, p->d_packed + cp.pk_b, mb.n_dst, p->xcd_remap};
-    if (cp.pk_ubf >= 0) a.Ubf = p->d_packed + cp.pk_ubf;
-    if (cp.pk_uh >= 0) a.Uh = p->d_packed + cp.pk_uh;
-    a.hdr = mb.d_seq_hdr;
-    {   // MFMAs per wave step: split-fp16 / split-bf16 (variants 6, 7 / 4, 5; H = 32 / 64) passes x
-        // 3 gates x H/16 x H/32 on the 16x16x32 pipe; f32 (seq_gru2) 3 gates x H/16 x H/4
-      const int v = p->seq_variant;
-      const int passes = v == 6 ? 3 : 6;
-      const bool bf = v >= 4 && (cp.H == 32 || cp.H == 64) && a.Ubf;
-      const double ws = (double)mb.wave_steps;
-      tm.begin(K_SEQ, mb.flops, mb.bytes,
-               bf ? ws * passes * 3 * (cp.H / 16) * (cp.H / 32) * kMfmaBf16Flops : 0,
-               bf ? 0 : ws * 3 * (cp.H / 16) * (cp.H / 4) * kMfmaF32Flops);
-    }
-    HIP_TRY(launch_seq_gru(a, cp.H, p->seq_variant, st));
-    tm.end();
-  } else {
-    // destinations [first, first + count) of the order array
-    const int64_t first = part == IGN_PART_BOUNDARY ? mb.n_interior : 0;
-    const int64_t count = part == IGN_PART_INTERIOR ? mb.n_interior
-                        : part == IGN_PART_BOUNDARY ? mb.n_dst - mb.n_interior : mb.n_dst;
-    if (mp.aggr == IGN_AGGR_ATTENTION) {   // AUX:287-343: scores, then the axis-0 softmax weights
-      // a softmax group spans interior and boundary destinations: no split
-      if (part != IGN_PART_ALL) return fail(IGN_ERR_UNSUPPORTED, "interior/boundary split with attention");
-      tm.begin(K_OTHER, 0, 0);
-      if ((rc = attention_weights(p, b, mp, mb, sbases.base, hin, st))) return rc;
-      tm.end();
-    }
-    if (count > 0) {
-      // windowed or segmented aggregation (sum MPs over all destinations): the sum kernel writes x,
-      // then the GRU step reads it through an identity CSR (one message per destination: x itself)
-      const bool pre = (mb.n_win_wg > 0 || mb.sum_seg) && part == IGN_PART_ALL && mp.aggr == IGN_AGGR_SUM;
-      SrcBases xb{};   // windowed: every x from the xsum table (slot 0); segmented: the mixed CSR's slot 1
-      if (mb.sum_seg) {
-        xb = sbases;
-        xb.base[1] = mb.d_xsum;
-      } else {
-        xb.base[0] = mb.d_xsum;
-      }
-      SumGruArgs a{hin, hout, pre ? xb : sbases, pre ? mb.d_order : mb.d_order + first,
-                   pre ? mb.d_id_ptr : mb.d_msg_ptr + first, pre ? mb.d_id_src : mb.d_msg_src,
-                   p->d_packed + cp.pk_w, p->d_packed + cp.pk_u, p->d_packed + cp.pk_b, count, p->xcd_remap};
-      if (mp.aggr == IGN_AGGR_ATTENTION) a.msg_w = mb.d_msg_w;
-      int sv = std::min(p->sum_variant, 7);
-      if (mp.aggr == IGN_AGGR_SUM && cp.pk_wbf >= 0 && cp.pk_ubf >= 0 && mp.din == cp.din && !mp.feature_concat) {
-        a.Wbf = p->d_packed + cp.pk_wbf;
-        a.Ubf = p->d_packed + cp.pk_ubf;
-        if (p->sum_variant == 8 && cp.pk_wh >= 0 && cp.pk_uh >= 0) {   // split-fp16 (DIN = H = 64)
-          a.Wbf = p->d_packed + cp.pk_wh;
-          a.Ubf = p->d_packed + cp.pk_uh;
-          sv = 8;
-        }
-      }
-      if (mp.aggr == IGN_AGGR_CONVOLUTION) {
-        a.conv_kp = p->d_packed + p->pk_conv;
-        a.conv_act = mp.act;
-      }
-      // the next ordered MP's input projection in the epilogue (sum_gru_g32 only)
-      int target = -1, tslot = 0;
-      if (b->fuse_ok && part == IGN_PART_ALL && sv == 7 && a.Wbf && a.Ubf && mp.aggr == IGN_AGGR_SUM &&
-          count == mb.n_dst && mb.n_dst == b->rows[dst])
-        target = fused_proj_target(p, b, mi, &tslot);
-      if (target >= 0) {
-        const CellP& tc = p->cells[p->mps[target].cell];
-        a.proj_out = b->mp[target].d_table + b->mp[target].src_off[tslot] * 3 * tc.H;
-        a.proj_W = p->d_packed + tc.pk_wbf;
-        a.proj_b = p->d_packed + tc.pk_b;
-        a.proj_bias_row = b->mp[target].d_table + b->mp[target].zero_row * 3 * tc.H;
-      }
-      const double frac = mb.n_dst ? (double)count / mb.n_dst : 0.0;
-      // split GRU step (sum_gru_g32 / sum_gru_bf: x6 of x.W and h.U per 16-row tile, sum_gru_h16:
-      // x3) or f32
-      const bool bf = sv >= 7 && a.Wbf && a.Ubf && mp.din == cp.H && (cp.H == 32 || cp.H == 64);
-      const double tiles = (double)((count + 15) / 16);
-      tm.begin(K_SUM, mb.flops * frac, mb.bytes * frac,
-               bf ? tiles * (sv == 8 ? 3 : 6) * 3 * (cp.H / 16) * (mp.din / 32 + cp.H / 32) * kMfmaBf16Flops : 0,
-               bf ? 0 : sum_mfma_f32(count, mp.din, cp.H));
-      if (pre && mb.sum_seg) {
-        SumSegArgs sa{sbases.base[0], mb.d_order, mb.d_msg_ptr, mb.d_msg_src, mb.d_xsum, mb.n_seg};
-        HIP_TRY(launch_sum_seg(sa, mp.din, st));
-      } else if (pre) {
-        SumWinArgs wa{sbases.base[0], mb.d_win_wg, mb.d_win_dst, mb.d_win_ptr, mb.d_win_src, mb.d_xsum, mb.n_win_wg};
-        HIP_TRY(launch_sum_win(wa, mp.din, st));
-      }
-      HIP_TRY(launch_sum_gru(a, mp.din, cp.H, sv, st));
-      tm.end();
-      if (target >= 0) b->proj_ready[target] |= (char)(1 << tslot);
-    }
-  }
+  s.hin = b->d_state[b->cur[dst]][dst];
+  s.hout = b->d_state[1 - b->cur[dst]][dst];
+  Timer tm{p};
+  if ((rc = mp_forward(p, b, mi, part, s, MpSave{}, tm))) return rc;
   if (part != IGN_PART_INTERIOR) b->cur[dst] ^= 1;   // GM:602: the destination state is overwritten
   return IGN_OK;
 }
 
 namespace {
-
-int accumulate_stats(ign_plan* p, int n, const int* kind, const EvCost* cost);
-
-// Resolve the pending event pairs of timed launches into the statistics (one host wait).
-int flush_timing(ign_plan* p) {
-  if (p->ev_slot == 0) return IGN_OK;
-  const int n = p->ev_slot;
-  p->ev_slot = 0;
-  return accumulate_stats(p, n, p->ev_kind.data(), p->ev_cost.data());
-}
-
-// Forget the pending event pairs (the statistics are being reset).
-void drop_timing(ign_plan* p) {
-  if (p->ev_slot && p->stream) hipStreamSynchronize(p->stream);
-  p->ev_slot = 0;
-}
 
 int accumulate_stats(ign_plan* p, int n, const int* kind, const EvCost* cost) {
   HIP_TRY(hipStreamSynchronize(p->stream));
@@ -1039,11 +802,16 @@ int accumulate_stats(ign_plan* p, int n, const int* kind, const EvCost* cost) {
   return IGN_OK;
 }
 
+// Forget the pending event pairs (the statistics are being reset).
+void drop_timing(ign_plan* p) {
+  if (p->ev_slot && p->stream) hipStreamSynchronize(p->stream);
+  p->ev_slot = 0;
+}
+
 // readout launches (GM:611-629); no host synchronisation, so it can be captured
 int readout(ign_plan* p, ign_batch* b) {
   hipStream_t st = p->stream;
   Timer tm{p};
-  // readout (GM:611-629)
   const int64_t P = b->n_pred;
   if (!p->ro_ops.empty()) {
     tm.begin(K_OTHER, 0, 0);
@@ -1051,52 +819,14 @@ int readout(ign_plan* p, ign_batch* b) {
     tm.end();
     if (rc) return rc;
   }
-  const float* x = readout_tensor(p, b, p->ro_in[0]);
-  int xs = p->ro_width;
-  if (p->ro_in.size() > 1) {
-    int col = 0;
-    for (int id : p->ro_in) {
-      const int w = p->ro_t[id].width;
-      HIP_TRY(launch_concat_cols(b->d_ro_in, P, p->ro_width, col, readout_tensor(p, b, id), w, st));
-      col += w;
-    }
-    x = b->d_ro_in;
-  }
+  const float* x = nullptr;
+  if (int rc = predict_input(p, b, nullptr, b->d_ro_in, &x, st)) return rc;
   const float* prm = p->d_params;
   if (p->fused_readout) {
-    const DenseP &l1 = p->dense[0], &l2 = p->dense[1], &l3 = p->dense[2];
-    Readout3Args a{x, P, xs,
-                   p->d_packed + l1.pk_w, l1.use_bias ? prm + l1.off_b : nullptr,
-                   p->d_packed + l2.pk_w, l2.use_bias ? prm + l2.off_b : nullptr,
-                   prm + l3.off_w, l3.use_bias ? prm + l3.off_b : nullptr,
-                   l1.act, l2.act, l3.act, b->d_pred};
-    if (!a.b1 || !a.b2) return fail(IGN_ERR_UNSUPPORTED, "fused readout requires use_bias on hidden layers");
-    double flops = 2.0 * P * ((double)l1.in * l1.out + (double)l2.in * l2.out + l3.in);
-    const bool bf = p->readout_variant >= 2 && l1.pk_bf >= 0 && l2.pk_bf >= 0;
-    const bool h32 = p->readout_variant == 5 && bf && l2.pk_h32 >= 0;
-    const bool h16 = (p->readout_variant == 4 || (p->readout_variant == 5 && !h32)) && bf && l2.pk_h >= 0;
-    const double tiles = (double)((P + 15) / 16);
-    // per 16-row tile: layer 1 out/16 x in/32 and layer 2 out/16 x in/32 MFMAs of 16x16x32, x6 or x9
-    // products (readout_bf); f32 (readout3): out/16 x in/4 each of 16x16x4
-    const double k1 = (double)(l1.out / 16) * (l1.in / 32) + (double)(l2.out / 16) * (l2.in / 32);
-    const double k1f = (double)(l1.out / 16) * (l1.in / 4) + (double)(l2.out / 16) * (l2.in / 4);
-    // variant 4: both layers x3 (16x16x32 f16, the bf16 rate)
-    const double kh = 3.0 * k1;
-    tm.begin(K_READOUT, flops, (double)P * (4.0 * l1.in + 4.0),
-             h16 || h32 ? tiles * kh * kMfmaBf16Flops : bf ? tiles * k1 * 6 * kMfmaBf16Flops : 0,
-             bf ? 0 : tiles * k1f * kMfmaF32Flops);
-    if (h32)   // variant 5: the same piece products on 32x32x16 (16-row-tile equivalent counted above)
-      HIP_TRY(launch_readout_h32(a, p->d_packed + l2.pk_h32, l1.in, st));
-    else if (h16)
-      HIP_TRY(launch_readout_h16(a, p->d_packed + l2.pk_h, l1.in, st));
-    else if (bf)
-      HIP_TRY(launch_readout_bf(a, p->d_packed + l1.pk_bf, p->d_packed + l2.pk_bf, l1.in, 6, st));
-    else
-      HIP_TRY(launch_readout3(a, l1.in, l1.out, l2.out, st));
-    tm.end();
+    if (int rc = readout_fused(p, b, x, nullptr, nullptr, tm, st)) return rc;
   } else {
     const float* in = x;
-    int in_stride = xs;
+    int in_stride = p->ro_width;
     // predict's layers in order, a Dropout being the identity here; the LayerNormalization layers
     // as dense_stack_forward runs them: each in front of a Dense layer writes its own buffer, and from
     // the last Dense layer on each layer writes the next one's buffer, the last d_pred
@@ -1140,6 +870,14 @@ int copy_out(ign_plan* p, ign_batch* b, float* pred_out) {
 }
 
 }  // namespace
+
+// Resolve the pending event pairs of timed launches into the statistics (one host wait).
+extern "C++" int ign::flush_timing(ign_plan* p) {
+  if (p->ev_slot == 0) return IGN_OK;
+  const int n = p->ev_slot;
+  p->ev_slot = 0;
+  return accumulate_stats(p, n, p->ev_kind.data(), p->ev_cost.data());
+}
 
 // the whole MP loop of a resident batch in one launch; the final states land in
 // buffer 0 of every entity, or (save: the training forward) in the state versions save names
@@ -1457,29 +1195,3 @@ int ign_stats(const ign_plan* p, ign_stats_t* out) {
 }
 
 }  // extern "C"
-
-int ign::run_message_net(ign_plan* p, const MsgNN& nn, const MPB& mb, int s, const float* src_state,
-                         const float* dst_state, hipStream_t st) {
-  return message_net_fwd(p, nn, mb, s, src_state, dst_state, st);
-}
-
-// Attention weights of one MP instance (AUX:287-343): per-row scores s_src = h_src (K1 a1),
-// s_dst = h_dst (K2 a2), then the axis-0 softmax over (graph, position) cells into mb.d_msg_w.
-int ign::attention_weights(ign_plan* p, ign_batch* b, const MPP& mp, const MPB& mb, const float* const* srcs,
-                           const float* hin, hipStream_t st) {
-  const CellP& cp = p->cells[mp.cell];
-  const float* w12 = p->d_packed + p->pk_w12;
-  for (size_t s = 0; s < mp.src.size(); ++s) {
-    const int se = mp.src[s].entity;
-    const int64_t rows_s = mp.nn[s].layers.empty() ? b->rows[se] + b->halo[se] : mb.n_edges[s];
-    HIP_TRY(launch_dense_fwd(srcs[s], rows_s, mp.din, mp.din, nullptr, w12, nullptr, 1, IGN_ACT_LINEAR, mb.d_s_src[s],
-                             st));
-  }
-  HIP_TRY(launch_dense_fwd(hin, mb.n_dst, cp.H, cp.H, nullptr, w12 + p->attn_F, nullptr, 1, IGN_ACT_LINEAR, mb.d_s_dst,
-                           st));
-  AttnArgs aa{mb.d_group_ptr, mb.d_group_empty, mb.d_cell_dst, mb.d_cell_ptr, mb.d_cell_msgs, mb.d_msg_src,
-              {mb.d_s_src[0], mb.d_s_src[1], mb.d_s_src[2], mb.d_s_src[3]}, mb.d_s_dst, mb.d_ecell, mb.d_msg_w,
-              mb.n_groups};
-  HIP_TRY(launch_attn_softmax(aa, st));
-  return IGN_OK;
-}

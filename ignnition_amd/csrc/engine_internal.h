@@ -250,14 +250,9 @@ int set_device(int dev);
 int ensure_device(ign_plan* p);
 int dev_alloc(ign_batch* b, float** out, int64_t n);
 int repack(ign_plan* p);                      // runs p->packs: fragments from d_params (set_params, optimizer)
-// message-creation network of MP source s (GM:440-475): per-edge inputs, then the Dense stack into
-// mb.d_msg_layer[s] (the last layer's rows are the messages)
-int run_message_net(ign_plan* p, const MsgNN& nn, const MPB& mb, int s, const float* src_state,
-                    const float* dst_state, hipStream_t st);
-// attention weights of one MP instance (AUX:287-343) into mb.d_msg_w (scores in mb.d_s_src / d_s_dst)
-int attention_weights(ign_plan* p, ign_batch* b, const MPP& mp, const MPB& mb, const float* const* srcs,
-                      const float* hin, hipStream_t st);
-// readout.cpp: the readout program (operations before predict, GM:611-655)
+// what every forward / backward entry point checks first; train: the batch has its training state too
+int check_pb(ign_plan* p, ign_batch* b, bool train = false);
+// readout.cpp: the readout program (operations before predict, GM:611-655) and predict's head
 int readout_batch(ign_plan* p, ign_batch* b, const ign_batch_desc* d);
 // ent: entity-state tensors to read (training keeps every version); null = the batch's current states
 // drop: the training forward's Dropout stream and buffers; null = inference (Dropout is identity)
@@ -271,7 +266,17 @@ int64_t stack_rows(const ign_plan* p, const ign_batch* b, int stack);
 int plan_add_dropout(ign_plan* p, int stack, int before_layer, float rate, uint64_t layer_seed);
 // ign_plan_add_layernorm's routine (likewise)
 int plan_add_layernorm(ign_plan* p, int stack, int before_layer, float epsilon, int center, int scale);
-const float* readout_tensor(const ign_plan* p, const ign_batch* b, int id);
+// readout tensor id (GM:660-675): an entity's final states (ent's, as readout_ops_run) or an operation's output
+const float* readout_tensor(const ign_plan* p, const ign_batch* b, int id, const float* const* ent = nullptr);
+// predict's input rows into *x: its one input tensor, or its inputs side by side in cat
+int predict_input(const ign_plan* p, const ign_batch* b, const float* const* ent, float* cat, const float** x,
+                  hipStream_t st);
+// The fused readout (p->fused_readout: three Dense layers in one launch) on x into b->d_pred, on the
+// kernel IGN_READOUT_VARIANT and the layers' fragments select.  save1 / save2: the hidden layers'
+// activations for a backward (readout_h16 / readout_h32 only), null in inference.
+struct Timer;   // mp_step.h
+int readout_fused(ign_plan* p, const ign_batch* b, const float* x, float* save1, float* save2, Timer& tm,
+                  hipStream_t st);
 int64_t space_rows(const ign_plan* p, const ign_batch* b, const RoTensor& t);
 // Batch construction (ign_batch_create, ign_batch_enable_training) copies and clears on a
 // non-blocking stream of the calling host thread, never the legacy null stream: a batch built on a

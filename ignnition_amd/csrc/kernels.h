@@ -216,14 +216,14 @@ struct ResidentArgs {
   // path_ver[it] and writes path_ver[it + 1] and every step's state into hs_save[it] from row hsb of
   // each position (seq_gru_h16<SAVE>'s layout); the sum MPs write their message sums into
   // x_save[s][it] and their new states into src_ver[s][it + 1]; every iteration projects with f32
-  // MFMA (build_table's project_kernel).  ver[.][0] hold the initial states (init_state).
+  // MFMA (mp_project's project_kernel).  ver[.][0] hold the initial states (init_state).
   float* const* path_ver;
   float* const* src_ver[kResidentMaxSrc];
   float* const* hs_save;
   float* const* x_save[kResidentMaxSrc];
   const int32_t* hsb;         // [headers] the position's first hs_save row (step_ptr + order position)
   float* const* tab_save;     // SAVE, optional: [T] the ordered MP's projected table per iteration, in
-                              // the batched layout (the backward's table; build_table is skipped)
+                              // the batched layout (the backward's table; mp_project is skipped)
   int64_t tab_off[kResidentMaxSrc];   // table row of each source entity's row 0 (MPB::src_off)
   int64_t tab_hole;           // the table's zero row (a hole: the bias alone)
 };

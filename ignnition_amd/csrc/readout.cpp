@@ -1,6 +1,7 @@
 // readout.cpp — the readout program of ComnetModel.call (GM:605-655): the operations that run
 // before predict, each writing a named tensor the later operations read (get_global_var_or_input,
-// GM:660-675).
+// GM:660-675), and the head of predict that the inference and the training forward share: the tensor
+// lookup, predict's input rows and the fused three-layer launch.
 //
 //   neural_network       Readout_nn (AUX:1188-1211): Dense stack on the axis-1 concatenation of
 //                        its inputs; weights readout_model_<op index> (GM:352-358).  The stack
@@ -26,6 +27,7 @@
 #include <cstring>
 
 #include "dense_stack.h"
+#include "mp_step.h"
 #include "readout_kernels.h"
 #include "train_kernels.h"
 
@@ -53,10 +55,60 @@ int64_t stack_rows(const ign_plan* p, const ign_batch* b, int stack) {
   return space_rows(p, b, p->ro_t[stack < 0 ? p->ro_in[0] : p->ro_ops[stack].in[0]]);
 }
 
-const float* readout_tensor(const ign_plan* p, const ign_batch* b, int id) {
-  const int NE = (int)p->ents.size();
-  if (id < NE) return b->d_state[b->cur[id]][id];
-  return b->ro_buf[id];
+const float* readout_tensor(const ign_plan* p, const ign_batch* b, int id, const float* const* ent) {
+  if (id >= (int)p->ents.size()) return b->ro_buf[id];
+  return ent ? ent[id] : b->d_state[b->cur[id]][id];
+}
+
+int predict_input(const ign_plan* p, const ign_batch* b, const float* const* ent, float* cat, const float** x,
+                  hipStream_t st) {
+  *x = readout_tensor(p, b, p->ro_in[0], ent);
+  if (p->ro_in.size() == 1) return IGN_OK;
+  int col = 0;
+  for (int id : p->ro_in) {
+    const int w = p->ro_t[id].width;
+    HIP_TRY(launch_concat_cols(cat, b->n_pred, p->ro_width, col, readout_tensor(p, b, id, ent), w, st));
+    col += w;
+  }
+  *x = cat;
+  return IGN_OK;
+}
+
+int readout_fused(ign_plan* p, const ign_batch* b, const float* x, float* save1, float* save2, Timer& tm,
+                  hipStream_t st) {
+  const int64_t P = b->n_pred;
+  const float* prm = p->d_params;
+  const DenseP &l1 = p->dense[0], &l2 = p->dense[1], &l3 = p->dense[2];
+  Readout3Args a{x, P, p->ro_width,
+                 p->d_packed + l1.pk_w, l1.use_bias ? prm + l1.off_b : nullptr,
+                 p->d_packed + l2.pk_w, l2.use_bias ? prm + l2.off_b : nullptr,
+                 prm + l3.off_w, l3.use_bias ? prm + l3.off_b : nullptr,
+                 l1.act, l2.act, l3.act, b->d_pred, save1, save2};
+  if (!a.b1 || !a.b2) return fail(IGN_ERR_UNSUPPORTED, "fused readout requires use_bias on hidden layers");
+  double flops = 2.0 * P * ((double)l1.in * l1.out + (double)l2.in * l2.out + l3.in);
+  const bool bf = p->readout_variant >= 2 && l1.pk_bf >= 0 && l2.pk_bf >= 0;
+  const bool h32 = p->readout_variant == 5 && bf && l2.pk_h32 >= 0;
+  const bool h16 = (p->readout_variant == 4 || (p->readout_variant == 5 && !h32)) && bf && l2.pk_h >= 0;
+  const double tiles = (double)((P + 15) / 16);
+  // per 16-row tile: layer 1 out/16 x in/32 and layer 2 out/16 x in/32 MFMAs of 16x16x32, x6 or x9
+  // products (readout_bf); f32 (readout3): out/16 x in/4 each of 16x16x4
+  const double k1 = (double)(l1.out / 16) * (l1.in / 32) + (double)(l2.out / 16) * (l2.in / 32);
+  const double k1f = (double)(l1.out / 16) * (l1.in / 4) + (double)(l2.out / 16) * (l2.in / 4);
+  // variant 4: both layers x3 (16x16x32 f16, the bf16 rate)
+  const double kh = 3.0 * k1;
+  tm.begin(K_READOUT, flops, (double)P * (4.0 * l1.in + 4.0),
+           h16 || h32 ? tiles * kh * kMfmaBf16Flops : bf ? tiles * k1 * 6 * kMfmaBf16Flops : 0,
+           bf ? 0 : tiles * k1f * kMfmaF32Flops);
+  if (h32)   // variant 5: the same piece products on 32x32x16 (16-row-tile equivalent counted above)
+    HIP_TRY(launch_readout_h32(a, p->d_packed + l2.pk_h32, l1.in, st));
+  else if (h16)
+    HIP_TRY(launch_readout_h16(a, p->d_packed + l2.pk_h, l1.in, st));
+  else if (bf)
+    HIP_TRY(launch_readout_bf(a, p->d_packed + l1.pk_bf, p->d_packed + l2.pk_bf, l1.in, 6, st));
+  else
+    HIP_TRY(launch_readout3(a, l1.in, l1.out, l2.out, st));
+  tm.end();
+  return IGN_OK;
 }
 
 int readout_batch(ign_plan* p, ign_batch* b, const ign_batch_desc* d) {
@@ -143,12 +195,8 @@ int readout_batch(ign_plan* p, ign_batch* b, const ign_batch_desc* d) {
 
 int readout_ops_run(ign_plan* p, ign_batch* b, hipStream_t st, const float* const* ent, const DropRun* drop,
                     const NormRun* norm) {
-  const int NE = (int)p->ents.size();
   const NormRun own{b->d_norm.data(), nullptr};   // inference: the batch's buffers, no statistics kept
   if (!norm) norm = &own;
-  auto readout_tensor = [&](const ign_plan* pp, const ign_batch* bb, int id) -> const float* {
-    return ent && id < NE ? ent[id] : ign::readout_tensor(pp, bb, id);
-  };
   for (size_t k = 0; k < p->ro_ops.size(); ++k) {
     const RoOp& op = p->ro_ops[k];
     RoBatchOp& bo = b->ro[k];
@@ -156,11 +204,11 @@ int readout_ops_run(ign_plan* p, ign_batch* b, hipStream_t st, const float* cons
     const int64_t n = space_rows(p, b, t0);
     switch (op.type) {
       case IGN_RO_NEURAL_NETWORK: {   // GM:612-628
-        const float* x = readout_tensor(p, b, op.in[0]);
+        const float* x = readout_tensor(p, b, op.in[0], ent);
         if (op.in.size() > 1) {
           int col = 0;
           for (int id : op.in) {
-            HIP_TRY(launch_concat_cols(bo.cat, n, op.in_width, col, readout_tensor(p, b, id), p->ro_t[id].width, st));
+            HIP_TRY(launch_concat_cols(bo.cat, n, op.in_width, col, readout_tensor(p, b, id, ent), p->ro_t[id].width, st));
             col += p->ro_t[id].width;
           }
           x = bo.cat;
@@ -171,13 +219,13 @@ int readout_ops_run(ign_plan* p, ign_batch* b, hipStream_t st, const float* cons
         break;
       }
       case IGN_RO_POOLING:            // GM:632-637
-        HIP_TRY(launch_pool(readout_tensor(p, b, op.in[0]), t0.width, bo.n_chunks, bo.d_chunk, bo.d_chunk_ptr,
+        HIP_TRY(launch_pool(readout_tensor(p, b, op.in[0], ent), t0.width, bo.n_chunks, bo.d_chunk, bo.d_chunk_ptr,
                             bo.d_count, b->G, op.mode, bo.d_partial, bo.out[0], st));
         break;
       case IGN_RO_PRODUCT: {          // GM:640-645
         const RoTensor& t1 = p->ro_t[op.in[1]];
         const RoTensor& to = p->ro_t[op.out];
-        ProductArgs a{readout_tensor(p, b, op.in[0]), readout_tensor(p, b, op.in[1]), t0.width, t1.width, to.width,
+        ProductArgs a{readout_tensor(p, b, op.in[0], ent), readout_tensor(p, b, op.in[1], ent), t0.width, t1.width, to.width,
                       t0.space == RS_GRAPH && to.space != RS_GRAPH, t1.space == RS_GRAPH && to.space != RS_GRAPH,
                       bo.d_seg, b->G, space_rows(p, b, to), bo.out[0]};
         HIP_TRY(launch_product(a, st));
@@ -185,8 +233,8 @@ int readout_ops_run(ign_plan* p, ign_batch* b, hipStream_t st, const float* cons
       }
       case IGN_RO_EXTEND: {           // GM:647-655
         const int64_t e = b->adj_rows[op.adj];
-        HIP_TRY(launch_gather(readout_tensor(p, b, op.in[0]), t0.width, bo.idx[0], e, bo.out[0], st));
-        HIP_TRY(launch_gather(readout_tensor(p, b, op.in[1]), p->ro_t[op.in[1]].width, bo.idx[1], e, bo.out[1], st));
+        HIP_TRY(launch_gather(readout_tensor(p, b, op.in[0], ent), t0.width, bo.idx[0], e, bo.out[0], st));
+        HIP_TRY(launch_gather(readout_tensor(p, b, op.in[1], ent), p->ro_t[op.in[1]].width, bo.idx[1], e, bo.out[1], st));
         break;
       }
     }

@@ -625,7 +625,7 @@ __global__ __launch_bounds__(64 * kW) void resident_forward_kernel(ResidentArgs 
         }
       }
       if (!last) {
-        if constexpr (SAVE) {   // build_table's projection (and the next iteration's saved table)
+        if constexpr (SAVE) {   // mp_project's projection (and the next iteration's saved table)
           float* gs = nullptr;
           if (a.tab_save && it + 1 < a.T) gs = in_global(a.tab_save[it + 1]) + tab_row(a, ll, L0, s00, s10) * 96;
           project_row_f32(a, hn, tab, ll, valid, lane, g, gs);

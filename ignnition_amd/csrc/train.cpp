@@ -4,7 +4,9 @@
 //   ign_forward_train   the forward of ComnetModel.call (GM:384-658), keeping what the backward
 //                       needs: every hidden-state version (no ping-pong), the per-step states of
 //                       each ordered update, the aggregated messages of each sum update, and
-//                       the readout activations
+//                       the readout activations.  Each MP instance is the inference forward's
+//                       routine (mp_step.cpp's mp_forward) given the buffers to save into, and
+//                       predict's head readout.cpp's; here are the versions and the records
 //   ign_backward        tf.gradients(total_loss, trainable_variables) (GM:790) for a given
 //                       dLoss/dpredictions, plus the Dense l2 regularizer terms (AUX:833-834)
 // The loss, the regularizer's value and the optimizer update around them are learn.cpp.
@@ -23,6 +25,7 @@
 #include <vector>
 
 #include "dense_stack.h"
+#include "mp_step.h"
 #include "readout_kernels.h"
 #include "train_kernels.h"
 #include "train_lower.h"
@@ -54,6 +57,7 @@ struct MPRec {
 struct TrainState {
   std::vector<std::vector<float*>> ver;   // [entity][version] hidden states
   hvec<int> cur;                   // current version per entity (after the forward)
+  std::vector<const float*> ent;   // ver[e][cur[e]] as of ign_forward_train_end: the readout's entity tensors
   std::vector<MPTrain> mp;
   std::vector<MPRec> recs;
   float* ga = nullptr;
@@ -97,7 +101,7 @@ struct TrainState {
   bool f_open = false;
   float** res_ptrs = nullptr;   // the graph-resident training forward's version / save pointer arrays
   std::vector<float*> tsave;    // its saved projected tables of the ordered MP, per iteration
-  bool tab_saved = false;       // this forward saved them (the backward skips build_table)
+  bool tab_saved = false;       // this forward saved them (the backward skips mp_project)
   // weight gradients formed once per MP instance (T of them per backward) keep their partial tiles
   // here and are reduced once, at ign_backward_end, in instance order (IGN_DEFER_WGRAD=0: per instance)
   struct DeferredGrad {
@@ -242,35 +246,13 @@ int tsgemm_deferred_flush(const ign_plan* p, TrainState* t, hipStream_t st) {
   return IGN_OK;
 }
 
-int check_train(ign_plan* p, ign_batch* b) {
-  if (!p || !b) return fail(IGN_ERR_INVALID, "null argument");
-  if (b->plan != p) return fail(IGN_ERR_INVALID, "batch was created for another plan");
-  if (!b->train) return fail(IGN_ERR_INVALID, "training not enabled on this batch (ign_batch_enable_training)");
-  if (!p->params_set) return fail(IGN_ERR_INVALID, "parameters not set (ign_plan_set_params)");
-  return set_device(p->device);
-}
-
-// project every source of sorted MP mb into its table, from the given source states
-int build_table(ign_plan* p, const MPP& mp, const MPB& mb, const CellP& cp, const float* const* src) {
-  const int W3 = 3 * cp.H;
-  for (size_t s = 0; s < mp.src.size(); ++s) {
-    // axis-2 concat (AUX:443-456): each source through its own row slice of the input kernel
-    const int sdin = mp.feature_concat ? p->ents[mp.src[s].entity].hidden_dim : mp.din;
-    const float* wp = p->d_packed + (mp.feature_concat ? mp.pk_slice[s] : cp.pk_w);
-    HIP_TRY(launch_project(src[s], mb.src_rows[s], wp, p->d_packed + cp.pk_b, mb.d_table + mb.src_off[s] * W3,
-                           s == 0 ? mb.d_table + mb.zero_row * W3 : nullptr, sdin, cp.H, p->stream));
-  }
-  if (mb.n_multi)
-    HIP_TRY(launch_multi_sum(mb.d_table, mb.zero_row + 1, mb.n_multi, mb.d_multi_ptr, mb.d_multi_rows, W3,
-                             mb.d_table + mb.zero_row * W3, p->stream));
-  return IGN_OK;
-}
+int check_train(ign_plan* p, ign_batch* b) { return check_pb(p, b, true); }
 
 // Backward of MP source s's message-creation network (GM:440-475), given d(messages) in t->dmsg:
 // Dense stack in reverse (weight / bias gradients; the l2 terms are added once per step by
 // ign_backward, not per MP instance), then the hs_source / hs_dest column
 // slices of d(input) gathered back to the state rows they were read from.  The layer activations
-// are the ones run_message_net left in mb (recomputed for this MP instance by the caller).
+// are the ones mp_message_nets left in mb (recomputed for this MP instance by the caller).
 int msg_net_backward(ign_plan* p, ign_batch* b, TrainState* t, const MPP& mp, const MPB& mb, const MPTrain& mt,
                      int s, float* dsrc, float* ddst, float* grads, hipStream_t st) {
   const MsgNN& nn = mp.nn[s];
@@ -297,10 +279,7 @@ int msg_net_backward(ign_plan* p, ign_batch* b, TrainState* t, const MPP& mp, co
   return IGN_OK;
 }
 
-// readout tensor id (GM:660-675): an entity's final states or an operation's output, and its gradient
-const float* ro_tensor(const ign_batch* b, const TrainState* t, int id) {
-  return id < (int)t->ver.size() ? t->ver[id][t->cur[id]] : b->ro_buf[id];
-}
+// the gradient of readout tensor id (GM:660-675): an entity's final states or an operation's output
 float* ro_grad(TrainState* t, int id) { return id < (int)t->ver.size() ? t->dS[0][id] : t->dT[id]; }
 
 // Backward of a readout Dense stack r (predict's, an operation's) from d(y) in dy: d(x) is added to
@@ -334,6 +313,7 @@ DenseStackRun predict_stack(const ign_plan* p, const ign_batch* b, TrainState* t
 // gradient of its output tensors (t->dT) into additions to its inputs' gradients
 int readout_ops_backward(ign_plan* p, ign_batch* b, TrainState* t, hipStream_t st) {
   int rc;
+  const float* const* ent = t->ent.data();   // the forward's entity tensors
   int xi = (int)t->rx_ptr.size();   // extend CSRs are stored in op order, two per op
   for (int k = (int)p->ro_ops.size() - 1; k >= 0; --k) {
     const RoOp& op = p->ro_ops[k];
@@ -342,24 +322,24 @@ int readout_ops_backward(ign_plan* p, ign_batch* b, TrainState* t, hipStream_t s
     const int64_t n = space_rows(p, b, t0);
     switch (op.type) {
       case IGN_RO_NEURAL_NETWORK: {   // Readout_nn (AUX:1188-1211): Dense stack on concat(inputs)
-        const float* x = op.in.size() > 1 ? bo.cat : ro_tensor(b, t, op.in[0]);
+        const float* x = op.in.size() > 1 ? bo.cat : readout_tensor(p, b, op.in[0], ent);
         const DenseStackRun r{op.layers.data(), (int)op.layers.size(), n, x, op.in_width, bo.tmp.data(), bo.out[0],
                               &t->drop, &op.seq, &t->norm};
         if ((rc = ro_stack_backward(p, t, r, t->dT[op.out], t->rz, op.in, t->rcat, st))) return rc;
         break;
       }
       case IGN_RO_POOLING:   // Pooling_operation (AUX:1165-1185)
-        HIP_TRY(launch_pool_bwd(ro_tensor(b, t, op.in[0]), bo.out[0], t->dT[op.out], t->rties, t0.width, bo.d_inoff, b->G,
-                                op.mode, n, ro_grad(t, op.in[0]), st));
+        HIP_TRY(launch_pool_bwd(readout_tensor(p, b, op.in[0], ent), bo.out[0], t->dT[op.out], t->rties, t0.width,
+                                bo.d_inoff, b->G, op.mode, n, ro_grad(t, op.in[0]), st));
         break;
       case IGN_RO_PRODUCT: {   // element_wise (AUX:1081-1088)
         const RoTensor& t1 = p->ro_t[op.in[1]];
         const RoTensor& to = p->ro_t[op.out];
         const int ag = t0.space == RS_GRAPH && to.space != RS_GRAPH, bg = t1.space == RS_GRAPH && to.space != RS_GRAPH;
-        HIP_TRY(launch_product_bwd(t->dT[op.out], ro_tensor(b, t, op.in[1]), t0.width, t1.width, to.width, ag, bg, bo.d_seg,
-                                   b->G, n, ro_grad(t, op.in[0]), st));
-        HIP_TRY(launch_product_bwd(t->dT[op.out], ro_tensor(b, t, op.in[0]), t1.width, t0.width, to.width, bg, ag, bo.d_seg,
-                                   b->G, space_rows(p, b, t1), ro_grad(t, op.in[1]), st));
+        HIP_TRY(launch_product_bwd(t->dT[op.out], readout_tensor(p, b, op.in[1], ent), t0.width, t1.width, to.width, ag,
+                                   bg, bo.d_seg, b->G, n, ro_grad(t, op.in[0]), st));
+        HIP_TRY(launch_product_bwd(t->dT[op.out], readout_tensor(p, b, op.in[0], ent), t1.width, t0.width, to.width, bg,
+                                   ag, bo.d_seg, b->G, space_rows(p, b, t1), ro_grad(t, op.in[1]), st));
         break;
       }
       case IGN_RO_EXTEND: {   // Extend_adjacencies (AUX:1236-1265): gathers, so scatter back per row
@@ -401,6 +381,7 @@ int alloc_states(const ign_plan* p, const ign_batch* b, TrainState* t) {
   for (auto& mp : p->mps) nver[mp.dst] += p->T;
   t->ver.resize(E);
   t->cur.assign(E, 0);
+  t->ent.assign(E, nullptr);
   for (int e = 0; e < E; ++e) {
     const int64_t n = (b->rows[e] + b->halo[e]) * p->ents[e].hidden_dim;   // owned rows, then halo rows
     for (int v = 0; v < nver[e]; ++v) {
@@ -792,61 +773,26 @@ int ign_forward_train_mp(ign_plan* p, ign_batch* b) {
   if (rc) return rc;
   TrainState* t = b->train;
   if (!t->f_open || t->f_it >= p->T) return fail(IGN_ERR_INVALID, "ign_forward_train_mp outside begin .. end");
-  hipStream_t st = p->stream;
   const int it = t->f_it, mi = t->f_mi;
-  {
-      const MPP& mp = p->mps[mi];
-      const MPB& mb = b->mp[mi];
-      const CellP& cp = p->cells[mp.cell];
-      MPTrain& mt = t->mp[mi];
-      MPRec rec{mi, it, t->cur[mp.dst], {0, 0, 0, 0}};
-      SrcBases sb{};
-      const float* srcs[IGN_MAX_SLOTS] = {nullptr, nullptr, nullptr, nullptr};
-      for (size_t s = 0; s < mp.src.size(); ++s) {
-        const int se = mp.src[s].entity;
-        rec.src_v[s] = t->cur[se];
-        srcs[s] = sb.base[s] = t->ver[se][t->cur[se]];
-      }
-      const float* hin = t->ver[mp.dst][rec.v_in];
-      float* hout = t->ver[mp.dst][rec.v_in + 1];
-      for (size_t s = 0; s < mp.src.size(); ++s) {   // message-creation networks (GM:440-475)
-        if (mp.nn[s].layers.empty()) continue;
-        if ((rc = run_message_net(p, mp.nn[s], mb, (int)s, srcs[s], hin, st))) return rc;
-        srcs[s] = sb.base[s] = mb.d_msg_layer[s].back();
-      }
-      if (mp.sorted) {
-        if ((rc = build_table(p, mp, mb, cp, srcs))) return rc;
-        SeqGruArgs a{hin, hout, mb.d_table, mb.d_order, mb.d_len, mb.d_step_ptr, mb.d_step_code,
-                     p->d_packed + cp.pk_u, p->d_packed + cp.pk_b, mb.n_dst, p->xcd_remap};
-        a.hs_save = mt.hs[it];
-        if (cp.pk_ubf >= 0) a.Ubf = p->d_packed + cp.pk_ubf;
-        if (cp.pk_uh >= 0) a.Uh = p->d_packed + cp.pk_uh;
-        a.hdr = mb.d_seq_hdr;
-        HIP_TRY(launch_seq_gru(a, cp.H, train_seq_variant(p, cp.H), st));
-      } else {
-        SumGruArgs a{hin, hout, sb, mb.d_order, mb.d_msg_ptr, mb.d_msg_src, p->d_packed + cp.pk_w,
-                     p->d_packed + cp.pk_u, p->d_packed + cp.pk_b, mb.n_dst, p->xcd_remap};
-        a.x_save = mt.xs[it];
-        if (mp.aggr == IGN_AGGR_ATTENTION) {     // AUX:287-343
-          if ((rc = attention_weights(p, b, mp, mb, srcs, hin, st))) return rc;
-          a.msg_w = mb.d_msg_w;
-        }
-        if (mp.aggr == IGN_AGGR_CONVOLUTION) {   // AUX:384-401
-          a.conv_kp = p->d_packed + p->pk_conv;
-          a.conv_act = mp.act;
-          a.sum_save = mt.ss[it];
-        }
-        // 64-wide plain sums on the forward's default split-bf16 kernel (x_save supported); else f32
-        if (p->sum_variant >= 7 && mp.aggr == IGN_AGGR_SUM && cp.pk_wbf >= 0 && cp.pk_ubf >= 0 && mp.din == cp.din &&
-            !mp.feature_concat) {
-          a.Wbf = p->d_packed + cp.pk_wbf;
-          a.Ubf = p->d_packed + cp.pk_ubf;
-        }
-        HIP_TRY(launch_sum_gru(a, mp.din, cp.H, cp.H == 64 ? (a.Wbf ? 7 : 3) : std::min(p->sum_variant, 7), st));
-      }
-      t->cur[mp.dst] = rec.v_in + 1;
-      t->recs.push_back(rec);
+  const MPP& mp = p->mps[mi];
+  const MPTrain& mt = t->mp[mi];
+  MPRec rec{mi, it, t->cur[mp.dst], {0, 0, 0, 0}};
+  MpStates s;
+  for (size_t k = 0; k < mp.src.size(); ++k) {
+    const int se = mp.src[k].entity;
+    rec.src_v[k] = t->cur[se];
+    s.src.base[k] = t->ver[se][t->cur[se]];
   }
+  s.hin = t->ver[mp.dst][rec.v_in];
+  s.hout = t->ver[mp.dst][rec.v_in + 1];
+  MpSave save;   // what ign_backward_mp reads of this instance
+  if (mp.sorted) save.hs = mt.hs[it];
+  else save.x = mt.xs[it];
+  if (!mp.sorted && mp.aggr == IGN_AGGR_CONVOLUTION) save.sum = mt.ss[it];   // AUX:384-401
+  Timer untimed{nullptr};
+  if ((rc = mp_forward(p, b, mi, IGN_PART_ALL, s, save, untimed))) return rc;
+  t->cur[mp.dst] = rec.v_in + 1;
+  t->recs.push_back(rec);
   if (++t->f_mi == (int)p->mps.size()) {
     t->f_mi = 0;
     ++t->f_it;
@@ -861,43 +807,25 @@ int ign_forward_train_end(ign_plan* p, ign_batch* b, float* pred_out) {
   if (!t->f_open || t->f_it != p->T) return fail(IGN_ERR_INVALID, "ign_forward_train_end before every MP ran");
   t->f_open = false;
   hipStream_t st = p->stream;
-  const int E = (int)p->ents.size();
   // readout operations, then the predict stack with every activation kept (GM:605-629)
-  std::vector<const float*> ent(E);
-  for (int e = 0; e < E; ++e) ent[e] = t->ver[e][t->cur[e]];
+  for (size_t e = 0; e < t->ent.size(); ++e) t->ent[e] = t->ver[e][t->cur[e]];
   // this forward's Dropout masks (ign_batch_set_dropout), kept for the backward that regenerates them
   t->drop = DropRun{b->drop_seed, b->drop_step, t->dbuf.data()};
   t->norm = NormRun{t->nbuf.data(), t->nstats.data()};
-  if (!p->ro_ops.empty() && (rc = readout_ops_run(p, b, st, ent.data(), &t->drop, &t->norm))) return rc;
+  if (!p->ro_ops.empty() && (rc = readout_ops_run(p, b, st, t->ent.data(), &t->drop, &t->norm))) return rc;
   const int64_t P = b->n_pred;
-  const float* x = ro_tensor(b, t, p->ro_in[0]);
-  if (p->ro_in.size() > 1) {
-    int col = 0;
-    for (int id : p->ro_in) {
-      HIP_TRY(launch_concat_cols(t->ro_x, P, p->ro_width, col, ro_tensor(b, t, id), p->ro_t[id].width, st));
-      col += p->ro_t[id].width;
-    }
-    x = t->ro_x;
-  }
-  // the inference readout kernel (readout_h16) with its activations written out: one launch, no
-  // re-read of layer 1's output (readout.cpp's fused-readout conditions, variant 4)
+  const float* x = nullptr;
+  if ((rc = predict_input(p, b, t->ent.data(), t->ro_x, &x, st))) return rc;
+  // the inference readout kernel (readout_h16 / _h32, as readout_fused picks it) with its activations
+  // written out: one launch, no re-read of layer 1's output; its two saving kernels, three Dense layers only
   // (a stack with a Dropout site runs layer by layer: the mask sits between two of its launches)
   const bool fused = p->train_fused_readout && p->fused_readout && p->readout_variant >= 4 && p->dense.size() == 3 &&
                      p->dense[1].pk_h >= 0 && p->dense[0].pk_bf >= 0 && p->dense[1].pk_bf >= 0 &&
                      p->dense[0].use_bias && p->dense[1].use_bias && p->seq.size() == p->dense.size();
-  if (!fused && (rc = dense_stack_forward(p, predict_stack(p, b, t, x), st))) return rc;
-  if (fused) {
-    const DenseP &l1 = p->dense[0], &l2 = p->dense[1], &l3 = p->dense[2];
-    Readout3Args a{x, P, p->ro_width,
-                   nullptr, p->d_params + l1.off_b,   // readout_h16 reads its pieces from pk_h only
-                   nullptr, p->d_params + l2.off_b,
-                   p->d_params + l3.off_w, l3.use_bias ? p->d_params + l3.off_b : nullptr,
-                   l1.act, l2.act, l3.act, b->d_pred, t->act[0], t->act[1]};
-    if (p->readout_variant == 5 && l2.pk_h32 >= 0)   // the inference kernel's variant (same predictions)
-      HIP_TRY(launch_readout_h32(a, p->d_packed + l2.pk_h32, l1.in, st));
-    else
-      HIP_TRY(launch_readout_h16(a, p->d_packed + l2.pk_h, l1.in, st));
-  }
+  Timer untimed{nullptr};
+  if ((rc = fused ? readout_fused(p, b, x, t->act[0], t->act[1], untimed, st)
+                  : dense_stack_forward(p, predict_stack(p, b, t, x), st)))
+    return rc;
   if (pred_out) {
     HIP_TRY(hipMemcpyAsync(pred_out, b->d_pred, P * b->out_units * sizeof(float), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -1008,7 +936,7 @@ int ign_backward_begin(ign_plan* p, ign_batch* b, const float* dpred, float* gra
       HIP_TRY(hipMemsetAsync(t->dT[id], 0, space_rows(p, b, p->ro_t[id]) * p->ro_t[id].width * sizeof(float), st));
 
   // ---- readout (GM:605-629) in reverse: predict, then the operations before it
-  const float* x = p->ro_in.size() > 1 ? t->ro_x : ro_tensor(b, t, p->ro_in[0]);
+  const float* x = p->ro_in.size() > 1 ? t->ro_x : readout_tensor(p, b, p->ro_in[0], t->ent.data());
   if ((rc = ro_stack_backward(p, t, predict_stack(p, b, t, x), dpred, t->dz, p->ro_in, t->dro, st)) ||
       (rc = readout_ops_backward(p, b, t, st)))
     return rc;
@@ -1039,11 +967,9 @@ int ign_backward_mp(ign_plan* p, ign_batch* b) {
       HIP_TRY(hipMemsetAsync(dh_out + b->rows[dst] * H, 0, b->halo[dst] * H * sizeof(float), st));
     const float* srcs[IGN_MAX_SLOTS] = {nullptr, nullptr, nullptr, nullptr};
     for (size_t s = 0; s < mp.src.size(); ++s) srcs[s] = t->ver[mp.src[s].entity][rec.src_v[s]];
-    for (size_t s = 0; s < mp.src.size(); ++s) {   // recompute this instance's message networks
-      if (mp.nn[s].layers.empty()) continue;
-      if ((rc = run_message_net(p, mp.nn[s], mb, (int)s, srcs[s], t->ver[dst][rec.v_in], st))) return rc;
-      srcs[s] = mb.d_msg_layer[s].back();
-    }
+    // recompute this instance's message networks (and, below, its table): the forward's routines, untimed
+    if ((rc = mp_message_nets(p, mp, mb, srcs, t->ver[dst][rec.v_in], st))) return rc;
+    Timer untimed{nullptr};
     auto src_grad = [&](size_t s) -> float* {      // where d(state of source s) accumulates
       const int se = mp.src[s].entity;
       return se == dst ? dh_out : t->dS[dcur[se]][se];
@@ -1054,7 +980,7 @@ int ign_backward_mp(ign_plan* p, ign_batch* b) {
     if (mp.sorted) {
       // the forward's table of this instance: saved by the resident training forward, else recomputed
       const bool saved = t->tab_saved && rec.mi == 0 && rec.it < (int)t->tsave.size();
-      if (!saved && (rc = build_table(p, mp, mb, cp, srcs))) return rc;
+      if (!saved && (rc = mp_project(p, mp, mb, srcs, 0, untimed))) return rc;
       SeqBwdArgs a{mt.hs[rec.it], saved ? t->tsave[rec.it] : mb.d_table, mb.d_order, mb.d_len, mb.d_step_ptr, mb.d_step_code,
                    p->d_packed + cp.pk_u, p->d_packed + cp.pk_b, p->d_packed + cp.pk_ut, dh_in, dh_out,
                    t->ga, t->gu, mb.n_dst};

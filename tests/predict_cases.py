@@ -2,9 +2,10 @@
 the forward parity, the gradient and the plan-lowering tests:
 {name: [(units, activation, extra Dense options), ...]}.
 
-Which kernels a case reaches (readout.cpp's fused-readout conditions, engine.cpp's readout() in
-inference; in training train.cpp's ign_forward_train_end for the fused SAVE launch, else
-dense_stack.cpp's dense_stack_forward, and its dense_stack_backward called by ign_backward_begin):
+Which kernels a case reaches (readout.cpp's readout_fused for the fused launch, from engine.cpp's
+readout() in inference and, with the SAVE form, from train.cpp's ign_forward_train_end; else
+engine.cpp's layer walk in inference and dense_stack.cpp's dense_stack_forward in training, and its
+dense_stack_backward called by ign_backward_begin):
 
   relu tanh sigmoid linear selu   256 a, 256 a, 1: the fused kernels' five ACT instantiations (readout3,
                                   readout_bf, readout_h16 with and without SAVE, readout_h32); act' of the layer
@@ -72,6 +73,9 @@ SEED = 3          # init_params(SEED, bias_scale=BIAS)
 # 100 % / 80 % / 66 % are positive (H = 16 / 32 / 64), so both arms of the output relu run at 32 and 64
 SEEDS = {"relu_out": 12}
 BIAS = 0.2
+# predict_inputs(*WIDE): the plain-sum model at DIN = H = 64, where IGN_SUM_VARIANT selects among three
+# sum kernels (3: f32 MFMA, 7: split-bf16, 8: split-fp16, which saves nothing and so never trains)
+WIDE = ("selu", 64)
 
 
 def layer_name(i):

@@ -85,6 +85,7 @@ def _loss_inputs(name, n):
 def _run_loss(eng, kind, p, y, want_loss=True):
     pd, yd = torch.from_numpy(p).cuda(), torch.from_numpy(y).cuda()
     d = torch.full_like(pd, float("nan"))
+    torch.cuda.synchronize()   # the fill runs on torch's stream, the loss on the plan's: nothing else orders them
     loss = eng.loss(kind, pd, yd, d, want_loss=want_loss)
     torch.cuda.synchronize()
     return loss, d.cpu().numpy()

@@ -749,6 +749,33 @@ def test_timing_kinds_mask(monkeypatch):
     assert st["readout"]["launches"] == 0 and st["sum_gru"]["launches"] == 0
 
 
+def test_training_records_no_timing(monkeypatch):
+    """The training forward and the backward run the inference forward's MP step and readout head with
+    a timer that never records: with every kind enabled they leave no launch in the statistics, and the
+    inference forward after them still records its own."""
+    import torch
+    monkeypatch.setenv("IGN_RESIDENT", "0")   # the batched launches (the resident forward is one kind)
+    desc, dims, mi, graphs, _ = workloads.make_batch_inputs("routenet", "nsfnet", 2)
+    plan = MPPlan.from_model_info(mi)
+    eng = Engine(plan, 0)
+    eng.set_params(plan.init_params(0))
+    b = Batch(eng, graphs)
+    b.enable_training()
+    eng.set_timing(True)
+    b.forward_train()
+    dpred = torch.ones(b.predictions * b.output_units, dtype=torch.float32, device="cuda")
+    grads = torch.zeros(eng.n_params, dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()   # torch's fills before the plan stream reads them
+    b.backward(dpred, grads)
+    torch.cuda.synchronize()
+    st = eng.stats()
+    assert {k: v["launches"] for k, v in st.items()} == {k: 0 for k in st}
+    b.forward()
+    assert eng.stats()["seq_gru"]["launches"] == plan.iterations
+    b.close()
+    eng.close()
+
+
 # ---------------------------------------------------------------------------------------------
 # schema-legal aggregations outside the example configs (AUX:264-401, SURVEY §8f rank 3)
 def _variant_inputs(desc, kind, n, seed0=0):

@@ -637,6 +637,29 @@ def test_gradients_predict_switches(monkeypatch, case):
             eng.close()
 
 
+def test_training_never_takes_the_split_fp16_sum(monkeypatch):
+    """IGN_SUM_VARIANT=8 at DIN = H = 64: the inference forward moves to sum_gru_h16, which saves no
+    message sums, so the training forward stays on variant 7's kernel: its predictions and the gradients
+    of one backward are bitwise those under IGN_SUM_VARIANT=7."""
+    from tests.predict_cases import WIDE, predict_inputs
+    desc, dims, plan, graphs, labels, prm = predict_inputs(*WIDE)
+    out = {}
+    for v in ("7", "8"):
+        monkeypatch.setenv("IGN_SUM_VARIANT", v)
+        eng = Engine(plan, 0)
+        eng.set_params(prm)
+        b = Batch(eng, graphs)
+        infer = b.forward().reshape(-1).copy()
+        b.close()
+        _, b, pred, _, _, grads = _engine_grads(desc, dims, graphs, labels, prm, eng=eng)
+        out[v] = infer, pred.reshape(-1).copy(), grads.cpu().numpy()
+        b.close()
+        eng.close()
+    assert not np.array_equal(out["7"][0], out["8"][0])   # the switch took effect where it may
+    np.testing.assert_array_equal(out["7"][1], out["8"][1])
+    np.testing.assert_array_equal(out["7"][2], out["8"][2])
+
+
 @pytest.mark.parametrize("hidden", [16, 64])
 def test_gradients_predict_selu_hidden_sizes(hidden):
     """The DIN = 64 SAVE form of readout_h16 and, at hidden 16 (no fused readout kernel with saves),

@@ -3,11 +3,11 @@
 (IGN_LIB_PATH), predictions compared bit for bit.  --train compares the parameter gradients of one backward instead (dpred = a
 fixed seeded vector).
     python tools/ab_bitwise.py base new [--graphs 512] [--model routenet] [--topology synth50] [--train]
---cases runs the models of the tests' case modules instead (predict_cases, test_gpu_dropout's GRAD_CASES
+--cases runs the models of the tests' case modules instead (predict_cases and its H = 64 model, test_gpu_dropout's GRAD_CASES
 with its mask stream, layernorm_cases' GRAD_CASES, readout_cases, test_gpu_training's message-network
 parameter sets), all of them in one process per library, and compares per case the training forward's
-predictions and the flat gradient of one backward; for the LayerNormalization, readout-operation and
-message-network cases the inference forward too.
+predictions and the flat gradient of one backward; for the H = 64, LayerNormalization, readout-operation
+and message-network cases the inference forward too.
 (Against a parent commit: tools/build_ab.sh base in a checkout of it, its lib_base.so copied to this ab/.)
     python tools/ab_bitwise.py base new --cases"""
 import argparse
@@ -56,6 +56,8 @@ def cases():
     for c in sorted(pc.PREDICT_CASES):
         desc, dims, _, graphs, _, prm = pc.predict_inputs(c)
         yield "predict/" + c, desc, dims, graphs, prm, None, False
+    desc, dims, _, graphs, _, prm = pc.predict_inputs(*pc.WIDE)   # H = 64: IGN_SUM_VARIANT's three kernels
+    yield "predict/%s_h%d" % pc.WIDE, desc, dims, graphs, prm, None, True
     for c in sorted(td.GRAD_CASES):
         desc = td.GRAD_CASES[c]()
         dims, _, graphs, _, prm = dc.inputs(desc)
