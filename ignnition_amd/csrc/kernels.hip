@@ -473,7 +473,10 @@ __global__ __launch_bounds__(256) void sum_gru_kernel(SumGruArgs a) {
 #pragma unroll
       for (int c = 0; c < NC; ++c)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) x[c][r] = act_apply((y[c][r] + h[c][r]) / deg, a.conv_act);
+        for (int r = 0; r < 4; ++r) {
+          const float u = (y[c][r] + h[c][r]) / deg;
+          x[c][r] = u != u ? u : act_apply(u, a.conv_act);   // relu(NaN) is NaN in the reference, not 0
+        }
     }
     if (a.x_save && valid) {
 #pragma unroll
@@ -619,7 +622,8 @@ __global__ __launch_bounds__(256) void attn_softmax_kernel(AttnArgs a) {
   for (int c = c0 + lane; c < c1; c += 64) z += __expf(a.ecell[c] - mx);
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) z += __shfl_xor(z, o);
-  z += (float)a.group_empty[grp] * __expf(-mx);         // empty cells hold 0
+  // empty cells hold 0 (then mx >= 0).  Without one, mx may lie below -88, where exp(-mx) is inf and 0 * inf NaN
+  if (a.group_empty[grp] > 0) z += (float)a.group_empty[grp] * __expf(-mx);
   const float inv = 1.0f / z;
   for (int c = c0 + lane; c < c1; c += 64) {
     const float w = __expf(a.ecell[c] - mx) * inv;

@@ -64,6 +64,7 @@ struct TrainState {
   float* gu = nullptr;
   float* dx = nullptr;
   float* dtab = nullptr;
+  float* rsrc = nullptr;      // convolution plans: an ordered MP's source rows, the unread ones as zeros
   std::vector<float*> dS[2];
   std::vector<float*> act;                // readout activations of layers 0 .. L-2
   float* dz[2] = {nullptr, nullptr};
@@ -508,7 +509,7 @@ int enable_mp(const ign_plan* p, const ign_batch* b, TrainState* t, size_t mi, b
 
 // floats of the scratch buffers the MP instances / readout layers of a backward share: the largest need of each
 struct TrainScratch {
-  int64_t ga = 0, gu = 0, dx = 0, dtab = 0, part = 0;
+  int64_t ga = 0, gu = 0, dx = 0, dtab = 0, part = 0, rsrc = 0;
   int64_t dmsg = 0, mz = 0, mdin = 0;            // message networks
   int64_t amsg = 0, arows = 0;                   // attention
   int64_t dz = 0, rz = 0, rcat = 0, ties = 0;    // readout
@@ -530,6 +531,9 @@ TrainScratch train_scratch(const ign_plan* p, const ign_batch* b) {
       if (p->bwd_fuse && seq_bwd_fused_supported(H)) z.part = std::max(z.part, seq_bwd_partial_floats(H));
       for (int s = 0; s < S; ++s) {
         z.dtab = std::max(z.dtab, mb.src_rows[s] * 3 * H);
+        if (p->conv_F && mp.nn[s].layers.empty())
+          z.rsrc = std::max(z.rsrc, train_keys(mp, s, b->rows, b->halo, mb.n_edges) *
+                                        (mp.feature_concat ? p->ents[mp.src[s].entity].hidden_dim : DIN));
         need_part(mb.src_rows[s], mp.feature_concat ? p->ents[mp.src[s].entity].hidden_dim : DIN, 3 * H);
       }
     } else {
@@ -604,6 +608,7 @@ int alloc_mp_scratch(const ign_plan* p, TrainState* t, const TrainScratch& z) {
   if ((rc = talloc(t, &t->ga, z.ga)) || (rc = talloc(t, &t->gu, z.gu)) || (rc = talloc(t, &t->dx, z.dx)) ||
       (rc = talloc(t, &t->dtab, z.dtab)))
     return rc;
+  if (z.rsrc && (rc = talloc(t, &t->rsrc, z.rsrc))) return rc;
   if (z.amsg && ((rc = talloc(t, &t->adw, z.amsg)) || (rc = talloc(t, &t->adv, z.amsg)) ||
                  (rc = talloc(t, &t->ads_src, z.arows)) || (rc = talloc(t, &t->ads_dst, z.arows)) ||
                  (rc = talloc(t, &t->adw12, 2 * p->attn_F))))
@@ -1021,14 +1026,23 @@ int ign_backward_mp(ign_plan* p, ign_batch* b) {
         HIP_TRY(launch_csr_gather_add(t->dtab, mt.trows[s], mt.tptr[s], mt.tidx[s], t->ga, H3, 0, st));
         const bool net = !mp.nn[s].layers.empty();
         float* target = net ? t->dmsg : se == dst ? dh_out : t->dS[dcur[se]][se];
+        // dW = x^T dtab over the source rows.  A row that no step reads has a zero dtab row, but in a plan
+        // with a convolution MP it may hold 0 / 0 (a destination without a message, AUX:384-401): NaN * 0.
+        // Autograd gathers the read rows only, so there the unread rows enter as zeros
+        const float* xs = srcs[s];
+        if (t->rsrc && !net) {
+          HIP_TRY(launch_read_rows(srcs[s], mt.tptr[s], mt.trows[s], mp.feature_concat ? p->ents[se].hidden_dim : DIN,
+                                   t->rsrc, st));
+          xs = t->rsrc;
+        }
         if (mp.feature_concat) {   // AUX:443-456: the source's slice of the input kernel
           const int sdin = p->ents[se].hidden_dim;
           const int64_t koff = (int64_t)mp.slice_off[s] * H3;
-          HIP_TRY(launch_tsgemm_add(srcs[s], sdin, t->dtab, H3, mt.trows[s], sdin, H3, t->part, gk + koff, nullptr, st));
+          HIP_TRY(launch_tsgemm_add(xs, sdin, t->dtab, H3, mt.trows[s], sdin, H3, t->part, gk + koff, nullptr, st));
           HIP_TRY(launch_row_gemm_t_generic(t->dtab, mt.trows[s], H3, p->d_params + cp.off_k + koff, sdin, target,
                                             net ? 0 : 1, -1, nullptr, st));
         } else {
-          if ((rc = tsgemm_deferred(t, srcs[s], DIN, t->dtab, H3, mt.trows[s], DIN, H3, gk, nullptr, st))) return rc;
+          if ((rc = tsgemm_deferred(t, xs, DIN, t->dtab, H3, mt.trows[s], DIN, H3, gk, nullptr, st))) return rc;
           HIP_TRY(launch_row_gemm_t(t->dtab, mt.trows[s], H3, p->d_packed + cp.pk_wt, DIN, target, net ? 0 : 1, -1,
                                     nullptr, st));
         }

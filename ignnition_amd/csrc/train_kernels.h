@@ -90,6 +90,8 @@ hipError_t launch_attn_param_bwd(const float* dw12, const float* K1, const float
 // convolution backward, elementwise: du = dx act'(x) / deg[row]; dh += du  ([n][F], rows by dst row)
 hipError_t launch_conv_bwd(const float* dx, const float* x, const float* deg, int64_t n, int F, int act, float* du,
                            float* dh, hipStream_t st);
+// out[n_rows][F] = in, the rows without a CSR entry (ptr[r] == ptr[r + 1]) as zeros
+hipError_t launch_read_rows(const float* in, const int32_t* ptr, int64_t n_rows, int F, float* out, hipStream_t st);
 // out[r][0:width] (+)= sum over the CSR list of r of in[idx][col0 : col0 + width] (row stride in_stride)
 hipError_t launch_csr_gather_cols_add(float* out, int64_t n_rows, const int32_t* ptr, const int32_t* idx,
                                       const float* in, int in_stride, int col0, int width, int accumulate,

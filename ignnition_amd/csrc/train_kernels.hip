@@ -802,14 +802,28 @@ __global__ void attn_param_bwd_kernel(const float* __restrict__ dw12, const floa
 
 // Convolution aggregation backward, elementwise part (AUX:384-401): x = act((s.K + h) / deg), so
 // du = dx act'(x) / deg (act' through the output x), and the destination's own state gets du.
+// A destination without a message (deg 0, x = 0 / 0) passes its non-finite du to its own state alone:
+// no message's s.K reaches it, so its row of du is 0 for the kernel's and the sources' gradients.
 __global__ void conv_bwd_kernel(const float* __restrict__ dx, const float* __restrict__ x,
                                 const float* __restrict__ deg, int64_t n, int F, int act, float* __restrict__ du,
                                 float* __restrict__ dh) {
   const int64_t total = n * F;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const float v = dx[i] * act_grad(x[i], act) / deg[i / F];
-    du[i] = v;
+    const float d = deg[i / F];
+    const float v = dx[i] * act_grad(x[i], act) / d;
+    du[i] = d > 0.f ? v : 0.f;
     dh[i] += v;
+  }
+}
+
+// out = in with the rows that no CSR entry reads (ptr[r] == ptr[r + 1]) as zeros: a source row without a
+// message has no part in a weight gradient, whatever it holds (an idle convolution destination holds 0 / 0)
+__global__ void read_rows_kernel(const float* __restrict__ in, const int32_t* __restrict__ ptr, int64_t n_rows, int F,
+                                 float* __restrict__ out) {
+  const int64_t total = n_rows * F;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = e / F;
+    out[e] = ptr[r] == ptr[r + 1] ? 0.f : in[e];
   }
 }
 
@@ -1522,6 +1536,12 @@ hipError_t launch_conv_bwd(const float* dx, const float* x, const float* deg, in
                            float* dh, hipStream_t st) {
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(conv_bwd_kernel, dim3(blocks_for(n * F)), dim3(256), 0, st, dx, x, deg, n, F, act, du, dh);
+  return hipGetLastError();
+}
+
+hipError_t launch_read_rows(const float* in, const int32_t* ptr, int64_t n_rows, int F, float* out, hipStream_t st) {
+  if (n_rows == 0) return hipSuccess;
+  hipLaunchKernelGGL(read_rows_kernel, dim3(blocks_for(n_rows * F)), dim3(256), 0, st, in, ptr, n_rows, F, out);
   return hipGetLastError();
 }
 

@@ -41,10 +41,10 @@ def routenet_aggregation(aggregation: dict, hidden: int = 32, iterations: int = 
     return d
 
 
-def qsize_aggregation(aggregation: dict, iterations: int = 8) -> dict:
+def qsize_aggregation(aggregation: dict, iterations: int = 8, hidden: int = 32) -> dict:
     """Q-size with the {link, node} -> path stage aggregated by ``aggregation`` instead of
     interleave: a two-source attention / convolution (AUX:264-401 with GM:523-541)."""
-    d = qsize(iterations=iterations)
+    d = qsize(hidden=hidden, iterations=iterations)
     mp = d["message_passing"]["stages"][0]["stage_mp"][0]
     mp["aggregation"] = dict(aggregation)
     if aggregation.get("type") == "concat":

@@ -100,6 +100,7 @@ class DenseOracle:
         self.dtype = dtype
         self.p = {k: np.asarray(v, dtype) for k, v in params.items()}
         self.nn = {n["nn_name"]: n for n in description["neural_networks"]}
+        self.scores = None   # a list: every attention MP appends its [num_dst, positions] scores before the softmax
 
     # ------------------------------------------------------------------------------------
     def forward_graph(self, x: dict) -> np.ndarray:
@@ -228,7 +229,9 @@ class DenseOracle:
             ai = np.where(ai > 0, ai, 0.2 * ai)                           # LeakyReLU(alpha=0.2)
             max_len = int(comb_seq.max()) + 1
             aux = _scatter_nd(comb_dst, comb_seq, ai, (num_dst, max_len, 1))
-            aux = aux - aux.max(axis=0, keepdims=True)                    # softmax over axis 0 (AUX:336)
+            if self.scores is not None:
+                self.scores.append(aux[:, :, 0].copy())
+            aux = aux - aux.max(axis=0, keepdims=True)                   # softmax over axis 0 (AUX:336)
             coef = np.exp(aux) / np.exp(aux).sum(axis=0, keepdims=True)
             fc = coef[comb_dst, comb_seq]                                 # gather_nd, [E, 1]
             src_input = np.zeros((num_dst, comb_src.shape[1]), dt)

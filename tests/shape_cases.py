@@ -67,14 +67,22 @@ def _check_degrees(deg, n, idle, hot, lens):
     assert np.all(deg[1 if hot is not None else 0:n] >= 1), "a row that is not idle is crossed by no path"
 
 
-def routenet_arrays(P, L, lens, seed, idle_links=0, hot=None):
+def routenet_arrays(P, L, lens, seed, idle_links=0, hot=None, link_positions=()):
     """One RouteNet input dict: P paths over L crossed links (+ idle_links that no path crosses), path p
     over lens[p] distinct links at positions 0 .. lens[p] - 1 (no holes, so sequence_mask(final_len) is as
-    wide as the padding); hot=k: link 0 is crossed by exactly k paths.  Features uniform in [-1, 1)."""
+    wide as the padding); hot=k: link 0 is crossed by exactly k paths.  Features uniform in [-1, 1).
+    link_positions: (link, positions) pairs that replace the seq_path_link values 0 .. deg - 1 of that
+    link's messages (in path order): a repeated value puts two messages into one (link, position) cell,
+    a skipped one leaves a position that this link does not fill."""
     rng = np.random.default_rng(seed)
     routes = _route(P, L, lens, rng, hot)
     g, deg = _adjacency(routes, P, L + idle_links, "link")
     _check_degrees(deg, L, idle_links, hot, lens)
+    for link, positions in link_positions:
+        at = np.flatnonzero(np.asarray(g["dst_adj_paths_links"]) == link)
+        assert at.size == len(positions), "link %d has %d messages, not %d" % (link, at.size, len(positions))
+        for k, q in zip(at, positions):
+            g["seq_path_link"][k] = np.int64(q)
     assert max(g["seq_link_path"]) + 1 == int(np.max(lens))
     assert np.array_equal(np.bincount(g["dst_adj_links_paths"], minlength=P), np.asarray(lens))
     g.update(link_capacity=rng.uniform(-1, 1, L + idle_links).astype(np.float32),

@@ -5,7 +5,7 @@ fixed seeded vector).
     python tools/ab_bitwise.py base new [--graphs 512] [--model routenet] [--topology synth50] [--train]
 --cases runs the models of the tests' case modules instead (predict_cases and its H = 64 model, test_gpu_dropout's GRAD_CASES
 with its mask stream, layernorm_cases' GRAD_CASES, readout_cases, test_gpu_training's message-network
-parameter sets), all of them in one process per library, and compares per case the training forward's
+parameter sets, aggregation_cases' table), all of them in one process per library, and compares per case the training forward's
 predictions and the flat gradient of one backward; for the H = 64, LayerNormalization, readout-operation
 and message-network cases the inference forward too.
 (Against a parent commit: tools/build_ab.sh base in a checkout of it, its lib_base.so copied to this ab/.)
@@ -82,6 +82,10 @@ def cases():
         desc["message_passing"]["stages"][1]["stage_mp"][0]["aggregation"] = {"type": "attention"}
         prm = MPPlan.from_model_info(Model_information(copy.deepcopy(desc), dims)).init_params(8, bias_scale=0.1)
         yield "attention_msgnet/%d" % k, desc, dims, graphs, prm, None, True
+    from tests import aggregation_cases as ac   # attention, convolution and concat MPs on their kernels' edges
+    for c in sorted(ac.CASES):
+        desc, dims, _, _, graphs, _, prm = ac.case_inputs(c)
+        yield "aggregation/" + c, desc, dims, graphs, prm, None, True
 
 
 def run_cases(out):
