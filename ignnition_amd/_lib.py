@@ -117,7 +117,8 @@ SYMBOLS = ["ign_abi_version", "ign_last_error", "ign_device_count", "ign_plan_cr
            "ign_forward_train_end", "ign_backward_begin", "ign_backward_mp", "ign_backward_end",
            "ign_batch_train_buffers", "ign_batch_read_predictions", "ign_batch_resident_info",
            "ign_loss_kind", "ign_optimizer_kind", "ign_loss", "ign_optimizer_num_slots", "ign_optimizer_step",
-           "ign_plan_add_dropout", "ign_batch_set_dropout", "ign_dropout_keep", "ign_plan_add_layernorm"]
+           "ign_plan_add_dropout", "ign_batch_set_dropout", "ign_dropout_keep", "ign_plan_add_layernorm",
+           "ign_plan_mp_dead_last"]
 
 ABI_VERSION = 13
 PART = {"all": 0, "interior": 1, "boundary": 2}
@@ -202,6 +203,7 @@ def _load():
         "ign_plan_add_layernorm": (C.c_int, [VP, i32, i32, f32, i32, i32]),
         "ign_batch_set_dropout": (C.c_int, [VP, C.c_uint64, C.c_uint32]),
         "ign_dropout_keep": (C.c_int, [C.c_uint64, i32, C.c_uint32, i64, i64, f32, P(C.c_uint8)]),
+        "ign_plan_mp_dead_last": (C.c_int, [VP, i32, P(i32)]),
     }
     # an A/B build of an older tree may lack newer entry points: only the A/B tools, which set
     # IGN_AB_LIB=1 next to IGN_LIB_PATH, skip them; any other library must export every symbol

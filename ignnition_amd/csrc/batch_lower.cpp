@@ -799,50 +799,60 @@ void lower_resident(const ResidentParams& sh, int K, const BatchRows& bb, const 
   out->form = form;
   out->G = G;
   out->K = K;
-  // the cost model of one launch (ign_batch_resident_info)
-  ign_resident_info_t& ri = out->info;
-  ri = ign_resident_info_t{};
-  ri.active = 1;
-  ri.form = form;
-  ri.lds_bytes = (int64_t)lds[form];
-  ri.tile_steps = (int64_t)(tile_steps * sh.T);
-  ri.seg_rows = seg_rows;
-  ri.messages = lmsg_off[G];
-  double utiles = 0;
-  for (int g = 0; g < G; ++g) utiles += (double)((Ls(0, g) + 15) / 16 + (Ls(1, g) + 15) / 16);
-  ri.union_tiles = (int64_t)utiles;
-  // compulsory: the features, tile headers, step codes and the sum CSR read once, the final states
-  // written once
-  const int64_t P = b->rows[path], Urows = uo[G];
-  double feat = 4.0 * P * sh.feature_total[path];
-  for (int s = 0; s < S; ++s) feat += 4.0 * b->rows[sh.src_ent[s]] * sh.feature_total[sh.src_ent[s]];
-  ri.bytes_compulsory = feat + 4.0 * hdr.size() + 2.0 * (double)lcode.size() + 4.0 * lmsg_ptr.size() +
-                        2.0 * lmsg_src.size() + 4.0 * 32 * (P + Urows);
-  // global-path forms: every iteration moves each path row once in and out of the ordered update and
-  // once per message into the sums (rows of 128 B) and reads the step codes again; the CSR-global
-  // form also reads the message rows every iteration
-  if (form != kResAllLds)
-    ri.bytes_roundtrip = sh.T * (128.0 * (2.0 * P + (double)lmsg_src.size()) + 2.0 * (double)lcode.size());
-  if (form == kResPathCsrGlobal) ri.bytes_roundtrip += sh.T * 2.0 * (double)lmsg_src.size();
-  // B_stage of every MP (MPB::bytes), T times
-  double stage = ma.bytes, mflops = ma.flops;
-  for (int s = 0; s < S; ++s) {
-    stage += sums[s].bytes;
-    mflops += sums[s].flops;
+  // the cost model of one launch (ign_batch_resident_info): source s's sum MP runs Ts[s] times, T
+  // less the last iteration's update where it is dead
+  double utiles_s[kResMaxSrc] = {0, 0}, utiles = 0, ptiles = 0;
+  for (int g = 0; g < G; ++g) {
+    for (int s = 0; s < S; ++s) utiles_s[s] += (double)((Ls(s, g) + 15) / 16);
+    ptiles += (double)((uo[g + 1] - uo[g] + 15) / 16);
   }
-  ri.bytes_stage = sh.T * stage;
-  // the MPs' FLOPs per iteration plus the ordered MP's input projection of every union row
-  ri.flops = sh.T * (mflops + 2.0 * Urows * 32 * 96);
-  // the matrix pipe: phase A's split-fp16 h.U (3 products x 3 gates x 2 tiles per tile-step), the
-  // split-bf16 GRU step (2 x 36 per tile), the projection (3 gates x 2 x 6, T - 1 times), all
-  // 16x16x32; iteration 0's projection on f32 MFMA (3 gates x 2 tiles x 8 k-steps per union tile;
-  // the projection's tiles straddle the entities, ceil(U / 16) per graph)
-  double ptiles = 0;
-  for (int g = 0; g < G; ++g) ptiles += (double)((uo[g + 1] - uo[g] + 15) / 16);
-  ri.mfma_bf16 = (sh.T * (tile_steps * 18.0 + utiles * 72.0) + (sh.T - 1) * utiles * 36.0) * kMfmaBf16Flops;
-  ri.mfma_f32 = ptiles * 48.0 * kMfmaF32Flops;
-  ri.workgroups = G;
-  ri.graphs_per_workgroup = K;
+  for (int s = 0; s < S; ++s) utiles += utiles_s[s];
+  const int64_t P = b->rows[path], Urows = uo[G];
+  auto cost = [&](const bool* dead, ign_resident_info_t& ri) {
+    ri = ign_resident_info_t{};
+    ri.active = 1;
+    ri.form = form;
+    ri.lds_bytes = (int64_t)lds[form];
+    ri.tile_steps = (int64_t)(tile_steps * sh.T);
+    ri.seg_rows = seg_rows;
+    ri.messages = lmsg_off[G];
+    ri.union_tiles = (int64_t)utiles;
+    // compulsory: the features, tile headers, step codes and the sum CSR read once, the final states
+    // written once
+    double feat = 4.0 * P * sh.feature_total[path];
+    for (int s = 0; s < S; ++s) feat += 4.0 * b->rows[sh.src_ent[s]] * sh.feature_total[sh.src_ent[s]];
+    ri.bytes_compulsory = feat + 4.0 * hdr.size() + 2.0 * (double)lcode.size() + 4.0 * lmsg_ptr.size() +
+                          2.0 * lmsg_src.size() + 4.0 * 32 * (P + Urows);
+    // global-path forms: every iteration moves each path row once in and out of the ordered update and
+    // once per message into the sums (rows of 128 B) and reads the step codes again; the CSR-global
+    // form also reads the message rows every iteration.  SURVEY §8(d): B_stage of every MP
+    // (MPB::bytes), as often as it runs; the MPs' FLOPs likewise, plus the ordered MP's input
+    // projection of every union row (T times: before iteration 0, then after every update but the last)
+    double msg_trips = 0, stage = sh.T * ma.bytes, mflops = sh.T * ma.flops, step_tiles = 0;
+    for (int s = 0; s < S; ++s) {
+      const int Ts = sh.T - (dead[s] ? 1 : 0);
+      msg_trips += Ts * (double)sums[s].h_msg_src.size();
+      stage += Ts * sums[s].bytes;
+      mflops += Ts * sums[s].flops;
+      step_tiles += Ts * utiles_s[s];
+    }
+    if (form != kResAllLds)
+      ri.bytes_roundtrip = 128.0 * (sh.T * 2.0 * P + msg_trips) + sh.T * 2.0 * (double)lcode.size();
+    if (form == kResPathCsrGlobal) ri.bytes_roundtrip += 2.0 * msg_trips;
+    ri.bytes_stage = stage;
+    ri.flops = mflops + sh.T * 2.0 * Urows * 32 * 96;
+    // the matrix pipe: phase A's split-fp16 h.U (3 products x 3 gates x 2 tiles per tile-step), the
+    // split-bf16 GRU step (2 x 36 per tile), the projection (3 gates x 2 x 6, T - 1 times), all
+    // 16x16x32; iteration 0's projection on f32 MFMA (3 gates x 2 tiles x 8 k-steps per union tile;
+    // the projection's tiles straddle the entities, ceil(U / 16) per graph)
+    ri.mfma_bf16 = (sh.T * tile_steps * 18.0 + step_tiles * 72.0 + (sh.T - 1) * utiles * 36.0) * kMfmaBf16Flops;
+    ri.mfma_f32 = ptiles * 48.0 * kMfmaF32Flops;
+    ri.workgroups = G;
+    ri.graphs_per_workgroup = K;
+  };
+  const bool none[kResMaxSrc] = {false, false};
+  cost(sh.dead_last, out->info);
+  cost(none, out->info_full);
   out->eligible = true;
 }
 

@@ -82,6 +82,7 @@ struct ResidentParams {
   int T = 0, sum_window = -1;
   bool path_global_ok = true;          // plan->resident_pg
   bool force_path_global = false;      // plan->resident_path_global
+  bool dead_last[kResMaxSrc] = {false, false};   // source s's last sum update is left out (the cost model)
   // the kernel's limits (kernels.h)
   int max_tiles = 0, state_stride = 0, table_stride = 0;
   size_t max_dyn_lds = 0;
@@ -108,7 +109,8 @@ struct ResidentTables {
   std::vector<int64_t> path_off, src_off[kResMaxSrc], urow_off;
   hvec<int32_t> ptile_off, hdr, hsb, lmsg_off, lmsg_ptr, lnseg, gorder, lcode_off;
   hvec<uint16_t> lmsg_src, lorder, lcode;
-  ign_resident_info_t info{};
+  ign_resident_info_t info{};          // the cost model of one launch as rp.dead_last says
+  ign_resident_info_t info_full{};     // ... with every update (the training forward's launch)
 };
 struct BatchRows {   // views of the batch's G, row_off, rows, halo (BatchShape's, or the ign_batch's copies)
   int G;

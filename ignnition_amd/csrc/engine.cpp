@@ -244,6 +244,7 @@ static PlanSwitches switches_from_env() {
     s.seq_variant = sv == 2 || sv == 4 ? sv : 6;
   }
   flag("IGN_HIP_GRAPH", &s.use_graph);
+  flag("IGN_DEAD_LAST", &s.dead_last);
   if (const char* v = getenv("IGN_SUM_VARIANT")) s.sum_variant = atoi(v) == 7 || atoi(v) == 8 ? atoi(v) : 3;
   if (const char* v = getenv("IGN_SUM_WINDOW")) s.sum_window = atoi(v);
   if (const char* v = getenv("IGN_RESIDENT")) {   // 0 off; 1 default; 2 also force the global-path form
@@ -370,6 +371,13 @@ int ign_plan_param_tensor(const ign_plan* p, int32_t i, int32_t* kind, int32_t* 
   if (offset) *offset = t.offset;
   if (rows) *rows = t.rows;
   if (cols) *cols = t.cols;
+  return IGN_OK;
+}
+
+int ign_plan_mp_dead_last(const ign_plan* p, int32_t mi, int32_t* dead) {
+  if (!p || !dead) return fail(IGN_ERR_INVALID, "null argument");
+  if (mi < 0 || mi >= (int)p->mps.size()) return fail(IGN_ERR_INVALID, "mp index %d out of range", mi);
+  *dead = p->mps[mi].dead_in_last_iter;
   return IGN_OK;
 }
 
@@ -609,6 +617,8 @@ int ign_batch_create(ign_plan* p, const ign_batch_desc* d, ign_batch** out) {
   b->d_state[0].assign(E, nullptr);
   b->d_state[1].assign(E, nullptr);
   b->cur.assign(E, 0);
+  b->behind.assign(E, -1);
+  b->ext_state.assign(E, 0);
   for (int e = 0; e < E; ++e) {
     const int H = p->ents[e].hidden_dim, F = p->ents[e].feature_total;
     if (F > 0) {
@@ -759,15 +769,15 @@ int ign_forward_begin(ign_plan* p, ign_batch* b) {
     HIP_TRY(launch_init_state(b->d_state[0][e], b->d_feat[e], b->rows[e], H, F, p->stream));
     tm.end();
     b->cur[e] = 0;
+    b->behind[e] = -1;
   }
   return IGN_OK;
 }
 
-int ign_forward_mp(ign_plan* p, ign_batch* b, int32_t mi, int32_t part) {
-  int rc = check_pb(p, b);
-  if (rc) return rc;
-  if (mi < 0 || mi >= (int)p->mps.size()) return fail(IGN_ERR_INVALID, "mp index %d out of range", mi);
-  if (part < IGN_PART_ALL || part > IGN_PART_BOUNDARY) return fail(IGN_ERR_INVALID, "part %d", part);
+namespace {
+
+// MP instance mi on the batch's current states (ign_forward_mp's work)
+int forward_mp(ign_plan* p, ign_batch* b, int32_t mi, int32_t part) {
   const MPP& mp = p->mps[mi];
   const int dst = mp.dst;
   MpStates s;
@@ -778,9 +788,36 @@ int ign_forward_mp(ign_plan* p, ign_batch* b, int32_t mi, int32_t part) {
   s.hin = b->d_state[b->cur[dst]][dst];
   s.hout = b->d_state[1 - b->cur[dst]][dst];
   Timer tm{p};
-  if ((rc = mp_forward(p, b, mi, part, s, MpSave{}, tm))) return rc;
+  if (int rc = mp_forward(p, b, mi, part, s, MpSave{}, tm)) return rc;
   if (part != IGN_PART_INTERIOR) b->cur[dst] ^= 1;   // GM:602: the destination state is overwritten
   return IGN_OK;
+}
+
+// Entity e's states as a forward that runs every MP leaves them: where ign_forward left the last
+// iteration's update of e out (b->behind), it runs now, once, on the plan's stream and outside any
+// captured graph, through the same MP step from the same inputs -- nothing the MP reads has changed
+// since (mark_dead_last) -- so the states are the eager forward's bits, on the batched and on the
+// resident route (whose rows are the batched forward's bits).
+int finish_entity(ign_plan* p, ign_batch* b, int e) {
+  const int mi = b->behind[e];
+  if (mi < 0) return IGN_OK;
+  if (int rc = check_pb(p, b)) return rc;
+  if (int rc = forward_mp(p, b, mi, IGN_PART_ALL)) return rc;
+  b->behind[e] = -1;
+  return IGN_OK;
+}
+
+}  // namespace
+
+int ign_forward_mp(ign_plan* p, ign_batch* b, int32_t mi, int32_t part) {
+  int rc = check_pb(p, b);
+  if (rc) return rc;
+  if (mi < 0 || mi >= (int)p->mps.size()) return fail(IGN_ERR_INVALID, "mp index %d out of range", mi);
+  if (part < IGN_PART_ALL || part > IGN_PART_BOUNDARY) return fail(IGN_ERR_INVALID, "part %d", part);
+  // stepping on after an ign_forward: from the states every MP of that forward leaves
+  for (int e = 0; e < (int)p->ents.size(); ++e)
+    if ((rc = finish_entity(p, b, e))) return rc;
+  return forward_mp(p, b, mi, part);
 }
 
 namespace {
@@ -922,6 +959,10 @@ extern "C++" int ign::resident_launch(ign_plan* p, ign_batch* b, const ResidentS
   r.proj_Wf = p->d_packed + ca.pk_w;
   r.T = p->T;
   r.seg_on = save ? 0 : 1;   // the training forward's sums are all lane walks (sum_gru_g32 with x_save)
+  // the last iteration's sum updates nothing reads (the training forward keeps them: its backward
+  // reads every saved version)
+  for (int s = 0; s < sh.n_src && !save; ++s)
+    if (skips_last(p, b, sh.sum_mp[s])) r.dead_last |= 1 << s;
   if (save) {
     r.path_ver = save->path_ver;
     r.hs_save = save->hs_save;
@@ -934,7 +975,7 @@ extern "C++" int ign::resident_launch(ign_plan* p, ign_batch* b, const ResidentS
       r.x_save[s] = save->x_save[s];
     }
   }
-  const ign_resident_info_t& ri = b->res_info;
+  const ign_resident_info_t& ri = save ? b->res_info_full : b->res_info;
   Timer tm{p};
   tm.begin(K_RESIDENT, ri.flops, ri.bytes_stage, ri.mfma_bf16, ri.mfma_f32);
   HIP_TRY(launch_resident_forward(r, b->res_graphs, save ? b->res_train_lds : b->res_lds, save ? b->res_train_form : b->res_form,
@@ -942,7 +983,11 @@ extern "C++" int ign::resident_launch(ign_plan* p, ign_batch* b, const ResidentS
   tm.end();
   if (!save) {
     b->cur[path] = 0;
-    for (int s = 0; s < sh.n_src; ++s) b->cur[sh.src_ent[s]] = 0;
+    b->behind[path] = -1;
+    for (int s = 0; s < sh.n_src; ++s) {
+      b->cur[sh.src_ent[s]] = 0;
+      b->behind[sh.src_ent[s]] = r.dead_last >> s & 1 ? sh.sum_mp[s] : -1;
+    }
   }
   return IGN_OK;
 }
@@ -970,6 +1015,7 @@ static int resident_upload(ign_batch* b, const ResidentTables& t, int S) {
   b->res_form = t.form;
   b->res_graphs = t.G;
   b->res_info = t.info;
+  b->res_info_full = t.info_full;
   b->resident = true;
   return IGN_OK;
 }
@@ -999,6 +1045,7 @@ static int resident_batch(ign_plan* p, ign_batch* b) {
   std::vector<ResSumIn> sums;
   for (int s = 0; s < sh.n_src; ++s) {
     rp.src_ent[s] = sh.src_ent[s];
+    rp.dead_last[s] = skips_last(p, b, sh.sum_mp[s]);
     const MPB& m = b->mp[sh.sum_mp[s]];
     sums.push_back(ResSumIn{m.h_order, m.h_msg_ptr, m.h_msg_src, m.flops, m.bytes});
   }
@@ -1045,8 +1092,10 @@ int forward_body(ign_plan* p, ign_batch* b) {
   b->fuse_ok = p->fuse_proj;
   for (int it = 0; it < p->T && !rc; ++it) {            // GM:406
     b->fuse_last_iter = it + 1 == p->T;
+    // every MP of every iteration, a dead last update included (the resident launch alone leaves
+    // those out): T launches per MP is what the per-kind launch statistics of this route state
     for (int mi = 0; mi < (int)p->mps.size() && !rc; ++mi)   // GM:410-414 (stages flattened in order)
-      rc = ign_forward_mp(p, b, mi, IGN_PART_ALL);
+      rc = forward_mp(p, b, mi, IGN_PART_ALL);
   }
   b->fuse_ok = false;
   return rc ? rc : readout(p, b);
@@ -1076,6 +1125,8 @@ int capture(ign_plan* p, ign_batch* b) {
     return fail(IGN_ERR_DEVICE, "hipGraphInstantiate: %s", hipGetErrorString(e));
   }
   b->graph_timing = p->timing;
+  b->graph_cur = b->cur;
+  b->graph_behind = b->behind;
   const int n = p->timing ? p->ev_slot : 0;
   b->graph_kind.assign(p->ev_kind.begin(), p->ev_kind.begin() + n);
   b->graph_cost.assign(p->ev_cost.begin(), p->ev_cost.begin() + n);
@@ -1107,6 +1158,8 @@ int ign_forward(ign_plan* p, ign_batch* b, float* pred_out) {
       }
     }
     HIP_TRY(hipGraphLaunch(b->graph, p->stream));
+    b->cur = b->graph_cur;   // where the captured launches leave the states (a finish_entity since
+    b->behind = b->graph_behind;   // the capture moved an entity's slot), and which are behind again
     if ((rc = copy_out(p, b, pred_out))) return rc;
     if (p->timing)
       return accumulate_stats(p, (int)b->graph_kind.size(), b->graph_kind.data(), b->graph_cost.data());
@@ -1146,6 +1199,10 @@ int ign_batch_bind_state(ign_plan* p, ign_batch* b, int32_t e, float* dev0, floa
   b->d_state[0][e] = dev0;
   b->d_state[1][e] = dev1;
   b->cur[e] = 0;
+  // the caller reads these buffers itself and cannot ask for a left-out update: from here on every
+  // MP into e runs in every iteration (skips_last)
+  b->ext_state[e] = 1;
+  b->behind[e] = -1;
   return IGN_OK;
 }
 
@@ -1180,6 +1237,8 @@ int ign_batch_state(ign_plan* p, ign_batch* b, int32_t e, float* host_out) {
   if (e < 0 || e >= (int)p->ents.size()) return fail(IGN_ERR_INVALID, "entity index");
   int rc = set_device(p->device);
   if (rc) return rc;
+  if (b->plan != p) return fail(IGN_ERR_INVALID, "batch was created for another plan");
+  if ((rc = finish_entity(p, b, e))) return rc;   // the last iteration's update, if ign_forward left it out
   HIP_TRY(hipMemcpyAsync(host_out, b->d_state[b->cur[e]][e], b->rows[e] * p->ents[e].hidden_dim * sizeof(float),
                          hipMemcpyDeviceToHost, p->stream));
   HIP_TRY(hipStreamSynchronize(p->stream));

@@ -182,6 +182,11 @@ struct ign_batch {
   std::vector<float*> d_feat;                   // per entity [rows][F] or null
   std::vector<float*> d_state[2];               // per entity ping-pong
   std::vector<int> cur;
+  // per entity: the MP whose last-iteration update the resident ign_forward left out (MPP::dead_in_last_iter), so
+  // the entity's states are one update behind until finish_entity runs it; -1: they are final
+  std::vector<int> behind;
+  std::vector<char> ext_state;                  // per entity: ign_batch_bind_state's buffers, read by others
+                                                // who cannot ask for that update: its MPs always run
   std::vector<MPB> mp;
   // forward_body only: a sum update may project its new states for the next ordered MP that reads
   // them (fused_proj_target); proj_ready[m'] tells m' that its table is already filled
@@ -194,7 +199,8 @@ struct ign_batch {
   int res_form = 0;               // IGN_RES_ALL_LDS / IGN_RES_PATH_GLOBAL / IGN_RES_PATH_CSR_GLOBAL
   int res_graphs = 0;             // resident workgroups per launch (graphs / IGN_RES_GROUP)
   ign_resident_info_t res_info{}; // per launch: bytes (compulsory, round trips, SURVEY B_stage), FLOPs,
-                                  // MFMA FLOPs, tile-steps (ign_batch_resident_info)
+                                  // MFMA FLOPs, tile-steps (ign_batch_resident_info): what ign_forward runs
+  ign_resident_info_t res_info_full{};   // ... with every update of the last iteration (the training forward)
   int64_t* d_res_path_off = nullptr;
   int64_t* d_res_src_off[kResidentMaxSrc] = {nullptr, nullptr};
   int64_t* d_res_urow_off = nullptr;
@@ -229,6 +235,7 @@ struct ign_batch {
   uint32_t drop_step = 0;                       // mask stream (never set: (0, 0))
   // captured ign_forward (init .. readout) for replay; the event slots it records
   hipGraphExec_t graph = nullptr;
+  std::vector<int> graph_cur, graph_behind;     // cur / behind as the captured forward leaves them (each replay)
   bool graph_timing = false;
   std::vector<int> graph_kind;
   std::vector<EvCost> graph_cost;
@@ -246,6 +253,10 @@ struct ResidentSave {
 int resident_tables(ign_plan* p, ign_batch* b);   // once per batch; leaves b->resident false if not eligible
 int resident_launch(ign_plan* p, ign_batch* b, const ResidentSave* save);
 int resident_sum_mps(const ign_plan* p, int* sum_mp, int* n_src);   // 0: not a resident plan shape
+// the resident ign_forward leaves MP mi out of its last iteration and marks its destination behind
+inline bool skips_last(const ign_plan* p, const ign_batch* b, int mi) {
+  return p->dead_last && p->mps[mi].dead_in_last_iter && !b->ext_state[p->mps[mi].dst];
+}
 int set_device(int dev);
 int ensure_device(ign_plan* p);
 int dev_alloc(ign_batch* b, float** out, int64_t n);

@@ -106,6 +106,8 @@ struct MPP {
   std::vector<int> slice_off;     // feature_concat: first kernel row of each source's slice
   std::vector<int64_t> pk_slice;  // feature_concat: packed W-slice fragments per source
   std::vector<MsgNN> nn;          // per source; no layers = direct_assignation
+  bool dead_in_last_iter = false; // nothing reads the destination's states after the last iteration's
+                                  // update (plan_lower.cpp mark_dead_last): the resident forward leaves it out
 };
 
 // one index array of an ign_batch_desc (adj_src / adj_dst / adj_seq / interleave_idx): int32

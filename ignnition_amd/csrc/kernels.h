@@ -212,6 +212,10 @@ struct ResidentArgs {
   int T;
   int n_src;
   int seg_on;                 // 0: every message sum as the lane walk (the training forward's sums)
+  int dead_last;              // bit s: nothing reads source entity s's states after the last iteration
+                              // (MPP::dead_in_last_iter), so its last sum update is left out and
+                              // src_state[s] leaves after T - 1 updates (T = 1: [features | zeros]);
+                              // every source dead: the last iteration ends with phase A.  0 with SAVE
   // SAVE (the training forward, global-path forms): iteration it's ordered MP reads the path states
   // path_ver[it] and writes path_ver[it + 1] and every step's state into hs_save[it] from row hsb of
   // each position (seq_gru_h16<SAVE>'s layout); the sum MPs write their message sums into

@@ -503,6 +503,29 @@ int add_site(PlanModel* p, int kind, int stack, int before_layer, DropSite d, No
 
 }  // namespace
 
+void mark_dead_last(PlanModel* p) {
+  const int NE = (int)p->ents.size(), n = (int)p->mps.size();
+  // the entities whose final states the readout reads: every input of every operation (whatever
+  // the operation does with it) and predict's inputs; tensor ids below NE are entity states
+  std::vector<char> read(NE, 0);
+  for (const RoOp& op : p->ro_ops)
+    for (int id : op.in)
+      if (id >= 0 && id < NE) read[id] = 1;
+  for (int id : p->ro_in)
+    if (id >= 0 && id < NE) read[id] = 1;
+  for (int mi = 0; mi < n; ++mi) {
+    MPP& mp = p->mps[mi];
+    bool dead = !read[mp.dst];
+    for (int m2 = mi + 1; m2 < n && dead; ++m2) {
+      const MPP& q = p->mps[m2];
+      if (q.dst == mp.dst) dead = false;          // its previous state (and, with a message network, hs_dest)
+      for (const auto& s : q.src) dead = dead && s.entity != mp.dst;
+      for (const auto& s : mp.src) dead = dead && s.entity != q.dst;   // mi's input would change under it
+    }
+    mp.dead_in_last_iter = dead;
+  }
+}
+
 int add_dropout(PlanModel* p, int stack, int before_layer, float rate, uint64_t layer_seed) {
   DropSite d;
   d.rate = rate;
@@ -527,6 +550,7 @@ int lower_plan(const ign_plan_desc* d, const PlanSwitches& sw, PlanModel* m) {
   static_cast<PlanSwitches&>(*m) = sw;
   int rc;
   if ((rc = lower_mps(d, m)) || (rc = lower_readout(d, m))) return rc;
+  mark_dead_last(m);
   layout_params(m);
   layout_packed(m);
   return IGN_OK;

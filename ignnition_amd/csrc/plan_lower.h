@@ -108,6 +108,8 @@ struct PlanSwitches {
                                   // Measured 0.120 vs 0.112 ms (RouteNet link update, 37 messages per link);
                                   // Q-size x512 7.33 -> 6.44 ms/step with both sum MPs windowed
   bool use_graph = true;          // replay ign_forward as one captured hipGraph; IGN_HIP_GRAPH=0 disables
+  bool dead_last = true;          // the resident ign_forward leaves out the last iteration's MPs that are dead_in_last_iter
+                                  // (ign_batch_state runs them on demand); IGN_DEAD_LAST=0: every MP runs
 };
 
 // One slot of d_packed and the pack launch that fills it from the raw parameters (ign::repack runs
@@ -195,6 +197,12 @@ int add_layernorm(PlanModel* p, int stack, int before_layer, float epsilon, int 
 
 // d + sw -> *m (a fresh PlanModel); IGN_OK or the refusal's code, its text in ign_last_error
 int lower_plan(const ign_plan_desc* d, const PlanSwitches& sw, PlanModel* m);
+// MPP::dead_in_last_iter of every MP (lower_plan calls it): a property of the model alone, whatever
+// PlanSwitches::dead_last says.  MP m into entity e is dead when no readout operation and no predict
+// input reads e's states, no later MP of the iteration reads them (as a source or as its own
+// destination), and no later MP writes an entity m reads: then the update can also run after the
+// forward, from the states the forward left, with the same result.  Anything else keeps the MP live.
+void mark_dead_last(PlanModel* m);
 
 inline bool act_ok(int a) { return a >= IGN_ACT_LINEAR && a <= IGN_ACT_TANH; }
 

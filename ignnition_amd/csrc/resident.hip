@@ -477,6 +477,18 @@ __global__ __launch_bounds__(64 * kW) void resident_forward_kernel(ResidentArgs 
     IGN_STAMP(t_b);
     s_aw += t_b - t_a;
 #endif
+    // the last iteration's sum updates that nothing reads (ResidentArgs::dead_last; `last` and `dl`
+    // are uniform over the workgroup).  All of them: the path states are final, phase B and its
+    // barriers are left out, and the union-row states leave one update behind
+    const bool last = it + 1 == a.T;
+    const int dl = !SAVE && last ? a.dead_last : 0;
+    if (dl != 0 && dl == (1 << a.n_src) - 1) {
+      if constexpr (!PG) __syncthreads();   // the epilogue copies every wave's path states out of LDS
+#ifdef IGN_RES_STAMP
+      t_a = t_b;
+#endif
+      break;
+    }
     __syncthreads();
 #ifdef IGN_RES_STAMP
     IGN_STAMP(t_a);
@@ -491,6 +503,7 @@ __global__ __launch_bounds__(64 * kW) void resident_forward_kernel(ResidentArgs 
     const int nseg = a.seg_on ? a.lnseg[gph] : 0;
     for (int k = wave; k < nseg; k += kW) {
       const int ll = slo[k];
+      if (dl >> (ll >= L0) & 1) continue;   // a dead update's row (wave-uniform): its sum is not read
       int lo = lane;   // opaque: the lane's column pointer stays inside the loop (no spill, as project_row)
       asm volatile("" : "+v"(lo));
       const int c = lo & 7, q = lo >> 3;
@@ -532,6 +545,7 @@ __global__ __launch_bounds__(64 * kW) void resident_forward_kernel(ResidentArgs 
     for (int64_t i = (int64_t)nseg * 8 + tlw; i < U * (H / 4); i += 64 * kW) {
       const int64_t ll = slo[i >> 3];   // rows by message count, descending: the long chains first
       const int c4 = (int)(i & 7);
+      if (dl >> (ll >= L0) & 1) continue;   // a dead update's row
       const int m0 = smp[ll], m1 = smp[ll + 1];
       const float* hp = hPo + 4 * c4;
       f4 x = {0, 0, 0, 0};
@@ -578,15 +592,16 @@ __global__ __launch_bounds__(64 * kW) void resident_forward_kernel(ResidentArgs 
     // the GRU step of both column halves with the tile's own sum MP's weights, the new states, then
     // the next iteration's projected rows of the tile.  Each wave reads its tiles' message sums into
     // registers before a barrier: they alias table rows that other waves' projections overwrite (a
-    // tile's states are only written by its own wave: read after the barrier)
-    const bool last = it + 1 == a.T;
+    // tile's states are only written by its own wave: read after the barrier).  The tiles of a dead
+    // update (dl) are left out of the range: no step, no store, their states stay
     const int nt0 = (int)((L0 + 15) / 16);
     const int ntt = nt0 + (int)((L1 + 15) / 16);
+    const int kb = dl & 1 ? nt0 : 0, ke = dl & 2 ? nt0 : ntt;   // the live updates' tiles
     f4 xr[2][2];
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-      const int k = wave + kW * q;
-      const bool act = k < ntt;   // wave-uniform
+      const int k = kb + wave + kW * q;
+      const bool act = k < ke;   // wave-uniform
       const bool e1 = k >= nt0;
       const int64_t idx = e1 ? L0 + 16 * (k - nt0) + j : 16 * k + j;
       const bool valid = act && idx < (e1 ? U : L0);
@@ -597,8 +612,8 @@ __global__ __launch_bounds__(64 * kW) void resident_forward_kernel(ResidentArgs 
     __syncthreads();
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-      const int k = wave + kW * q;
-      if (k >= ntt) break;   // wave-uniform
+      const int k = kb + wave + kW * q;
+      if (k >= ke) break;   // wave-uniform
       const int e1 = k >= nt0;
       const int64_t idx = e1 ? L0 + 16 * (k - nt0) + j : 16 * k + j;
       const bool valid = idx < (e1 ? U : L0);
@@ -650,8 +665,9 @@ __global__ __launch_bounds__(64 * kW) void resident_forward_kernel(ResidentArgs 
     o[7] = t_a - t_0;
   }
 #endif
-  // the final states leave the workgroup (the readout and ign_batch_state read them; SAVE: the
-  // versions hold every state already)
+  // the final states leave the workgroup (the readout and ign_batch_state read them; a source entity
+  // in dead_last: one update behind, ign_batch_state runs it.  SAVE: the versions hold every state
+  // already)
   if constexpr (SAVE) return;
   if constexpr (!PG)   // PG: the path states are already there
     for (int64_t i = tid; i < P * (H / 4); i += 64 * kW) {
@@ -693,7 +709,7 @@ hipError_t launch_resident_forward(const ResidentArgs& a, int n_graphs, size_t l
                                    hipStream_t st) {
   if (n_graphs == 0) return hipSuccess;
   if (lds_bytes > kResidentMaxDynLds || a.n_src < 1 || a.n_src > kResidentMaxSrc) return hipErrorInvalidValue;
-  if (save && (form == IGN_RES_ALL_LDS || !a.path_ver || !a.hs_save || !a.hsb)) return hipErrorInvalidValue;
+  if (save && (form == IGN_RES_ALL_LDS || !a.path_ver || !a.hs_save || !a.hsb || a.dead_last)) return hipErrorInvalidValue;
   const dim3 grid((unsigned)n_graphs), block(64 * kW);
   if (save && form == IGN_RES_PATH_CSR_GLOBAL)
     hipLaunchKernelGGL((resident_forward_kernel<true, false, true>), grid, block, lds_bytes, st, a);

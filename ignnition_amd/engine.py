@@ -340,6 +340,23 @@ class MPPlan:
         return [(e[0], stack) + (e[1:] if e[0] == "dropout" else (e[1], e[2], int(e[3]), int(e[4])))
                 for stack, _, _, extra in self._stacks() for e in extra]
 
+    def dead_in_last_iter(self):
+        """Per MP, in execution order: True where nothing reads what its last iteration's update writes
+        (ign_plan_mp_dead_last), so the graph-resident forward leaves that update out until Batch.state asks for the
+        entity.  Lowered on the host: needs no GPU."""
+        desc, keep = self.to_desc()
+        h = C.c_void_p()
+        check(lib.ign_plan_create(C.byref(desc), 0, C.byref(h)))
+        try:
+            dead = C.c_int32()
+            out = []
+            for mi in range(len(self.mps)):
+                check(lib.ign_plan_mp_dead_last(h, mi, C.byref(dead)))
+                out.append(bool(dead.value))
+            return out
+        finally:
+            lib.ign_plan_destroy(h)
+
     # ------------------------------------------------------------------ C structures
     def to_desc(self):
         keep = []

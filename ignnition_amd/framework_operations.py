@@ -130,6 +130,7 @@ def debug(model_description, out_dir: str = "../debug_model/"):
         "adjacency_slots": [s.__dict__ for s in plan.adj_slots],
         "interleave_slots": plan.il_slots,
         "message_passings": plan.mps,
+        "dead_in_last_iter": plan.dead_in_last_iter(),   # per MP: the resident forward leaves its last update out
         "cells": plan.cells,
         "readout_ops": plan.readout_ops,
         "readout_inputs": plan.readout_inputs,

@@ -275,9 +275,10 @@ typedef struct {
   int64_t lds_bytes;               /* dynamic LDS per workgroup (the batch's largest graph) */
   int64_t tile_steps;              /* phase A: 16-path tile-steps per launch (T x per tile its longest
                                       sequence) */
-  int64_t union_tiles;             /* phase B: 16-row tiles of the source entities' rows, per iteration */
+  int64_t union_tiles;             /* phase B: 16-row tiles of the source entities' rows, per iteration
+                                      (the last iteration: less the tiles of updates nothing reads) */
   int64_t seg_rows;                /* rows whose message sum takes sum_seg's wave-per-row order */
-  int64_t messages;                /* sum-MP messages per iteration */
+  int64_t messages;                /* sum-MP messages per iteration (the last one: as union_tiles) */
   double  bytes_compulsory;        /* features, index tables read once, final states written once */
   double  bytes_roundtrip;         /* global-path forms: the path states' (and CSR's) L2 round trips */
   double  bytes_stage;             /* sum over the T iterations' MPs of
@@ -303,8 +304,18 @@ int  ign_batch_predictions(ign_batch* batch, const float** dev_ptr);
  * stream (waits for that stream only): the host side of a forward launched with pred_out NULL,
  * e.g. one of several sub-batches on several plans launched before any wait (ABI 10). */
 int  ign_batch_read_predictions(ign_plan* plan, ign_batch* batch, float* host_out);
-/* Copy the current hidden state of an entity (after ign_forward) to host [rows][H]. */
+/* Copy the current hidden state of an entity (after ign_forward) to host [rows][H].  The graph-resident
+ * forward (ign_batch_resident_info: active) leaves out the last iteration's update of an entity whose
+ * final states nothing reads (ign_plan_mp_dead_last); this call runs that update first, once, on the plan's stream, so the states are those of a forward
+ * that runs every update, bit for bit. */
 int  ign_batch_state(ign_plan* plan, ign_batch* batch, int32_t entity, float* host_out);
+/* *dead = 1 when no readout operation, no predict input and no later MP of the same iteration reads
+ * the states MP `mp` writes in the last iteration, and no later MP writes what it reads: the
+ * graph-resident ign_forward then leaves that one update out (IGN_DEAD_LAST=0: never) until
+ * ign_batch_state asks for the entity.  A property of the model alone, whatever IGN_DEAD_LAST says.
+ * The per-MP launches of ign_forward, the training forward, the stepped forward and an entity with bound state buffers (ign_batch_bind_state) run every update.  The
+ * statistics (ign_stats, ign_batch_resident_info's bytes and FLOPs) count what runs. */
+int  ign_plan_mp_dead_last(const ign_plan* plan, int32_t mp, int32_t* dead);
 int  ign_stats(const ign_plan* plan, ign_stats_t* out);
 
 /* ---- Stepped forward, for edge-cut partitions exchanging halo rows between MPs ----
@@ -320,7 +331,8 @@ int  ign_forward_end(ign_plan* plan, ign_batch* batch, float* pred_out);
  * without halo rows). */
 int  ign_batch_mp_split(const ign_batch* batch, int32_t mp, int64_t* interior, int64_t* boundary);
 /* Replace an entity's two state buffers by caller-owned device memory, each at least
- * (rows + halo) * hidden_dim + 256 floats, 16-byte aligned.  State contents are not copied. */
+ * (rows + halo) * hidden_dim + 256 floats, 16-byte aligned.  State contents are not copied.  Every
+ * update of the entity runs from here on (ign_plan_mp_dead_last): its reader is the caller. */
 int  ign_batch_bind_state(ign_plan* plan, ign_batch* batch, int32_t entity, float* dev0, float* dev1,
                           int64_t capacity_floats);
 /* Which of the two state buffers (0/1) holds the entity's current state. */
