@@ -5,7 +5,7 @@ fixed seeded vector).
     python tools/ab_bitwise.py base new [--graphs 512] [--model routenet] [--topology synth50] [--train]
 --cases runs the models of the tests' case modules instead (predict_cases and its H = 64 model, test_gpu_dropout's GRAD_CASES
 with its mask stream, layernorm_cases' GRAD_CASES, readout_cases, test_gpu_training's message-network
-parameter sets, aggregation_cases' table), all of them in one process per library, and compares per case the training forward's
+parameter sets, aggregation_cases' and readout_op_cases' tables), all of them in one process per library, and compares per case the training forward's
 predictions and the flat gradient of one backward; for the H = 64, LayerNormalization, readout-operation
 and message-network cases the inference forward too.
 (Against a parent commit: tools/build_ab.sh base in a checkout of it, its lib_base.so copied to this ab/.)
@@ -86,6 +86,10 @@ def cases():
     for c in sorted(ac.CASES):
         desc, dims, _, _, graphs, _, prm = ac.case_inputs(c)
         yield "aggregation/" + c, desc, dims, graphs, prm, None, True
+    from tests import readout_op_cases as rc   # the readout operations on their kernels' edges
+    for c in rc.ALL:
+        desc, dims, _, _, graphs, _, prm = rc.case_inputs(c)
+        yield "readout_op/" + c, desc, dims, graphs, prm, None, True
 
 
 def run_cases(out):
