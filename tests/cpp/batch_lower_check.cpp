@@ -496,6 +496,62 @@ static void resident_case(int ib) {
     CHECK(!t.eligible);
   }
 }
+// The byte budget's edges on the fixture above (per graph 2686 / 2072 / 2056 bytes in the all-LDS, path-global
+// and CSR-global forms; 4942 / 3736 / 3704 for two graphs in one workgroup), with max_dyn_lds moved onto and
+// one byte under each: the form, the training form (path states always global) and whether the batch lowers.
+// (The 16-bit row limit has no tiny instance: tests/test_gpu_resident_cases.py holds it at 65 535 paths.)
+static void resident_budget_case(int ib) {
+  Desc ds = routenet_desc(2, false);
+  Resident r;
+  r.rp.path = 1, r.rp.src_ent[0] = 0;
+  OK(r.lower(ds, ib, routenet_mps(), 1));
+  const struct { size_t max; bool pg_ok, force; int K; bool eligible; int form, train_form; } rows[] = {
+      // A: all-LDS <-> path-global
+      {2686, true, false, 1, true, kResAllLds, kResPathGlobal},
+      {2685, true, false, 1, true, kResPathGlobal, kResPathGlobal},
+      {2686, false, false, 1, true, kResAllLds, kResPathGlobal},
+      {2685, false, false, 1, false, 0, 0},                          // IGN_RESIDENT_PG=0: no other form
+      {2686, true, true, 1, true, kResPathGlobal, kResPathGlobal},   // IGN_RESIDENT=2
+      // B: path-global <-> CSR-global (the training form moves with it)
+      {2072, true, false, 1, true, kResPathGlobal, kResPathGlobal},
+      {2071, true, false, 1, true, kResPathCsrGlobal, kResPathCsrGlobal},
+      {2071, true, true, 1, true, kResPathCsrGlobal, kResPathCsrGlobal},
+      // C: CSR-global <-> not resident
+      {2056, true, false, 1, true, kResPathCsrGlobal, kResPathCsrGlobal},
+      {2055, true, false, 1, false, 0, 0},
+      // D: two graphs per workgroup: the union's own bytes decide its form, and whether it lowers at all
+      {4942, true, false, 2, true, kResAllLds, kResPathGlobal},
+      {4941, true, false, 2, true, kResPathGlobal, kResPathGlobal},
+      {3736, true, false, 2, true, kResPathGlobal, kResPathGlobal},
+      {3735, true, false, 2, true, kResPathCsrGlobal, kResPathCsrGlobal},
+      {3704, true, false, 2, true, kResPathCsrGlobal, kResPathCsrGlobal},
+      {3703, true, false, 2, false, 0, 0}};                          // (one graph per workgroup still lowers: 2056)
+  for (const auto& w : rows) {
+    r.rp.max_dyn_lds = w.max, r.rp.path_global_ok = w.pg_ok, r.rp.force_path_global = w.force;
+    ResidentTables t;
+    r.run(w.K, &t);
+    bool ok = t.eligible == w.eligible;
+    if (ok && w.eligible) {
+      static const size_t one[3] = {2686, 2072, 2056}, two[3] = {4942, 3736, 3704};
+      const size_t* want = w.K == 1 ? one : two;
+      ok = t.form == w.form && t.train_form == w.train_form && t.K == w.K && t.G == (w.K == 1 ? 2 : 1) &&
+           t.lds[0] == want[0] && t.lds[1] == want[1] && t.lds[2] == want[2] && t.info.lds_bytes == (int64_t)want[w.form] &&
+           t.info.form == w.form && t.info.graphs_per_workgroup == w.K && t.info.workgroups == t.G;
+    }
+    if (!ok) printf("FAIL [%s]: max_dyn_lds %zu, K %d, pg_ok %d, force %d\n", g_case, w.max, w.K, w.pg_ok, w.force), ++g_bad;
+  }
+  // the automatic rule of the engine (two graphs per workgroup where one graph's all-LDS bytes fit twice)
+  // never asks for a union that needs another form: the union's bytes are at most twice one graph's
+  CHECK(4942 <= 2 * 2686 && 3736 <= 2 * 2072 && 3704 <= 2 * 2056);
+  // the tile limit: a graph's 3 links are one union-row tile
+  r.rp.max_dyn_lds = 144 * 1024, r.rp.path_global_ok = true, r.rp.force_path_global = false;
+  for (int tiles : {1, 0}) {
+    r.rp.max_tiles = tiles;
+    ResidentTables t;
+    r.run(2, &t);
+    CHECK(t.eligible == (tiles == 1));
+  }
+}
 // Q-size shape, one small graph: entities 0 = links, 1 = nodes, 2 = paths; the path is l0 n0 l1 n1.
 // Union rows: entity 0's rows, then entity 1's
 static void resident_two_source_case(int ib) {
@@ -529,7 +585,7 @@ int main() {
       {"interleave", interleave_case}, {"sum", sum_case}, {"sum halo", sum_halo_case}, {"segmented", segmented_case},
       {"windowed", windowed_case}, {"attention", attention_case}, {"validation", validation_case},
       {"empty destination", empty_destination_case}, {"resident", resident_case},
-      {"resident two sources", resident_two_source_case}};
+      {"resident budget", resident_budget_case}, {"resident two sources", resident_two_source_case}};
   // every case at both index widths against the same hand tables: int32 and int64 descs lower equally
   for (int ib : {8, 4})
     for (auto& c : cases) {
