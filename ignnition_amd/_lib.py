@@ -101,7 +101,11 @@ AGGR = {"sum": 0, "ordered": 1, "interleave": 2, "concat": 3, "attention": 4, "c
 READOUT_OP = {"neural_network": 0, "pooling": 1, "product": 2, "extend_adjacencies": 3}
 POOLING = {"sum": 0, "mean": 1, "max": 2}
 PRODUCT = {"element_wise": 0, "dot_product": 1}
-ACT = {None: 0, "None": 0, "linear": 0, "relu": 1, "selu": 2, "sigmoid": 3, "tanh": 4}
+ACT = {None: 0, "None": 0, "linear": 0, "relu": 1, "selu": 2, "sigmoid": 3, "tanh": 4,
+       "elu": 5, "softplus": 6, "softsign": 7, "exponential": 8, "hard_sigmoid": 9}
+# what plan_lower.h's act_ok refuses per position: as before those five were lowered
+ACT_REFUSED_AT = {"predict": (), "readout_op": ("elu",), "message": ("hard_sigmoid",),
+                  "convolution": ("softplus", "hard_sigmoid")}
 
 # every symbol declared in include/ignmp.h
 SYMBOLS = ["ign_abi_version", "ign_last_error", "ign_device_count", "ign_plan_create", "ign_plan_destroy",

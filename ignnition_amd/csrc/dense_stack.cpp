@@ -88,7 +88,7 @@ int dense_stack_forward(const ign_plan* p, const DenseStackRun& r, hipStream_t s
     const float* bias = d.use_bias ? p->d_params + d.off_b : nullptr;
     if (p->train_dense_bf && p->train_dense_h16 && d.pk_hn >= 0 && stride % 4 == 0)   // split-fp16 (x3)
       HIP_TRY(launch_dense_h16(in, r.n, d.in, stride, p->d_packed + d.pk_hn, bias, d.out, d.act, o, st));
-    else if (p->train_dense_bf && d.pk_bfn >= 0 && stride % 4 == 0)   // split-bf16, fp32-exact operands
+    else if (p->train_dense_bf && d.pk_bfn >= 0 && stride % 4 == 0 && act_first_five(d.act))   // split-bf16, fp32-exact operands
       HIP_TRY(launch_dense_bf(in, r.n, d.in, stride, p->d_packed + d.pk_bfn, bias, d.out, d.act, o, st));
     else   // (MFMA fragments cover the whole row: a message network's layer 0 contracts its zero-padded stride)
       HIP_TRY(launch_dense_fwd(in, r.n, d.pk_w >= 0 ? stride : d.in, stride, d.pk_w >= 0 ? p->d_packed + d.pk_w : nullptr,
@@ -142,7 +142,8 @@ int dense_stack_backward(const ign_plan* p, const DenseStackRun& r, hipStream_t 
     };
     const bool outer = xo.s != nullptr;   // this layer's dz is formed by its dense_t from hid[l]
     if (!outer && (rc = wgrad(gz[zi]))) return rc;
-    if (l > 0 && d.out == 1 && d.in % 4 == 0 && p->fuse_outer_bwd && dense_t_bf(r.layers[l - 1]) && !ns) {
+    if (l > 0 && d.out == 1 && d.in % 4 == 0 && p->fuse_outer_bwd && dense_t_bf(r.layers[l - 1]) && !ns &&
+        act_first_five(r.layers[l - 1].act)) {
       xo = OuterRows{gz[zi], p->d_params + d.off_w, r.layers[l - 1].act, r.hid[l - 1]};
       continue;   // zi stays: gz[zi] holds dz_out for the layer below
     }
@@ -155,10 +156,15 @@ int dense_stack_backward(const ign_plan* p, const DenseStackRun& r, hipStream_t 
     float* out = to_dx ? r.dx : gz[1 - zi];
     const int acc = to_dx ? r.dx_acc : 0;
     const float* dzin = outer ? xo.out : gz[zi];
+    // dense_h16_t / dense_bf_t apply linear .. tanh's derivative themselves; another activation's
+    // follows as its own launch (never beside an added-to dx: act >= 0 only above layer 0)
+    const bool late = act >= 0 && !act_first_five(act) && p->train_dense_bf &&
+                      ((p->train_dense_h16 && d.pk_ht >= 0) || d.pk_bft >= 0);
+    const int act_t = late ? -1 : act;
     if (p->train_dense_bf && p->train_dense_h16 && d.pk_ht >= 0)   // split-fp16 (x3)
-      HIP_TRY(launch_dense_h16_t(dzin, n, d.out, p->d_packed + d.pk_ht, d.in, out, acc, act, aprev, st, xo));
+      HIP_TRY(launch_dense_h16_t(dzin, n, d.out, p->d_packed + d.pk_ht, d.in, out, acc, act_t, aprev, st, xo));
     else if (p->train_dense_bf && d.pk_bft >= 0)   // split-bf16, fp32-exact operands
-      HIP_TRY(launch_dense_bf_t(dzin, n, d.out, p->d_packed + d.pk_bft, d.in, out, acc, act, aprev, st, xo));
+      HIP_TRY(launch_dense_bf_t(dzin, n, d.out, p->d_packed + d.pk_bft, d.in, out, acc, act_t, aprev, st, xo));
     else if (outer)
       return fail(IGN_ERR_RUNTIME, "on-the-fly output-layer gradient without a dense_bf backward");
     else if (d.pk_wt >= 0)
@@ -167,6 +173,10 @@ int dense_stack_backward(const ign_plan* p, const DenseStackRun& r, hipStream_t 
       HIP_TRY(launch_row_gemm_t_generic(gz[zi], n, d.out, p->d_params + d.off_w, d.in, out, acc, act, aprev, st));
     if (outer && (rc = wgrad(xo.out))) return rc;   // on the rows dense_t just wrote over hid[l]
     xo = OuterRows{};
+    if (late) {
+      HIP_TRY(launch_act_bwd(out, aprev, n * d.in, act, gz[zi], st));
+      continue;   // the layer below's dz is in gz[zi]: zi stays
+    }
     if (ns) {   // d(z) -> d(y) through them, last first, in place
       // a LayerNormalization that stands first in front of layer 0 adds its rows to an added-to dx itself
       bool norm_to_dx = false;

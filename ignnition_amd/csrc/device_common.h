@@ -100,7 +100,35 @@ __device__ __forceinline__ float sig2_(float a) { return rcpf_(1.0f + __builtin_
 // tanh of the pre-scaled candidate argument c' = 2 log2(e) c (ln2 / 2 = 1 / (2 log2 e))
 __device__ __forceinline__ float tanh2_(float c) { return tanh_tc_(c * 0.34657359027997264f, c); }
 
-__device__ __forceinline__ float act_apply(float x, int act) {
+// ---- elu, softplus, softsign, exponential, hard_sigmoid (tf.keras.activations, TF 2.x) ----
+// On v_exp_f32 / v_log_f32 / v_rcp_f32 like the gates above.
+constexpr float kActLn2 = 0.6931471805599453f, kActLog2e = 1.4426950408889634f;
+
+// log(1 + t), 0 <= t <= 1.  u = fl(1 + t) has lost t's low bits; log(u) t / (u - 1) gives them back
+// (u - 1 is exact), and u == 1 leaves t itself: softplus(z) for z << 0 is exp(z), not a cancelled 0.
+__device__ __forceinline__ float log1p_unit_(float t) {
+  const float u = 1.0f + t, d = u - 1.0f;
+  return d == 0.f ? t : __builtin_amdgcn_logf(u) * kActLn2 * t * rcpf_(d);
+}
+__device__ __forceinline__ float softplusf_(float x) {   // max(x, 0) + log1p(exp(-|x|))
+  return fmaxf(x, 0.f) + log1p_unit_(__builtin_amdgcn_exp2f(-fabsf(x) * kActLog2e));
+}
+// 1 - exp(-a) = softplus' through its output a >= 0.  Below 1/2 the same correction the other way:
+// u = fl(exp(-a)), (1 - u) a / -log(u), and u == 1 leaves a: no 0 by cancellation for z << 0.
+__device__ __forceinline__ float neg_expm1_neg_(float a) {
+  const float u = __builtin_amdgcn_exp2f(-a * kActLog2e), d = 1.0f - u;
+  const float small = d == 0.f ? a : d * a * rcpf_(-kActLn2 * __builtin_amdgcn_logf(u));
+  return a < 0.5f ? small : d;
+}
+__device__ __forceinline__ float eluf_(float x) {   // alpha 1; exp of min(x, 0): no overflow in the dead arm
+  return x > 0.f ? x : __expf(fminf(x, 0.f)) - 1.0f;
+}
+__device__ __forceinline__ float softsignf_(float x) { return x * rcpf_(1.0f + fabsf(x)); }
+__device__ __forceinline__ float hard_sigmoidf_(float x) { return fminf(fmaxf(fmaf(0.2f, x, 0.5f), 0.f), 1.f); }
+
+// The five activations of the fused readouts' output layer (act3), whose kernels stay as they were
+// tuned: fused_readout_acts (kernel_shapes.h) keeps every other code away from them.
+__device__ __forceinline__ float act_apply_base(float x, int act) {
   switch (act) {
     case IGN_K_ACT_RELU: return x > 0.f ? x : 0.f;
     case IGN_K_ACT_SELU: {
@@ -113,8 +141,55 @@ __device__ __forceinline__ float act_apply(float x, int act) {
   }
 }
 
+// Every activation code.  A launcher checks act_code_ok first: no other code reaches the default arm.
+__device__ __forceinline__ float act_apply(float x, int act) {
+  switch (act) {
+    case IGN_K_ACT_ELU: return eluf_(x);
+    case IGN_K_ACT_SOFTPLUS: return softplusf_(x);
+    case IGN_K_ACT_SOFTSIGN: return softsignf_(x);
+    case IGN_K_ACT_EXPONENTIAL: return __expf(x);
+    case IGN_K_ACT_HARD_SIGMOID: return hard_sigmoidf_(x);
+    default: return act_apply_base(x, act);
+  }
+}
+
+// act' through the activation's output a (all of them are monotone): what the backward kernels apply
+// to the saved activations.  _base: the five of dense_bf_kernel's backward forms, as act_apply_base.
+__device__ __forceinline__ float act_grad_out_base(float a, int act) {
+  switch (act) {
+    case IGN_K_ACT_RELU: return a > 0.f ? 1.f : 0.f;
+    case IGN_K_ACT_SELU: {
+      const float lam = 1.0507009873554805f, la = 1.0507009873554805f * 1.6732632423543772f;
+      return a > 0.f ? lam : a + la;
+    }
+    case IGN_K_ACT_SIGMOID: return a * (1.f - a);
+    case IGN_K_ACT_TANH: return 1.f - a * a;
+    default: return 1.f;
+  }
+}
+__device__ __forceinline__ float act_grad_out(float a, int act) {
+  switch (act) {
+    case IGN_K_ACT_ELU: return a > 0.f ? 1.f : a + 1.f;
+    case IGN_K_ACT_SOFTPLUS: return neg_expm1_neg_(a);
+    case IGN_K_ACT_SOFTSIGN: {
+      const float t = 1.f - fabsf(a);
+      return t * t;
+    }
+    case IGN_K_ACT_EXPONENTIAL: return a;
+    case IGN_K_ACT_HARD_SIGMOID: return a > 0.f && a < 1.f ? 0.2f : 0.f;
+    default: return act_grad_out_base(a, act);
+  }
+}
+
 template <int ACT>
 __device__ __forceinline__ float act_t(float x) {
+  static_assert(ACT >= IGN_K_ACT_LINEAR && ACT <= IGN_K_ACT_HARD_SIGMOID, "no such activation");
+  if constexpr (ACT == IGN_K_ACT_ELU) return eluf_(x);
+  else if constexpr (ACT == IGN_K_ACT_SOFTPLUS) return softplusf_(x);
+  else if constexpr (ACT == IGN_K_ACT_SOFTSIGN) return softsignf_(x);
+  else if constexpr (ACT == IGN_K_ACT_EXPONENTIAL) return __expf(x);
+  else if constexpr (ACT == IGN_K_ACT_HARD_SIGMOID) return hard_sigmoidf_(x);
+  else
   if constexpr (ACT == IGN_K_ACT_RELU) return x > 0.f ? x : 0.f;
   else if constexpr (ACT == IGN_K_ACT_SELU) {   // branch-free: exp of min(x, 0), then select
     const float lam = 1.0507009873554805f, la = 1.0507009873554805f * 1.6732632423543772f;

@@ -8,11 +8,22 @@
 inline bool gru_shape_supported(int din, int h) {
   return ((din == 16 || din == 32) && (h == 16 || h == 32)) || (din == 64 && h == 64);
 }
-inline bool readout3_supported(int din, int n1, int n2, int act1, int act2) {
-  return (din == 16 || din == 32 || din == 64) && n1 == 256 && n2 == 256 && act1 == act2;
+// the activation codes (ignmp.h's IGN_ACT_*, kernels.h's IGN_K_ACT_*): a launcher refuses any other
+inline bool act_code_ok(int a) { return a >= 0 && a <= 9; }
+// linear, relu, selu, sigmoid, tanh: the codes every templated kernel is instantiated for.  elu ..
+// hard_sigmoid (5 .. 9) run on the runtime-switched kernels and on dense_h16's forward.
+inline bool act_first_five(int a) { return a >= 0 && a <= 4; }
+// The fused readouts (readout3, readout_bf, readout_h16, readout_h32) are instantiated for those five
+// alone, and the scaled split-fp16 forms bound their layer-2 input by those activations' growth
+// (DESIGN.md §3b'); a stack with any other code runs layer by layer.
+inline bool fused_readout_acts(int act1, int act2, int act3) {
+  return act1 == act2 && act_first_five(act1) && act_first_five(act3);
 }
-inline bool readout_bf_supported(int din, int n1, int n2, int act1, int act2) {
-  return (din == 32 || din == 64) && n1 == 256 && n2 == 256 && act1 == act2;
+inline bool readout3_supported(int din, int n1, int n2, int act1, int act2, int act3) {
+  return (din == 16 || din == 32 || din == 64) && n1 == 256 && n2 == 256 && fused_readout_acts(act1, act2, act3);
+}
+inline bool readout_bf_supported(int din, int n1, int n2, int act1, int act2, int act3) {
+  return (din == 32 || din == 64) && n1 == 256 && n2 == 256 && fused_readout_acts(act1, act2, act3);
 }
 // dense_bf / dense_h16 and their transposed forms: K in {32, 64, 128, 256}, M a multiple of 128
 inline bool dense_bf_supported(int K, int M) {

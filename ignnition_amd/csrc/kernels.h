@@ -9,7 +9,9 @@
 #define IGN_ROW_MASK ((1u << IGN_SLOT_SHIFT) - 1u)
 #define IGN_MAX_SLOTS 4
 
-enum { IGN_K_ACT_LINEAR = 0, IGN_K_ACT_RELU = 1, IGN_K_ACT_SELU = 2, IGN_K_ACT_SIGMOID = 3, IGN_K_ACT_TANH = 4 };
+enum { IGN_K_ACT_LINEAR = 0, IGN_K_ACT_RELU = 1, IGN_K_ACT_SELU = 2, IGN_K_ACT_SIGMOID = 3, IGN_K_ACT_TANH = 4,
+       IGN_K_ACT_ELU = 5, IGN_K_ACT_SOFTPLUS = 6, IGN_K_ACT_SOFTSIGN = 7, IGN_K_ACT_EXPONENTIAL = 8,
+       IGN_K_ACT_HARD_SIGMOID = 9 };   // act_code_ok (kernel_shapes.h) spans them
 
 // Base pointer of each source slot's current hidden-state table (message code = slot<<29 | row).
 struct SrcBases {

@@ -870,8 +870,8 @@ __global__ __launch_bounds__(256) void readout3_kernel(Readout3Args a) {
   if (g == 0) {
     const float b3 = a.b3 ? a.b3[0] : 0.f;
     int64_t r0 = base + j, r1 = base + 16 + j;
-    if (r0 < a.n_rows) a.y[r0] = act_apply(y0 + b3, a.act3);
-    if (r1 < a.n_rows) a.y[r1] = act_apply(y1 + b3, a.act3);
+    if (r0 < a.n_rows) a.y[r0] = act_apply_base(y0 + b3, a.act3);
+    if (r1 < a.n_rows) a.y[r1] = act_apply_base(y1 + b3, a.act3);
   }
 }
 
@@ -1036,6 +1036,7 @@ hipError_t launch_sum_gru(const SumGruArgs& args, int din, int h, int variant, h
   // (0.109 vs 0.141 ms on 512 x synth50): more independent waves queue behind the resident ones
   dim3 grid(grid_for(args.n_dst, 64));
   const int mode = args.conv_kp ? 2 : args.msg_w ? 1 : 0;
+  if (mode == 2 && !act_code_ok(args.conv_act)) return hipErrorInvalidValue;
   // variant 7 (default): split-bf16 GRU step where its kernels exist (plain sums at DIN = H = 32
   // or 64); otherwise the f32-MFMA kernels
   if (din == 32 && h == 32 && mode == 0 && variant == 7 && args.Wbf && args.Ubf)
@@ -1074,14 +1075,15 @@ static hipError_t readout3_din(const Readout3Args& args, int act, dim3 grid, hip
     case IGN_K_ACT_RELU: hipLaunchKernelGGL((readout3_kernel<DIN, 256, 256, IGN_K_ACT_RELU>), grid, dim3(256), 0, st, args); break;
     case IGN_K_ACT_TANH: hipLaunchKernelGGL((readout3_kernel<DIN, 256, 256, IGN_K_ACT_TANH>), grid, dim3(256), 0, st, args); break;
     case IGN_K_ACT_SIGMOID: hipLaunchKernelGGL((readout3_kernel<DIN, 256, 256, IGN_K_ACT_SIGMOID>), grid, dim3(256), 0, st, args); break;
-    default: hipLaunchKernelGGL((readout3_kernel<DIN, 256, 256, IGN_K_ACT_LINEAR>), grid, dim3(256), 0, st, args); break;
+    case IGN_K_ACT_LINEAR: hipLaunchKernelGGL((readout3_kernel<DIN, 256, 256, IGN_K_ACT_LINEAR>), grid, dim3(256), 0, st, args); break;
+    default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }
 
 hipError_t launch_readout3(const Readout3Args& args, int din, int n1, int n2, hipStream_t st) {
   if (args.n_rows == 0) return hipSuccess;
-  if (!readout3_supported(din, n1, n2, args.act1, args.act2)) return hipErrorInvalidValue;
+  if (!readout3_supported(din, n1, n2, args.act1, args.act2, args.act3)) return hipErrorInvalidValue;
   dim3 grid(grid_for(args.n_rows, 128));
   if (din == 32) return readout3_din<32>(args, args.act1, grid, st);
   if (din == 16) return readout3_din<16>(args, args.act1, grid, st);
@@ -1090,6 +1092,7 @@ hipError_t launch_readout3(const Readout3Args& args, int din, int n1, int n2, hi
 
 hipError_t launch_dense_generic(const float* x, int64_t n, int in, int x_stride, const float* W, const float* b,
                                 int out, int act, float* y, hipStream_t st) {
+  if (!act_code_ok(act)) return hipErrorInvalidValue;
   int64_t total = n * (int64_t)out;
   int blocks = (int)std::min<int64_t>((total + 255) / 256, 16384);
   if (blocks < 1) blocks = 1;

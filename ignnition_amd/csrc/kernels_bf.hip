@@ -1120,19 +1120,6 @@ __global__ __launch_bounds__(256) void tsgemm_bf_kernel(const float* __restrict_
   }
 }
 
-__device__ __forceinline__ float act_grad_out(float a, int act) {   // act' through the output a
-  switch (act) {
-    case IGN_K_ACT_RELU: return a > 0.f ? 1.f : 0.f;
-    case IGN_K_ACT_SELU: {
-      const float lam = 1.0507009873554805f, la = 1.0507009873554805f * 1.6732632423543772f;
-      return a > 0.f ? lam : a + la;
-    }
-    case IGN_K_ACT_SIGMOID: return a * (1.f - a);
-    case IGN_K_ACT_TANH: return 1.f - a * a;
-    default: return 1.f;
-  }
-}
-
 // tsgemm_bf_kernel for M % 64 == N % 64 == 0 with the pieces split once per block: a block of
 // mtb x tiles_n waves holds the tiles of mtb 64-column groups of A against all of B.  Per 32-row
 // step every (column, 8-row group) pair of the block's A columns and of B is loaded once (64 lanes =
@@ -1494,7 +1481,7 @@ __global__ __launch_bounds__(64 * WAVES) void readout_bf_kernel(Readout3Args a, 
     const int64_t r = r0 + 16 * t;
     if (g == 0 && r < a.n_rows) {
       const float b3 = a.b3 ? a.b3[0] : 0.f;
-      a.y[r] = act_apply(yt + b3, a.act3);
+      a.y[r] = act_apply_base(yt + b3, a.act3);
     }
   }
   }  // row groups
@@ -1830,7 +1817,7 @@ __global__ __launch_bounds__(64 * WAVES) void readout_h16_kernel(Readout3Args a,
     const int64_t r = r0 + 16 * t;
     if (g == 0 && r < a.n_rows) {
       const float b3 = a.b3 ? a.b3[0] : 0.f;
-      a.y[r] = act_apply(fmaf(yt, cSS[t], b3), a.act3);
+      a.y[r] = act_apply_base(fmaf(yt, cSS[t], b3), a.act3);
     }
   }
 #ifdef IGN_RO_NOPREFETCH
@@ -1888,7 +1875,7 @@ __global__ __launch_bounds__(512) void dense_bf_kernel(const float* x, int64_t n
       for (int q = 0; q < 4; ++q) {
         float sq = 0.f;
         sq += xsr * w[q];
-        o[q] = sq * act_grad_out(v[q], xo.act);
+        o[q] = sq * act_grad_out_base(v[q], xo.act);
       }
       if (xo.out) st4(xo.out + r * (int64_t)x_stride + c0, o);   // for the weight gradient (may be x itself)
       return o;
@@ -1979,7 +1966,7 @@ __global__ __launch_bounds__(512) void dense_bf_kernel(const float* x, int64_t n
         if constexpr (BWD) {
           const f4 av = aprev ? ld4(aprev + r * M + 16 * u + 4 * g) : f4{0, 0, 0, 0};
 #pragma unroll
-          for (int q = 0; q < 4; ++q) o[q] = aprev ? acc[t][q] * act_grad_out(av[q], ACT) : acc[t][q];
+          for (int q = 0; q < 4; ++q) o[q] = aprev ? acc[t][q] * act_grad_out_base(av[q], ACT) : acc[t][q];
           if (accumulate) o += ld4(po);
         } else {
 #pragma unroll
@@ -2031,7 +2018,8 @@ static hipError_t readout_bf_din(const Readout3Args& args, const void* W1f, cons
     case IGN_K_ACT_RELU: readout_bf_launch<DIN, IGN_K_ACT_RELU, WAVES, PASSES, CT, W1L, RT, PERSIST>(args, w1, w2, st); break;
     case IGN_K_ACT_TANH: readout_bf_launch<DIN, IGN_K_ACT_TANH, WAVES, PASSES, CT, W1L, RT, PERSIST>(args, w1, w2, st); break;
     case IGN_K_ACT_SIGMOID: readout_bf_launch<DIN, IGN_K_ACT_SIGMOID, WAVES, PASSES, CT, W1L, RT, PERSIST>(args, w1, w2, st); break;
-    default: readout_bf_launch<DIN, IGN_K_ACT_LINEAR, WAVES, PASSES, CT, W1L, RT, PERSIST>(args, w1, w2, st); break;
+    case IGN_K_ACT_LINEAR: readout_bf_launch<DIN, IGN_K_ACT_LINEAR, WAVES, PASSES, CT, W1L, RT, PERSIST>(args, w1, w2, st); break;
+    default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }
@@ -2039,7 +2027,7 @@ static hipError_t readout_bf_din(const Readout3Args& args, const void* W1f, cons
 hipError_t launch_readout_bf(const Readout3Args& args, const void* W1f, const void* W2f, int din, int passes,
                              hipStream_t st) {
   if (args.n_rows == 0) return hipSuccess;
-  if (!readout_bf_supported(din, 256, 256, args.act1, args.act2) || !W1f || !W2f || passes != 6)
+  if (!readout_bf_supported(din, 256, 256, args.act1, args.act2, args.act3) || !W1f || !W2f || passes != 6)
     return hipErrorInvalidValue;
   // split-bf16 x6 (the x9 form was dropped in round 3: no caller after the precision study): two 16-row tiles per wave sharing every W2 fragment read, 8-wave blocks
   // (246 VGPRs, 2 waves/SIMD): 1.03-1.05 ms against 1.13-1.16 ms for one tile per wave in 12-wave
@@ -2075,25 +2063,25 @@ static void readout_h16_launch(const Readout3Args& args, const h8* w, hipStream_
 }
 
 template <int DIN>
-static void readout_h16_din(const Readout3Args& args, const h8* w, hipStream_t st) {
+static hipError_t readout_h16_din(const Readout3Args& args, const h8* w, hipStream_t st) {
   switch (args.act1) {
     case IGN_K_ACT_SELU: readout_h16_launch<DIN, IGN_K_ACT_SELU>(args, w, st); break;
     case IGN_K_ACT_RELU: readout_h16_launch<DIN, IGN_K_ACT_RELU>(args, w, st); break;
     case IGN_K_ACT_TANH: readout_h16_launch<DIN, IGN_K_ACT_TANH>(args, w, st); break;
     case IGN_K_ACT_SIGMOID: readout_h16_launch<DIN, IGN_K_ACT_SIGMOID>(args, w, st); break;
-    default: readout_h16_launch<DIN, IGN_K_ACT_LINEAR>(args, w, st); break;
+    case IGN_K_ACT_LINEAR: readout_h16_launch<DIN, IGN_K_ACT_LINEAR>(args, w, st); break;
+    default: return hipErrorInvalidValue;
   }
+  return hipGetLastError();
 }
 
 hipError_t launch_readout_h16(const Readout3Args& args, const void* Wh, int din, hipStream_t st) {
   if (args.n_rows == 0) return hipSuccess;
-  if (!readout_bf_supported(din, 256, 256, args.act1, args.act2) || !Wh || !args.b1 || !args.b2 ||
+  if (!readout_bf_supported(din, 256, 256, args.act1, args.act2, args.act3) || !Wh || !args.b1 || !args.b2 ||
       !args.save1 != !args.save2)
     return hipErrorInvalidValue;
   const h8* w = static_cast<const h8*>(Wh);
-  if (din == 32) readout_h16_din<32>(args, w, st);
-  else readout_h16_din<64>(args, w, st);
-  return hipGetLastError();
+  return din == 32 ? readout_h16_din<32>(args, w, st) : readout_h16_din<64>(args, w, st);
 }
 
 // the variant-4 / variant-5 headers alone (readout_h32.hip packs its own pieces)
@@ -2129,7 +2117,19 @@ static hipError_t dense_bf_ks(const float* x, int64_t n, int x_stride, const voi
     case IGN_K_ACT_RELU: DBF(IGN_K_ACT_RELU); break;
     case IGN_K_ACT_TANH: DBF(IGN_K_ACT_TANH); break;
     case IGN_K_ACT_SIGMOID: DBF(IGN_K_ACT_SIGMOID); break;
-    default: DBF(IGN_K_ACT_LINEAR); break;
+    case IGN_K_ACT_LINEAR: DBF(IGN_K_ACT_LINEAR); break;
+    default:
+      // The other five are instantiated for the split-fp16 forward alone (dense_stack.cpp takes another
+      // kernel, or applies the derivative after, elsewhere: DESIGN.md §3f).  Never the identity in their place.
+      if constexpr (BWD || NP != 2) return hipErrorInvalidValue;
+      else switch (act) {
+        case IGN_K_ACT_ELU: DBF(IGN_K_ACT_ELU); break;
+        case IGN_K_ACT_SOFTPLUS: DBF(IGN_K_ACT_SOFTPLUS); break;
+        case IGN_K_ACT_SOFTSIGN: DBF(IGN_K_ACT_SOFTSIGN); break;
+        // (no exponential: lower_plan keeps such a plan off the scaled split-fp16 Dense kernels)
+        case IGN_K_ACT_HARD_SIGMOID: DBF(IGN_K_ACT_HARD_SIGMOID); break;
+        default: return hipErrorInvalidValue;
+      }
   }
 #undef DBF
   return hipGetLastError();
@@ -2149,12 +2149,13 @@ static hipError_t dense_bf_any(const float* x, int64_t n, int K, int x_stride, c
       case 128: return dense_bf_ks<4, 4, BWD, NP>(x, n, x_stride, W, bias, M, act, y, aprev, accumulate, xo, st);
       default: return dense_bf_ks<8, 2, BWD, NP>(x, n, x_stride, W, bias, M, act, y, aprev, accumulate, xo, st);
     }
-  }
-  switch (K) {
-    case 32: return dense_bf_ks<1, 8, BWD, NP>(x, n, x_stride, W, bias, M, act, y, aprev, accumulate, xo, st);
-    case 64: return dense_bf_ks<2, 4, BWD, NP>(x, n, x_stride, W, bias, M, act, y, aprev, accumulate, xo, st);
-    case 128: return dense_bf_ks<4, 2, BWD, NP>(x, n, x_stride, W, bias, M, act, y, aprev, accumulate, xo, st);
-    default: return dense_bf_ks<8, 1, BWD, NP>(x, n, x_stride, W, bias, M, act, y, aprev, accumulate, xo, st);
+  } else {   // (else: the other NP's stage sizes are not instantiated)
+    switch (K) {
+      case 32: return dense_bf_ks<1, 8, BWD, NP>(x, n, x_stride, W, bias, M, act, y, aprev, accumulate, xo, st);
+      case 64: return dense_bf_ks<2, 4, BWD, NP>(x, n, x_stride, W, bias, M, act, y, aprev, accumulate, xo, st);
+      case 128: return dense_bf_ks<4, 2, BWD, NP>(x, n, x_stride, W, bias, M, act, y, aprev, accumulate, xo, st);
+      default: return dense_bf_ks<8, 1, BWD, NP>(x, n, x_stride, W, bias, M, act, y, aprev, accumulate, xo, st);
+    }
   }
 }
 
@@ -2175,7 +2176,7 @@ hipError_t launch_dense_h16(const float* x, int64_t n, int K, int x_stride, cons
 hipError_t launch_dense_h16_t(const float* dz, int64_t n, int K, const void* Wth, int M, float* out, int accumulate,
                               int act, const float* aprev, hipStream_t st, OuterRows xo) {
   if (n == 0) return hipSuccess;
-  if (!dense_bf_supported(K, M) || !Wth) return hipErrorInvalidValue;
+  if (!dense_bf_supported(K, M) || !Wth || (xo.s && !act_first_five(xo.act))) return hipErrorInvalidValue;
   return dense_bf_any<true, 2>(dz, n, K, K, Wth, nullptr, M, act < 0 ? IGN_K_ACT_LINEAR : act, out,
                                act < 0 ? nullptr : aprev, accumulate, st, xo);
 }
@@ -2231,7 +2232,7 @@ hipError_t launch_pack_dense_f16(const float* W, void* out, int IN, int OUT, int
 hipError_t launch_dense_bf_t(const float* dz, int64_t n, int K, const void* Wtbf, int M, float* out, int accumulate,
                              int act, const float* aprev, hipStream_t st, OuterRows xo) {
   if (n == 0) return hipSuccess;
-  if (!dense_bf_supported(K, M) || !Wtbf) return hipErrorInvalidValue;
+  if (!dense_bf_supported(K, M) || !Wtbf || (xo.s && !act_first_five(xo.act))) return hipErrorInvalidValue;
   return dense_bf_any<true>(dz, n, K, K, Wtbf, nullptr, M, act < 0 ? IGN_K_ACT_LINEAR : act,
                             out, act < 0 ? nullptr : aprev, accumulate, st, xo);
 }

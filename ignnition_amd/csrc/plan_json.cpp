@@ -85,14 +85,20 @@ std::string quote(const std::string& s) {
   return o + "\"";
 }
 
-int activation(const JVal* a, const std::string& where) {   // _lib.ACT
+// _lib.ACT; at: the position (plan_lower.h's ACT_AT_*), which refuses what act_ok refuses there, by name
+int activation(const JVal* a, const std::string& where, int at) {
   if (!a || a->t == JVal::Null) return IGN_ACT_LINEAR;
   const std::string s = str(*a, where);
+  static const std::map<std::string, int> NEW = {{"elu", IGN_ACT_ELU}, {"softplus", IGN_ACT_SOFTPLUS},
+                                                 {"softsign", IGN_ACT_SOFTSIGN}, {"exponential", IGN_ACT_EXPONENTIAL},
+                                                 {"hard_sigmoid", IGN_ACT_HARD_SIGMOID}};
+  if (NEW.count(s) && !act_ok(NEW.at(s), at)) unsupported("activation '" + s + "' not supported");
   if (s == "None" || s == "linear") return IGN_ACT_LINEAR;
   if (s == "relu") return IGN_ACT_RELU;
   if (s == "selu") return IGN_ACT_SELU;
   if (s == "sigmoid") return IGN_ACT_SIGMOID;
   if (s == "tanh") return IGN_ACT_TANH;
+  if (NEW.count(s)) return NEW.at(s);
   unsupported("activation '" + s + "' not supported");
 }
 
@@ -117,7 +123,7 @@ struct Extra {
 // LayerNormalization layers go (a readout stack); null for a message-creation network, which takes
 // none.  The default-name counter counts every layer, Dropout included.
 std::vector<Layer> dense_layers(const JVal& architecture, const std::string& role, const char* what,
-                                std::vector<Extra>* extra) {
+                                std::vector<Extra>* extra, int at) {
   std::vector<Layer> out;
   int counter = 0;
   for (const JVal& l : arr(architecture, std::string(what) + " nn_architecture")) {
@@ -175,7 +181,7 @@ std::vector<Layer> dense_layers(const JVal& architecture, const std::string& rol
     const JVal* nm = opt(l, "name");
     y.name = nm ? str(*nm, "layer name") : "layer_" + std::to_string(counter) + "_" + type + "_" + role;
     y.d.units = (int32_t)number(need(l, "units", what), "units");
-    y.d.activation = activation(opt(l, "activation"), "activation");
+    y.d.activation = activation(opt(l, "activation"), "activation", at);
     const JVal* ub = opt(l, "use_bias");
     y.d.use_bias = ub ? (truthy(*ub) ? 1 : 0) : 1;
     const JVal* kr = opt(l, "kernel_regularizer");
@@ -406,7 +412,7 @@ Lowered lower(const JVal& data, const JVal& dims) {
         JVal tmp;
         tmp.t = JVal::Str;
         tmp.str = fn;
-        act = activation(&tmp, "convolution activation");
+        act = activation(&tmp, "convolution activation", ACT_AT_CONVOLUTION);
       }
       const int axis = aggr == "concat" ? (int)number(need(ag, "concat_axis", "concat"), "concat_axis") : 0;
       const bool feature_concat = aggr == "concat" && axis == 2;
@@ -452,7 +458,7 @@ Lowered lower(const JVal& data, const JVal& dims) {
             }
           const JVal* arch_n = nets[str(need(op, "nn_name", "message network"), "nn_name")];
           net.layers = dense_layers(need(*arch_n, "nn_architecture", "message network"),
-                                    "message_creation_" + std::to_string(net_counter), "message", nullptr);
+                                    "message_creation_" + std::to_string(net_counter), "message", nullptr, ACT_AT_MESSAGE);
           net.param_dim = extra_params;
           net.prefix = sname + "_to_" + dst + "_message_creation_0/";
         }
@@ -523,7 +529,7 @@ Lowered lower(const JVal& data, const JVal& dims) {
       d.type = IGN_RO_NEURAL_NETWORK;
       const std::string nn = str(need(op, "nn_name", "readout neural_network"), "nn_name");
       if (!nets.count(nn)) invalid("readout nn_name '" + nn + "' is not defined");
-      d.layers = dense_layers(need(*nets[nn], "nn_architecture", "readout network"), "readout", "readout", &d.extra);
+      d.layers = dense_layers(need(*nets[nn], "nn_architecture", "readout network"), "readout", "readout", &d.extra, ACT_AT_READOUT_OP);
       for (int i : d.inputs) d.in_width += p.ro_widths[i];
       const JVal* on = opt(op, "output_name");
       add(on ? str(*on, "output_name") : "None", d.layers.back().d.units, first);
@@ -564,7 +570,7 @@ Lowered lower(const JVal& data, const JVal& dims) {
   p.label = str(need(*pred, "label", "predict"), "label");
   for (const JVal& i : arr(need(*pred, "input", "predict"), "input")) p.ro_inputs.push_back(resolve(i));
   const std::string nn = pred->get("nn_name")->str;
-  p.dense = dense_layers(need(*nets[nn], "nn_architecture", "predict network"), "readout", "readout", &p.extra);
+  p.dense = dense_layers(need(*nets[nn], "nn_architecture", "predict network"), "readout", "readout", &p.extra, ACT_AT_PREDICT);
   return p;
 }
 
@@ -624,7 +630,25 @@ std::string describe(const Lowered& p, const PlanModel& m) {
          (x.center ? "true" : "false") + ", \"scale\": " + (x.scale ? "true" : "false") + ", \"units\": " +
          std::to_string(x.units) + ", \"name\": " + quote(names[i]) + "}";
   }
-  return s + "]}";
+  // The activation codes (ign_activation) the plan carries, by position: predict's Dense layers, each
+  // readout operation's (empty unless a neural_network), each MP's message networks per source, and
+  // each MP's convolution activation_function (0 for another aggregation)
+  auto codes = [](const std::vector<DenseP>& layers) {
+    std::string o = "[";
+    for (size_t l = 0; l < layers.size(); ++l) o += (l ? ", " : "") + std::to_string(layers[l].act);
+    return o + "]";
+  };
+  s += "], \"activations\": {\"predict\": " + codes(m.dense) + ", \"readout_ops\": [";
+  for (size_t k = 0; k < m.ro_ops.size(); ++k) s += (k ? ", " : "") + codes(m.ro_ops[k].layers);
+  s += "], \"message\": [";
+  for (size_t i = 0; i < m.mps.size(); ++i) {
+    s += i ? ", [" : "[";
+    for (size_t q = 0; q < m.mps[i].nn.size(); ++q) s += (q ? ", " : "") + codes(m.mps[i].nn[q].layers);
+    s += "]";
+  }
+  s += "], \"convolution\": [";
+  for (size_t i = 0; i < m.mps.size(); ++i) s += (i ? ", " : "") + std::to_string(m.mps[i].act);
+  return s + "]}}";
 }
 
 }  // namespace

@@ -64,7 +64,7 @@ int lower_mps(const ign_plan_desc* d, PlanModel* p) {
       case IGN_AGGR_CONVOLUTION:
         mp.sorted = false;
         mp.act = md.activation;
-        if (mp.aggr == IGN_AGGR_CONVOLUTION && !act_ok(mp.act))
+        if (mp.aggr == IGN_AGGR_CONVOLUTION && !act_ok(mp.act, ACT_AT_CONVOLUTION))
           return fail(IGN_ERR_UNSUPPORTED, "mp %d: convolution activation %d", m, mp.act);
         break;
       default:
@@ -104,7 +104,7 @@ int lower_mps(const ign_plan_desc* d, PlanModel* p) {
           dp.use_bias = s.msg_layers[l].use_bias;
           dp.l2 = s.msg_layers[l].l2;   // kernel_regularizer: part of model.losses (AUX:833-834)
           if (dp.out <= 0) return fail(IGN_ERR_INVALID, "mp %d: message layer %d units", m, l);
-          if (!act_ok(dp.act)) return fail(IGN_ERR_UNSUPPORTED, "mp %d: message layer activation %d", m, dp.act);
+          if (!act_ok(dp.act, ACT_AT_MESSAGE)) return fail(IGN_ERR_UNSUPPORTED, "mp %d: message layer activation %d", m, dp.act);
           nn.layers.push_back(dp);
           in = dp.out;
         }
@@ -156,7 +156,7 @@ int lower_mps(const ign_plan_desc* d, PlanModel* p) {
   return IGN_OK;
 }
 
-int parse_dense(const ign_dense_desc* d, int n, int in, std::vector<DenseP>& out, const char* what, int idx) {
+int parse_dense(const ign_dense_desc* d, int n, int in, std::vector<DenseP>& out, const char* what, int idx, int at) {
   for (int l = 0; l < n; ++l) {
     DenseP dp;
     dp.in = in;
@@ -165,7 +165,7 @@ int parse_dense(const ign_dense_desc* d, int n, int in, std::vector<DenseP>& out
     dp.use_bias = d[l].use_bias;
     dp.l2 = d[l].l2;
     if (dp.out <= 0) return fail(IGN_ERR_INVALID, "%s %d, dense layer %d: units must be > 0", what, idx, l);
-    if (!act_ok(dp.act)) return fail(IGN_ERR_UNSUPPORTED, "%s %d, dense layer %d: activation %d", what, idx, l, dp.act);
+    if (!act_ok(dp.act, at)) return fail(IGN_ERR_UNSUPPORTED, "%s %d, dense layer %d: activation %d", what, idx, l, dp.act);
     out.push_back(dp);
     in = dp.out;
   }
@@ -210,7 +210,7 @@ int lower_readout(const ign_plan_desc* d, PlanModel* p) {
           op.in_width += p->ro_t[id].width;
         }
         if (od.num_dense <= 0 || !od.dense) return fail(IGN_ERR_INVALID, "readout op %d: no Dense layer", k);
-        if ((rc = parse_dense(od.dense, od.num_dense, op.in_width, op.layers, "readout op", k))) return rc;
+        if ((rc = parse_dense(od.dense, od.num_dense, op.in_width, op.layers, "readout op", k, ACT_AT_READOUT_OP))) return rc;
         for (int l = 0; l < od.num_dense; ++l) op.seq.push_back({SL_DENSE, l});
         p->ro_t.push_back({t0.space, t0.sid, op.layers.back().out});
         break;
@@ -270,12 +270,13 @@ int lower_readout(const ign_plan_desc* d, PlanModel* p) {
     width += p->ro_t[id].width;
   }
   p->ro_width = width;
-  int rc = parse_dense(d->dense, d->num_dense, width, p->dense, "predict", 0);
+  int rc = parse_dense(d->dense, d->num_dense, width, p->dense, "predict", 0, ACT_AT_PREDICT);
   if (rc) return rc;
   if (p->dense.empty()) return fail(IGN_ERR_INVALID, "readout has no Dense layer");
   for (int l = 0; l < d->num_dense; ++l) p->seq.push_back({SL_DENSE, l});
   p->fused_readout = p->dense.size() == 3 &&
-                     readout3_supported(width, p->dense[0].out, p->dense[1].out, p->dense[0].act, p->dense[1].act) &&
+                     readout3_supported(width, p->dense[0].out, p->dense[1].out, p->dense[0].act, p->dense[1].act,
+                                        p->dense[2].act) &&
                      p->dense[2].out == 1 && p->dense[0].use_bias && p->dense[1].use_bias;
   return IGN_OK;
 }
@@ -386,7 +387,8 @@ void layout_packed(PlanModel* p) {
     if ((p->fused_readout && l < 2) || dense_fwd_supported(in, out))
       dp.pk_w = slot(AT_DENSE, l, 0, PK_DENSE_PAD, pack_dense_floats(in, out), dp.off_w, -1, -1, in, in, out);
     if (p->fused_readout && l < 2 && in % 32 == 0 && out % 16 == 0 &&
-        readout_bf_supported(p->dense[0].in, p->dense[0].out, p->dense[1].out, p->dense[0].act, p->dense[1].act)) {
+        readout_bf_supported(p->dense[0].in, p->dense[0].out, p->dense[1].out, p->dense[0].act, p->dense[1].act,
+                             p->dense[2].act)) {
       // layer 1 reads its input from memory (natural k), layer 2 chains from registers
       dp.pk_bf = slot(AT_DENSE, l, 1, PK_DENSE_BF16, pack_dense_bf16_floats(in, out), dp.off_w, -1, -1, in, out, l != 0);
       if (l == 1) {
@@ -550,6 +552,21 @@ int lower_plan(const ign_plan_desc* d, const PlanSwitches& sw, PlanModel* m) {
   static_cast<PlanSwitches&>(*m) = sw;
   int rc;
   if ((rc = lower_mps(d, m)) || (rc = lower_readout(d, m))) return rc;
+  // exp(z) and whatever a relu / selu / linear layer makes of it reach 2^127, beyond the 2^75 a tile of
+  // dense_h16 (forward and transposed) scales into fp16 range (its exponent clamp): a plan that names
+  // `exponential` anywhere runs its Dense stacks on split-bf16 (exact pieces, no scale) and f32 operands
+  auto has_exp = [](const std::vector<DenseP>& layers) {
+    for (const DenseP& l : layers)
+      if (l.act == IGN_ACT_EXPONENTIAL) return true;
+    return false;
+  };
+  bool any_exp = has_exp(m->dense);
+  for (const RoOp& op : m->ro_ops) any_exp = any_exp || has_exp(op.layers);
+  for (const MPP& mp : m->mps) {
+    any_exp = any_exp || (mp.aggr == IGN_AGGR_CONVOLUTION && mp.act == IGN_ACT_EXPONENTIAL);
+    for (const MsgNN& nn : mp.nn) any_exp = any_exp || has_exp(nn.layers);
+  }
+  if (any_exp) m->train_dense_h16 = false;
   mark_dead_last(m);
   layout_params(m);
   layout_packed(m);

@@ -81,7 +81,8 @@ struct PlanSwitches {
   int sum_variant = 8;            // sum update: 8 = split-fp16 GRU step at DIN = H = 64 and split-bf16
                                   // at 32, 7 = split-bf16 at both, 3 = f32 MFMA; IGN_SUM_VARIANT
   bool train_dense_bf = true;     // training forward's Dense layers on dense_bf (IGN_TRAIN_DENSE_BF=0: f32)
-  bool train_dense_h16 = true;    // ... on the split-fp16 form of dense_bf (IGN_TRAIN_DENSE_H16=0: split-bf16)
+  bool train_dense_h16 = true;    // ... on the split-fp16 form of dense_bf (IGN_TRAIN_DENSE_H16=0: split-bf16;
+                                  // lower_plan turns it off for a plan that names `exponential`)
   bool tsgemm_bf = true;          // weight-gradient row contractions on tsgemm_bf (IGN_TSGEMM_BF=0: f32 MFMA)
   bool train_fused_readout = true;   // training forward's readout on readout_h16 with saves (IGN_TRAIN_FUSED_READOUT=0: per layer)
   bool fuse_outer_bwd = true;     // 1-unit output layer's backward formed on the fly (IGN_FUSE_OUTER_BWD=0: row_outer_t)
@@ -204,7 +205,19 @@ int lower_plan(const ign_plan_desc* d, const PlanSwitches& sw, PlanModel* m);
 // forward, from the states the forward left, with the same result.  Anything else keeps the MP live.
 void mark_dead_last(PlanModel* m);
 
-inline bool act_ok(int a) { return a >= IGN_ACT_LINEAR && a <= IGN_ACT_TANH; }
+// The activation codes a position of the model takes.  Predict's Dense layers take all ten.  Three
+// position / code pairs, and softplus as a convolution activation, stay refused as they were before
+// elu .. hard_sigmoid were lowered: the kernels make no such difference.
+enum { ACT_AT_PREDICT, ACT_AT_READOUT_OP, ACT_AT_MESSAGE, ACT_AT_CONVOLUTION };
+inline bool act_ok(int a, int at) {
+  if (a < IGN_ACT_LINEAR || a > IGN_ACT_HARD_SIGMOID) return false;
+  switch (at) {
+    case ACT_AT_READOUT_OP: return a != IGN_ACT_ELU;
+    case ACT_AT_MESSAGE: return a != IGN_ACT_HARD_SIGMOID;
+    case ACT_AT_CONVOLUTION: return a != IGN_ACT_SOFTPLUS && a != IGN_ACT_HARD_SIGMOID;
+    default: return true;
+  }
+}
 
 // the training forward's ordered update: split-fp16 x3 with state saving (seq_gru_h16<SAVE>) where
 // the backward can recompute its gates bitwise (fused seq_gru_bwd, H = 32; IGN_TRAIN_SEQ_H16=0: the

@@ -365,7 +365,7 @@ void readout_h32_kernel(Readout3Args a, const h8* __restrict__ Wp) {
             if (row[t] < a.n_rows) st4(a.save2 + row[t] * kN2 + 32 * v + 8 * m + 4 * h, av * cSS[t]);
         }
       y += __shfl_xor(y, 32);
-      if (h == 0 && row[t] < a.n_rows) a.y[row[t]] = act_apply(fmaf(y, cSS[t], b3), a.act3);
+      if (h == 0 && row[t] < a.n_rows) a.y[row[t]] = act_apply_base(fmaf(y, cSS[t], b3), a.act3);
     }
   }
 }
@@ -380,25 +380,25 @@ static void readout_h32_launch(const Readout3Args& args, const h8* w, hipStream_
 }
 
 template <int DIN>
-static void readout_h32_din(const Readout3Args& args, const h8* w, hipStream_t st) {
+static hipError_t readout_h32_din(const Readout3Args& args, const h8* w, hipStream_t st) {
   switch (args.act1) {
     case IGN_K_ACT_SELU: readout_h32_launch<DIN, IGN_K_ACT_SELU>(args, w, st); break;
     case IGN_K_ACT_RELU: readout_h32_launch<DIN, IGN_K_ACT_RELU>(args, w, st); break;
     case IGN_K_ACT_TANH: readout_h32_launch<DIN, IGN_K_ACT_TANH>(args, w, st); break;
     case IGN_K_ACT_SIGMOID: readout_h32_launch<DIN, IGN_K_ACT_SIGMOID>(args, w, st); break;
-    default: readout_h32_launch<DIN, IGN_K_ACT_LINEAR>(args, w, st); break;
+    case IGN_K_ACT_LINEAR: readout_h32_launch<DIN, IGN_K_ACT_LINEAR>(args, w, st); break;
+    default: return hipErrorInvalidValue;
   }
+  return hipGetLastError();
 }
 
 hipError_t launch_readout_h32(const Readout3Args& args, const void* Wh, int din, hipStream_t st) {
   if (args.n_rows == 0) return hipSuccess;
-  if ((din != 32 && din != 64) || !Wh || !args.b1 || !args.b2 || !args.w3 || args.act1 != args.act2 ||
+  if ((din != 32 && din != 64) || !Wh || !args.b1 || !args.b2 || !args.w3 || !fused_readout_acts(args.act1, args.act2, args.act3) ||
       (args.save1 != nullptr) != (args.save2 != nullptr))
     return hipErrorInvalidValue;
   const h8* w = static_cast<const h8*>(Wh);
-  if (din == 32) readout_h32_din<32>(args, w, st);
-  else readout_h32_din<64>(args, w, st);
-  return hipGetLastError();
+  return din == 32 ? readout_h32_din<32>(args, w, st) : readout_h32_din<64>(args, w, st);
 }
 
 // the headers by pack_readout_h16_kernel (the same positions), then the variant-5 pieces

@@ -30,20 +30,6 @@ namespace {
 
 constexpr float kInv2Log2e = 0.34657359027997264f;   // 1 / (2 log2 e)
 
-__device__ __forceinline__ float act_grad(float a, int act) {
-  // derivative of the activation expressed through its output a
-  switch (act) {
-    case IGN_K_ACT_RELU: return a > 0.f ? 1.f : 0.f;
-    case IGN_K_ACT_SELU: {
-      const float lam = 1.0507009873554805f, la = 1.0507009873554805f * 1.6732632423543772f;
-      return a > 0.f ? lam : a + la;
-    }
-    case IGN_K_ACT_SIGMOID: return a * (1.f - a);
-    case IGN_K_ACT_TANH: return 1.f - a * a;
-    default: return 1.f;
-  }
-}
-
 // pack_a: Mat [rows][cols] row-major -> float4-grouped A fragments, tiles over rows, k over cols:
 //   element ((t * KS/4 + s/4) * 64 + lane) * 4 + s%4 = Mat[16t + (lane&15)][k(s, lane>>4)], KS = cols/4
 __global__ void pack_a_kernel(const float* __restrict__ M, int rows, int cols, float* __restrict__ out) {
@@ -810,7 +796,7 @@ __global__ void conv_bwd_kernel(const float* __restrict__ dx, const float* __res
   const int64_t total = n * F;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const float d = deg[i / F];
-    const float v = dx[i] * act_grad(x[i], act) / d;
+    const float v = dx[i] * act_grad_out(x[i], act) / d;
     du[i] = d > 0.f ? v : 0.f;
     dh[i] += v;
   }
@@ -875,7 +861,7 @@ __global__ __launch_bounds__(256) void row_gemm_t_kernel(const float* __restrict
     if (act >= 0) {
       const f4 av = ld4(aprev + r * M + 16 * t + 4 * g);
 #pragma unroll
-      for (int q = 0; q < 4; ++q) v[q] *= act_grad(av[q], act);
+      for (int q = 0; q < 4; ++q) v[q] *= act_grad_out(av[q], act);
     }
     if (accumulate) v += ld4(po);
     st4(po, v);
@@ -891,7 +877,7 @@ __global__ void row_gemm_t_generic_kernel(const float* __restrict__ in, int64_t 
     const int m = (int)(e - r * M);
     float s = 0.f;
     for (int k = 0; k < K; ++k) s += in[r * K + k] * Mat[(int64_t)m * K + k];
-    if (act >= 0) s *= act_grad(aprev[e], act);
+    if (act >= 0) s *= act_grad_out(aprev[e], act);
     out[e] = accumulate ? out[e] + s : s;
   }
 }
@@ -913,7 +899,7 @@ __global__ void row_outer_t_kernel(const float* __restrict__ in, int64_t n, cons
     for (int q = 0; q < 4; ++q) {
       float s = 0.f;
       s += x * w[q];
-      if (act >= 0) s *= act_grad(av[q], act);
+      if (act >= 0) s *= act_grad_out(av[q], act);
       o[q] = accumulate ? o[q] + s : s;
     }
     st4(out + r * M + m, o);
@@ -933,7 +919,7 @@ __global__ void split_cols_add_kernel(float* __restrict__ dst, int64_t n, int wi
 __global__ void act_bwd_kernel(const float* __restrict__ da, const float* __restrict__ a, int64_t n, int act,
                                float* __restrict__ dz) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    dz[i] = da[i] * act_grad(a[i], act);
+    dz[i] = da[i] * act_grad_out(a[i], act);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1534,6 +1520,7 @@ hipError_t launch_attn_param_bwd(const float* dw12, const float* K1, const float
 
 hipError_t launch_conv_bwd(const float* dx, const float* x, const float* deg, int64_t n, int F, int act, float* du,
                            float* dh, hipStream_t st) {
+  if (!act_code_ok(act)) return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(conv_bwd_kernel, dim3(blocks_for(n * F)), dim3(256), 0, st, dx, x, deg, n, F, act, du, dh);
   return hipGetLastError();
@@ -1577,6 +1564,7 @@ hipError_t launch_csr_gather_add(float* out, int64_t n_rows, const int32_t* ptr,
 
 hipError_t launch_row_gemm_t(const float* in, int64_t n, int K, const float* Ap, int M, float* out, int accumulate,
                              int act, const float* aprev, hipStream_t st) {
+  if (act >= 0 && !act_code_ok(act)) return hipErrorInvalidValue;   // act < 0: no derivative applied
   if (n == 0) return hipSuccess;
   dim3 grid((unsigned)((n + 63) / 64));
 #define RG_CASE(KK, MM)                                                                                  \
@@ -1599,6 +1587,7 @@ hipError_t launch_row_gemm_t(const float* in, int64_t n, int K, const float* Ap,
 
 hipError_t launch_row_gemm_t_generic(const float* in, int64_t n, int K, const float* Mat, int M, float* out,
                                      int accumulate, int act, const float* aprev, hipStream_t st) {
+  if (act >= 0 && !act_code_ok(act)) return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
   if (K == 1 && M % 4 == 0) {
     hipLaunchKernelGGL(row_outer_t_kernel, dim3(blocks_for(n * (M / 4))), dim3(256), 0, st, in, n, Mat, M, out,
@@ -1619,6 +1608,7 @@ hipError_t launch_split_cols_add(float* dst, int64_t n, int width, const float* 
 }
 
 hipError_t launch_act_bwd(const float* da, const float* a, int64_t n, int act, float* dz, hipStream_t st) {
+  if (!act_code_ok(act)) return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(act_bwd_kernel, dim3(blocks_for(n)), dim3(256), 0, st, da, a, n, act, dz);
   return hipGetLastError();
@@ -1686,6 +1676,7 @@ hipError_t launch_colsum_add(const float* B, int ldb, int64_t n_rows, int N, flo
 
 hipError_t launch_dense_fwd(const float* x, int64_t n, int K, int x_stride, const float* Wp, const float* W,
                             const float* bias, int M, int act, float* y, hipStream_t st) {
+  if (!act_code_ok(act)) return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
   if (M == 1 && K % 4 == 0 && x_stride % 4 == 0) {
     hipLaunchKernelGGL(dense_dot_kernel, dim3((unsigned)((n * 16 + 255) / 256)), dim3(256), 0, st, x, n, K, x_stride,

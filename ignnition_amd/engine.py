@@ -79,7 +79,7 @@ def _message_net(s, dst, plan, eidx):
             raise UnsupportedModel("message layer type %s is not lowered (Dense only)" % l.type)
         prm = dict(l.parameters)
         act = prm.get("activation", None)
-        if act not in _lib.ACT:
+        if act not in _lib.ACT or act in _lib.ACT_REFUSED_AT["message"]:
             raise UnsupportedModel("activation %r not supported" % act)
         known = {"units", "activation", "kernel_regularizer", "name", "use_bias"}
         if set(prm) - known:
@@ -149,8 +149,8 @@ class MPPlan:
                 act = 0
                 if aggr == "convolution":       # AUX:370-374: activation_function, default relu
                     fn = getattr(mp.aggregation, "activation_function", "relu")
-                    if fn not in _lib.ACT:
-                        raise UnsupportedModel("convolution activation %r is not lowered" % fn)
+                    if fn not in _lib.ACT or fn in _lib.ACT_REFUSED_AT["convolution"]:
+                        raise UnsupportedModel("activation %r not supported" % fn)
                     act = _lib.ACT[fn]
                 feature_concat = aggr == "concat" and mp.aggregation.concat_axis == 2
                 srcs = []
@@ -186,7 +186,7 @@ class MPPlan:
         return p
 
     @staticmethod
-    def _dense_layers(arch, what):
+    def _dense_layers(arch, what, at="predict"):
         """(Dense layers, the other layers) of a readout stack.  The second list holds the stack's
         Dropout and LayerNormalization layers in the architecture's order, the one record of where
         each stands: ("dropout", before_layer, rate, seed) or ("layernorm", before_layer, epsilon,
@@ -229,7 +229,7 @@ class MPPlan:
                                        % (what, l.type))
             prm = dict(l.parameters)
             act = prm.get("activation", None)
-            if act not in _lib.ACT:
+            if act not in _lib.ACT or act in _lib.ACT_REFUSED_AT[at]:
                 raise UnsupportedModel("activation %r not supported" % act)
             known = {"units", "activation", "kernel_regularizer", "name", "use_bias"}
             if set(prm) - known:
@@ -269,7 +269,7 @@ class MPPlan:
             first = self.ro_spaces[ids[0]]
             d = {"type": op.type, "inputs": ids, "mode": 0, "adj": -1, "layers": [], "counter": counter}
             if op.type == "neural_network":
-                d["layers"], d["extra"] = self._dense_layers(op.architecture, "readout")
+                d["layers"], d["extra"] = self._dense_layers(op.architecture, "readout", "readout_op")
                 d["in_width"] = sum(self.ro_widths[i] for i in ids)
                 add(op.output_name, d["layers"][-1][1], first)
             elif op.type == "pooling":

@@ -66,7 +66,12 @@ enum ign_activation {         /* Dense activations accepted by the readout (AUX:
   IGN_ACT_RELU = 1,
   IGN_ACT_SELU = 2,
   IGN_ACT_SIGMOID = 3,
-  IGN_ACT_TANH = 4
+  IGN_ACT_TANH = 4,
+  IGN_ACT_ELU = 5,             /* alpha 1 */
+  IGN_ACT_SOFTPLUS = 6,
+  IGN_ACT_SOFTSIGN = 7,
+  IGN_ACT_EXPONENTIAL = 8,
+  IGN_ACT_HARD_SIGMOID = 9     /* clip(0.2 z + 0.5, 0, 1) (TF 2.x tf.keras.activations) */
 };
 
 typedef struct ign_plan ign_plan;
@@ -228,7 +233,9 @@ int  ign_plan_create_json(const char* model_json, const char* dims_json, int32_t
 /* For a plan from ign_plan_create_json: a JSON document with the entity / feature order, every
  * adjacency slot's input keys (src_<adj>, dst_<adj>, seq_<src>_<dst>, GM:127-158), the interleave
  * keys (indices_<src>_to_<dst>), the label and the parameter tensors' Keras-style names and shapes
- * in ign_plan_param_tensor order.  *needed = bytes incl. the terminating NUL; buf may be NULL. */
+ * in ign_plan_param_tensor order, and under "activations" the ign_activation codes the plan carries
+ * (predict's layers, each readout operation's, each MP's message networks per source, each MP's
+ * convolution activation_function).  *needed = bytes incl. the terminating NUL; buf may be NULL. */
 int  ign_plan_describe_json(const ign_plan* plan, char* buf, int64_t size, int64_t* needed);
 void ign_plan_destroy(ign_plan* plan);
 int  ign_plan_num_params(const ign_plan* plan, int64_t* n_floats);
