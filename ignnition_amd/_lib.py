@@ -40,6 +40,10 @@ class CellDesc(C.Structure):
     _fields_ = [("input_dim", i32), ("units", i32)]
 
 
+class CellOptions(C.Structure):
+    _fields_ = [("activation", i32), ("recurrent_activation", i32), ("use_bias", i32), ("reset_after", i32)]
+
+
 class ReadoutOpDesc(C.Structure):
     _fields_ = [("type", i32), ("num_inputs", i32), ("inputs", C.POINTER(i32)), ("mode", i32),
                 ("adjacency", i32), ("num_dense", i32), ("dense", C.POINTER(DenseDesc))]
@@ -122,7 +126,7 @@ SYMBOLS = ["ign_abi_version", "ign_last_error", "ign_device_count", "ign_plan_cr
            "ign_batch_train_buffers", "ign_batch_read_predictions", "ign_batch_resident_info",
            "ign_loss_kind", "ign_optimizer_kind", "ign_loss", "ign_optimizer_num_slots", "ign_optimizer_step",
            "ign_plan_add_dropout", "ign_batch_set_dropout", "ign_dropout_keep", "ign_plan_add_layernorm",
-           "ign_plan_mp_dead_last"]
+           "ign_plan_mp_dead_last", "ign_plan_set_cell_options"]
 
 ABI_VERSION = 13
 PART = {"all": 0, "interior": 1, "boundary": 2}
@@ -208,6 +212,7 @@ def _load():
         "ign_batch_set_dropout": (C.c_int, [VP, C.c_uint64, C.c_uint32]),
         "ign_dropout_keep": (C.c_int, [C.c_uint64, i32, C.c_uint32, i64, i64, f32, P(C.c_uint8)]),
         "ign_plan_mp_dead_last": (C.c_int, [VP, i32, P(i32)]),
+        "ign_plan_set_cell_options": (C.c_int, [VP, i32, P(CellOptions)]),
     }
     # an A/B build of an older tree may lack newer entry points: only the A/B tools, which set
     # IGN_AB_LIB=1 next to IGN_LIB_PATH, skip them; any other library must export every symbol

@@ -18,7 +18,7 @@ OUT = os.path.join(HERE, "libignmp.so")
 ISA_MIX = os.path.join(HERE, "isa_mix.json")
 SOURCES = ["engine.cpp", "mp_step.cpp", "plan_lower.cpp", "batch_lower.cpp", "devpool.cpp", "train.cpp", "dense_stack.cpp", "train_lower.cpp", "learn.cpp", "readout.cpp", "dataset.cpp", "plan_json.cpp", "kernels.hip", "kernels_bf.hip",
            "train_kernels.hip", "learn_kernels.hip", "readout_kernels.hip", "resident.hip", "readout_h32.hip", "train_csr.hip",
-           "dropout.cpp", "dropout_kernels.hip", "layernorm.cpp", "layernorm_kernels.hip"]
+           "dropout.cpp", "dropout_kernels.hip", "layernorm.cpp", "layernorm_kernels.hip", "cell_options.cpp", "gru_cell.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-Wno-unused-value"]
 EXTRA = {"kernels_bf.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "resident.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
          "readout_h32.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}

@@ -285,11 +285,11 @@ int ign::repack(ign_plan* p) {
     float* const dst = p->d_packed + j->dst;
     switch (j->kind) {
       case PK_GRU:   // the two records after it: its U and bias slots
-        HIP_TRY(launch_pack_gru(s[0], s[1], s[2], dst, p->d_packed + j[1].dst, p->d_packed + j[2].dst, j->a, j->b, st));
+        HIP_TRY(launch_pack_gru(s[0], s[1], s[2], dst, p->d_packed + j[1].dst, p->d_packed + j[2].dst, j->a, j->b, j->c, st));
         break;
       case PK_GRU_U:
       case PK_GRU_B: break;
-      case PK_GRU_W: HIP_TRY(launch_pack_gru(s[0], nullptr, nullptr, dst, nullptr, nullptr, j->a, j->b, st)); break;
+      case PK_GRU_W: HIP_TRY(launch_pack_gru(s[0], nullptr, nullptr, dst, nullptr, nullptr, j->a, j->b, j->c, st)); break;
       case PK_U_BF16: HIP_TRY(launch_pack_u_bf16(s[0], dst, j->a, st)); break;
       case PK_U_F16: HIP_TRY(launch_pack_u_f16(s[0], dst, j->a, st)); break;
       case PK_UT_F16: HIP_TRY(launch_pack_ut_f16(s[0], dst, j->a, st)); break;

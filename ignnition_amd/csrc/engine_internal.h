@@ -277,6 +277,8 @@ int64_t stack_rows(const ign_plan* p, const ign_batch* b, int stack);
 int plan_add_dropout(ign_plan* p, int stack, int before_layer, float rate, uint64_t layer_seed);
 // ign_plan_add_layernorm's routine (likewise)
 int plan_add_layernorm(ign_plan* p, int stack, int before_layer, float epsilon, int center, int scale);
+// ign_plan_set_cell_options' routine (likewise)
+int plan_set_cell_options(ign_plan* p, int cell, const ign_cell_options* o);
 // readout tensor id (GM:660-675): an entity's final states (ent's, as readout_ops_run) or an operation's output
 const float* readout_tensor(const ign_plan* p, const ign_batch* b, int id, const float* const* ent = nullptr);
 // predict's input rows into *x: its one input tensor, or its inputs side by side in cat

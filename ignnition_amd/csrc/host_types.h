@@ -72,6 +72,12 @@ struct CellP {
   int64_t pk_uh = -1;             // split-fp16 recurrent-kernel fragments + scale (seq variants 6/7)
   int64_t pk_uth = -1;            // backward: split-fp16 U fragments for dh = du . U^T (H = 32)
   bool used = false;
+  // ign_plan_set_cell_options (Keras GRUCell defaults).  A cell with any other value is a non-default
+  // cell: unscaled pack_gru fragments, none of the split pieces above, the generalised kernels
+  int act = IGN_ACT_TANH, ract = IGN_ACT_SIGMOID;
+  bool use_bias = true, reset_after = true;
+  bool is_default() const { return act == IGN_ACT_TANH && ract == IGN_ACT_SIGMOID && use_bias && reset_after; }
+  int bias_rows() const { return !use_bias ? 0 : reset_after ? 2 : 1; }   // of [3H] in the raw layout
 };
 
 struct DenseP {

@@ -40,6 +40,17 @@ inline bool bwd_shape_supported(int din, int h) {
          (din != 64 || h == 64);
 }
 inline bool seq_bwd_fused_supported(int h) { return h == 16 || h == 32; }
+// the generalised cell kernels (gru_cell.hip): the ordered update and its backward at H 16 / 32 / 64;
+// the sum update at the four 16 / 32 shapes in every mode (0 sum, 1 attention, 2 convolution: DIN = H)
+// and at 64 / 64 as a plain sum; the sum backward (mode 0's predicate) at all five
+inline bool gru_cell_seq_supported(int h) { return h == 16 || h == 32 || h == 64; }
+inline bool gru_cell_sum_supported(int din, int h, int mode) {
+  if (din == 64 && h == 64) return mode == 0;
+  return (din == 16 || din == 32) && (h == 16 || h == 32) && mode >= 0 && mode <= 2 && (mode != 2 || din == h);
+}
+// pack_gru's mode: 0 the default cell (scaled fragments, bias [2][3H]); else kPackGruRaw | the raw
+// bias tensor's rows (2: [2][3H], 1: [3H], 0: none, a block of zeros)
+constexpr int kPackGruRaw = 4;
 inline bool row_gemm_supported(int K, int M) {
   return (K == 48 || K == 96 || K == 192 || K == 256) && (M == 16 || M == 32 || M == 64 || M == 256);
 }

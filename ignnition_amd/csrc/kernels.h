@@ -97,8 +97,9 @@ struct Readout3Args {
 };
 
 hipError_t launch_init_state(float* state, const float* feats, int64_t n, int H, int F, hipStream_t st);
+// mode: 0 the default cell, else kPackGruRaw | the bias tensor's rows (kernel_shapes.h)
 hipError_t launch_pack_gru(const float* W, const float* U, const float* bias, float* Wp, float* Up, float* bp,
-                           int DIN, int H, hipStream_t st);
+                           int DIN, int H, int mode, hipStream_t st);
 hipError_t launch_pack_dense(const float* W, float* Wp, int IN, int OUT, hipStream_t st);
 hipError_t launch_project(const float* x, int64_t n, const float* Wp, const float* bp, float* out, float* bias_row,
                           int din, int h, hipStream_t st);

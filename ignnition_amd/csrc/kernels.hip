@@ -58,9 +58,14 @@ __global__ void init_state4_kernel(f4* __restrict__ state, const float* __restri
 // bias [2][3H]; gate column order z, r, h (AUX:748-749).
 // Packed fragment (gate, t, s), 64 lanes each, stored float4-grouped over s (see below):
 //   lane l -> M[k(s, l>>4)][gate*H + 16t + (l&15)]
+// mode (kernel_shapes.h): 0 the default cell.  kPackGruRaw | rows, a cell with options
+// (ign_plan_set_cell_options): unscaled fragments for gru_cell.hip, and the bias tensor [2][3H],
+// [3H] (reset_after false: b_hh = 0) or absent (use_bias false: the block is zeros).
 __global__ void pack_gru_kernel(const float* __restrict__ W, const float* __restrict__ U,
                                 const float* __restrict__ bias, float* __restrict__ Wp,
-                                float* __restrict__ Up, float* __restrict__ bp, int DIN, int H) {
+                                float* __restrict__ Up, float* __restrict__ bp, int DIN, int H, int mode) {
+  const bool raw = (mode & kPackGruRaw) != 0;
+  const int brows = raw ? (mode & 3) : 2;
   int NT = H / 16;
   int64_t nW = 3LL * NT * (DIN / 4) * 64;
   int64_t nU = 3LL * NT * (H / 4) * 64;
@@ -82,7 +87,7 @@ __global__ void pack_gru_kernel(const float* __restrict__ W, const float* __rest
       int gate = (int)(gt / NT);
       int k = 16 * (s >> 2) + 4 * (lane >> 4) + (s & 3);
       int col = gate * H + 16 * t + (lane & 15);
-      const float sc = gate == 2 ? IGN_2LOG2E : IGN_NLOG2E;   // see sig2_/tanh2_
+      const float sc = raw ? 1.0f : gate == 2 ? IGN_2LOG2E : IGN_NLOG2E;   // see sig2_/tanh2_
       if (isU) Up[idx] = sc * U[(int64_t)k * 3 * H + col];
       else     Wp[idx] = sc * W[(int64_t)k * 3 * H + col];
     } else {
@@ -92,7 +97,12 @@ __global__ void pack_gru_kernel(const float* __restrict__ W, const float* __rest
       const float* bin = bias;            // bias[0][:]
       const float* brec = bias + 3 * H;   // bias[1][:]
       float v;
-      if (which == 0) v = IGN_NLOG2E * (bin[u] + brec[u]);
+      if (raw) {
+        const int col = (which < 2 ? which : 2) * H + u;
+        const float bi = brows >= 1 && which < 3 ? bin[col] : 0.f;
+        const float br = brows == 2 && which != 2 ? brec[col] : 0.f;
+        v = bi + br;
+      } else if (which == 0) v = IGN_NLOG2E * (bin[u] + brec[u]);
       else if (which == 1) v = IGN_NLOG2E * (bin[H + u] + brec[H + u]);
       else if (which == 2) v = IGN_2LOG2E * bin[2 * H + u];
       else v = IGN_2LOG2E * brec[2 * H + u];
@@ -939,8 +949,10 @@ hipError_t launch_init_state(float* state, const float* feats, int64_t n, int H,
 }
 
 hipError_t launch_pack_gru(const float* W, const float* U, const float* bias, float* Wp, float* Up, float* bp,
-                           int DIN, int H, hipStream_t st) {
-  hipLaunchKernelGGL(pack_gru_kernel, dim3(64), dim3(256), 0, st, W, U, bias, Wp, Up, bp, DIN, H);
+                           int DIN, int H, int mode, hipStream_t st) {
+  if (mode != 0 && ((mode & ~(kPackGruRaw | 3)) || !(mode & kPackGruRaw) || (mode & 3) == 3)) return hipErrorInvalidValue;
+  if (Up && !bias && (mode & 3) != 0) return hipErrorInvalidValue;   // a bias tensor the caller did not pass
+  hipLaunchKernelGGL(pack_gru_kernel, dim3(64), dim3(256), 0, st, W, U, bias, Wp, Up, bp, DIN, H, mode);
   return hipGetLastError();
 }
 

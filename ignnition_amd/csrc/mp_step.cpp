@@ -172,6 +172,13 @@ int mp_forward(ign_plan* p, ign_batch* b, int mi, int part, MpStates s, const Mp
     if (cp.pk_ubf >= 0) a.Ubf = p->d_packed + cp.pk_ubf;
     if (cp.pk_uh >= 0) a.Uh = p->d_packed + cp.pk_uh;
     a.hdr = mb.d_seq_hdr;
+    if (!cp.is_default()) {   // a cell with options: seq_gru_cell (f32 MFMA; reset_after false: a second K = H sweep)
+      tm.begin(K_SEQ, mb.flops, mb.bytes, 0,
+               (double)mb.wave_steps * 3 * (cp.H / 16) * (cp.H / 4) * kMfmaF32Flops);
+      HIP_TRY(launch_seq_gru_cell(a, cp.H, cell_opt(cp), st));
+      tm.end();
+      return IGN_OK;
+    }
     const int v = saving ? train_seq_variant(p, cp.H) : p->seq_variant;
     {   // MFMAs per wave step: split-fp16 / split-bf16 (variants 6, 7 / 4, 5; H = 32 / 64) passes x
         // 3 gates x H/16 x H/32 on the 16x16x32 pipe; f32 (seq_gru2) 3 gates x H/16 x H/4
@@ -200,7 +207,11 @@ int mp_forward(ign_plan* p, ign_batch* b, int mi, int part, MpStates s, const Mp
   if (count <= 0) return IGN_OK;
   // windowed or segmented aggregation (sum MPs over all destinations): the sum kernel writes x,
   // then the GRU step reads it through an identity CSR (one message per destination: x itself)
-  const bool pre = (mb.n_win_wg > 0 || mb.sum_seg) && part == IGN_PART_ALL && mp.aggr == IGN_AGGR_SUM && !saving;
+  // (the training forward of a plan of default cells sums in the lane walk; a plan with a cell with
+  // options, for all its sum MPs, default cells' included, keeps one summation order for both forwards,
+  // so its training forward gives the inference forward's bits: DESIGN.md 3g)
+  const bool pre = (mb.n_win_wg > 0 || mb.sum_seg) && part == IGN_PART_ALL && mp.aggr == IGN_AGGR_SUM &&
+                   (!saving || p->any_cell_options);
   SrcBases xb = mb.sum_seg ? s.src : SrcBases{};   // windowed: every x from the xsum table (slot 0);
   xb.base[mb.sum_seg ? 1 : 0] = mb.d_xsum;          // segmented: the mixed CSR's slot 1
   SumGruArgs a{s.hin, s.hout, pre ? xb : s.src, pre ? mb.d_order : mb.d_order + first,
@@ -253,7 +264,9 @@ int mp_forward(ign_plan* p, ign_batch* b, int mi, int part, MpStates s, const Mp
     SumWinArgs wa{s.src.base[0], mb.d_win_wg, mb.d_win_dst, mb.d_win_ptr, mb.d_win_src, mb.d_xsum, mb.n_win_wg};
     HIP_TRY(launch_sum_win(wa, mp.din, st));
   }
-  HIP_TRY(launch_sum_gru(a, mp.din, cp.H, sv, st));
+  // a cell with options has no split pieces (Wbf / Ubf unset above, no projection target): sum_gru_cell
+  if (cp.is_default()) HIP_TRY(launch_sum_gru(a, mp.din, cp.H, sv, st));
+  else HIP_TRY(launch_sum_gru_cell(a, mp.din, cp.H, cell_opt(cp), st));
   tm.end();
   if (target >= 0) b->proj_ready[target] |= (char)(1 << tslot);
   return IGN_OK;

@@ -3,8 +3,12 @@
 // (train.cpp).  What depends on the mode hangs on the save record.
 #pragma once
 #include "engine_internal.h"
+#include "gru_cell.h"
 
 namespace ign {
+
+// the options of a cell as gru_cell.hip's kernels take them
+inline CellOpt cell_opt(const CellP& cp) { return CellOpt{cp.act, cp.ract, cp.reset_after ? 1 : 0}; }
 
 // Event pairs around the launches of one kind into the plan's ring (ign_plan_set_timing), resolved
 // lazily by flush_timing; a null plan never records (the training forward and the backward).

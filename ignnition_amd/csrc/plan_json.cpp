@@ -226,6 +226,7 @@ struct Lowered {
   };
   std::vector<MP> mps;
   std::vector<std::pair<std::string, std::pair<int, int>>> cells;   // dst name, (din, H)
+  std::vector<ign_cell_options> cell_opts;                          // per cell (ign_plan_set_cell_options)
   int conv_dim = 0, attn_dim = 0;
   struct RoOp {
     int type, mode = 0, adj = -1, counter = 0, in_width = 0;
@@ -243,11 +244,14 @@ struct Lowered {
 
   std::vector<std::pair<std::string, std::vector<int64_t>>> param_specs() const {
     std::vector<std::pair<std::string, std::vector<int64_t>>> s;
-    for (auto& c : cells) {
+    for (size_t k = 0; k < cells.size(); ++k) {
+      const auto& c = cells[k];
       const int din = c.second.first, h = c.second.second;
       s.push_back({c.first + "_update/kernel", {din, 3 * h}});
       s.push_back({c.first + "_update/recurrent_kernel", {h, 3 * h}});
-      s.push_back({c.first + "_update/bias", {2, 3 * h}});
+      // Keras' GRUCell: [2][3H]; reset_after false, [3H]; use_bias false, no variable
+      if (cell_opts[k].use_bias && cell_opts[k].reset_after) s.push_back({c.first + "_update/bias", {2, 3 * h}});
+      else if (cell_opts[k].use_bias) s.push_back({c.first + "_update/bias", {3 * h}});
     }
     for (auto& m : mps)
       for (auto& sr : m.srcs) {
@@ -379,17 +383,29 @@ Lowered lower(const JVal& data, const JVal& dims) {
       const JVal* arch = nets.count(un) ? nets[un] : nullptr;
       if (!arch) invalid("update nn_name '" + un + "' is not defined");
       // JO:287-291: the network's keys other than nn_name / nn_type join the update dict
+      // of GRUCell's keys the four of ign_plan_set_cell_options are lowered (absent: the Keras default)
       std::string rtype;
       std::vector<std::string> extra;
+      ign_cell_options copt{IGN_ACT_TANH, IGN_ACT_SIGMOID, 1, 1};
+      const JVal *act_v = nullptr, *ract_v = nullptr;   // (named after the refusal of other keys, as engine.py)
+      auto cell_key = [&](const std::string& k, const JVal& v) {
+        if (k == "units" || k == "name") return;
+        if (k == "activation") act_v = &v;
+        else if (k == "recurrent_activation") ract_v = &v;
+        else if (k == "use_bias") copt.use_bias = truthy(v);
+        else if (k == "reset_after") copt.reset_after = truthy(v);
+        else extra.push_back(k);
+      };
       for (auto& kv : arch->obj) {
         if (kv.first == "nn_name" || kv.first == "nn_type") continue;
         if (kv.first == "recurrent_type") rtype = str(kv.second, "recurrent_type");
-        else if (kv.first != "units" && kv.first != "name") extra.push_back(kv.first);
       }
-      for (auto& kv : upd.obj)
-        if (kv.first != "type" && kv.first != "nn_name" && kv.first != "recurrent_type" && kv.first != "units" &&
-            kv.first != "name")
-          extra.push_back(kv.first);
+      if (rtype == "GRU") {   // (any other type is refused below, before its keys are read)
+        for (auto& kv : arch->obj)
+          if (kv.first != "nn_name" && kv.first != "nn_type" && kv.first != "recurrent_type") cell_key(kv.first, kv.second);
+        for (auto& kv : upd.obj)
+          if (kv.first != "type" && kv.first != "nn_name" && kv.first != "recurrent_type") cell_key(kv.first, kv.second);
+      }
       if (rtype != "GRU")
         unsupported("recurrent_type " + rtype + " is not lowered (only GRU; LSTM passes one state, AUX:764)");
       if (!extra.empty()) {
@@ -398,6 +414,8 @@ Lowered lower(const JVal& data, const JVal& dims) {
         for (size_t i = 0; i < extra.size(); ++i) e += (i ? ", '" : "'") + extra[i] + "'";
         unsupported(e + "] are not lowered (Keras defaults only)");
       }
+      if (act_v) copt.activation = activation(act_v, "GRU activation", ACT_AT_PREDICT);
+      if (ract_v) copt.recurrent_activation = activation(ract_v, "GRU recurrent_activation", ACT_AT_PREDICT);
       const JVal& ag = need(mp, "aggregation", "message passing");
       const std::string aggr = str(need(ag, "type", "aggregation"), "aggregation type");
       static const std::map<std::string, int> AGG = {{"sum", IGN_AGGR_SUM}, {"ordered", IGN_AGGR_ORDERED},
@@ -484,6 +502,7 @@ Lowered lower(const JVal& data, const JVal& dims) {
       if (!cell_of.count(dst)) {
         cell_of[dst] = (int)p.cells.size();
         p.cells.push_back({dst, {din, p.hidden[m.dst]}});
+        p.cell_opts.push_back(copt);   // one cell per destination entity (GM:309-313): its first MP's keys
       }
       m.cell = cell_of[dst];
       if (aggr == "convolution") p.conv_dim = p.hidden[m.dst];   // GM:288-300: the last MP's weights
@@ -648,7 +667,16 @@ std::string describe(const Lowered& p, const PlanModel& m) {
   }
   s += "], \"convolution\": [";
   for (size_t i = 0; i < m.mps.size(); ++i) s += (i ? ", " : "") + std::to_string(m.mps[i].act);
-  return s + "]}}";
+  // the GRU cells as the plan carries them (ign_plan_set_cell_options), in cell order
+  s += "]}, \"cells\": [";
+  for (size_t c = 0; c < m.cells.size(); ++c) {
+    const CellP& cp = m.cells[c];
+    s += (c ? ", " : "") + std::string("{\"name\": ") + quote(p.cells[c].first) + ", \"input_dim\": " +
+         std::to_string(cp.din) + ", \"units\": " + std::to_string(cp.H) + ", \"activation\": " +
+         std::to_string(cp.act) + ", \"recurrent_activation\": " + std::to_string(cp.ract) + ", \"use_bias\": " +
+         (cp.use_bias ? "true" : "false") + ", \"reset_after\": " + (cp.reset_after ? "true" : "false") + "}";
+  }
+  return s + "]}";
 }
 
 }  // namespace
@@ -743,6 +771,7 @@ int ign_plan_create_json(const char* model_json, const char* dims_json, int32_t 
   };
   for (size_t k = 0; k < p.ro_ops.size(); ++k) add_sites((int)k, p.ro_ops[k].extra);
   add_sites(-1, p.extra);
+  for (size_t c = 0; !rc && c < p.cell_opts.size(); ++c) rc = plan_set_cell_options(plan, (int)c, &p.cell_opts[c]);
   if (rc) {
     ign_plan_destroy(plan);
     return rc;

@@ -301,7 +301,8 @@ void layout_params(PlanModel* p) {
     CellP& cp = p->cells[c];
     cp.off_k = put(0, (int)c, cp.din, 3 * cp.H);
     cp.off_rk = put(1, (int)c, cp.H, 3 * cp.H);
-    cp.off_b = put(2, (int)c, 2, 3 * cp.H);
+    // Keras' GRUCell: bias [2][3H]; reset_after false, [3H]; use_bias false, no variable
+    cp.off_b = cp.bias_rows() ? put(2, (int)c, cp.bias_rows(), 3 * cp.H) : -1;
   }
   for (size_t mi = 0; mi < p->mps.size(); ++mi)
     for (size_t s = 0; s < p->mps[mi].nn.size(); ++s)
@@ -340,9 +341,15 @@ void layout_packed(PlanModel* p) {
   // from clean slots: every pk_* offset below is assigned here or stays unset (the layouts run again
   // when ign_plan_add_layernorm changes the stacks)
   p->packs.clear();
+  p->any_cell_options = false;
+  for (const CellP& c : p->cells) p->any_cell_options = p->any_cell_options || !c.is_default();
   for (CellP& c : p->cells) {   // (a fresh struct carries every slot's default)
     CellP z{c.din, c.H, c.off_k, c.off_rk, c.off_b, -1, -1, -1};
     z.used = c.used;
+    z.act = c.act;
+    z.ract = c.ract;
+    z.use_bias = c.use_bias;
+    z.reset_after = c.reset_after;
     c = z;
   }
   auto unpacked = [](DenseP& d) {
@@ -371,9 +378,17 @@ void layout_packed(PlanModel* p) {
     CellP& cp = p->cells[c];
     if (!cp.used) continue;
     const int din = cp.din, H = cp.H;
-    cp.pk_w = slot(AT_CELL, c, 0, PK_GRU, pack_gru_w_floats(din, H), cp.off_k, cp.off_rk, cp.off_b, din, H);
+    // A cell with options (ign_plan_set_cell_options) runs on gru_cell.hip's kernels: pack_gru's unscaled
+    // fragments and its bias form, and none of the split pieces below.  Their absence is what takes
+    // the cell off the fast paths: the resident forward (resident_plan_shape needs pk_uh / pk_wbf /
+    // pk_ubf), the split-bf16 / split-fp16 sequence and sum variants, and sum_gru_g32's fused projection
+    // (its own pieces, and the target cell's pk_wbf).  mp_step.cpp and train.cpp dispatch on is_default().
+    const bool dflt = cp.is_default();
+    const int mode = dflt ? 0 : kPackGruRaw | cp.bias_rows();
+    cp.pk_w = slot(AT_CELL, c, 0, PK_GRU, pack_gru_w_floats(din, H), cp.off_k, cp.off_rk, cp.off_b, din, H, mode);
     cp.pk_u = slot(AT_CELL, c, 1, PK_GRU_U, pack_gru_u_floats(H), -1, cp.off_rk, -1, din, H);
     cp.pk_b = slot(AT_CELL, c, 2, PK_GRU_B, pack_gru_b_floats(H), -1, -1, cp.off_b, din, H);
+    if (!dflt) continue;
     if (pack_u_bf16_floats(H)) cp.pk_ubf = slot(AT_CELL, c, 3, PK_U_BF16, pack_u_bf16_floats(H), cp.off_rk, -1, -1, H);
     if (pack_u_f16_floats(H)) cp.pk_uh = slot(AT_CELL, c, 4, PK_U_F16, pack_u_f16_floats(H), cp.off_rk, -1, -1, H);
     if (din == 64 && H == 64)
@@ -414,7 +429,7 @@ void layout_packed(PlanModel* p) {
     CellP& cp = p->cells[c];
     if (!cp.used || !bwd_shape_supported(cp.H, cp.H)) continue;   // U^T: the recurrent backward
     cp.pk_ut = slot(AT_CELL, c, 8, PK_A, pack_gru_u_floats(cp.H), cp.off_rk, -1, -1, cp.H, 3 * cp.H);
-    if (pack_ut_f16_floats(cp.H))
+    if (pack_ut_f16_floats(cp.H) && cp.is_default())
       cp.pk_uth = slot(AT_CELL, c, 9, PK_UT_F16, pack_ut_f16_floats(cp.H), cp.off_rk, -1, -1, cp.H);
     if (!bwd_shape_supported(cp.din, cp.H)) continue;            // W^T (an axis-2 concat cell goes generic)
     cp.pk_wt = slot(AT_CELL, c, 7, PK_A, pack_gru_w_floats(cp.din, cp.H), cp.off_k, -1, -1, cp.din, 3 * cp.H);
@@ -440,7 +455,8 @@ void layout_packed(PlanModel* p) {
     for (size_t s = 0; s < mp.src.size(); ++s) {
       const int w = p->ents[mp.src[s].entity].hidden_dim;
       mp.pk_slice.push_back(slot(AT_SLICE, mi, (int)s, PK_GRU_W, pack_gru_w_floats(w, cp.H),
-                                 cp.off_k + (int64_t)mp.slice_off[s] * 3 * cp.H, -1, -1, w, cp.H));
+                                 cp.off_k + (int64_t)mp.slice_off[s] * 3 * cp.H, -1, -1, w, cp.H,
+                                 cp.is_default() ? 0 : kPackGruRaw));
     }
   }
   if (p->conv_F)
@@ -544,6 +560,23 @@ int add_layernorm(PlanModel* p, int stack, int before_layer, float epsilon, int 
   if (int rc = add_site(p, SL_LAYERNORM, stack, before_layer, DropSite(), n)) return rc;
   if (stack == -1) p->fused_readout = false;   // the fused 256-256-1 kernel has no place for the layer
   layout_params(p);   // both layouts again
+  layout_packed(p);
+  return IGN_OK;
+}
+
+int set_cell_options(PlanModel* p, int cell, const ign_cell_options* o) {
+  if (!o) return fail(IGN_ERR_INVALID, "ign_plan_set_cell_options: null options");
+  if (cell < 0 || cell >= (int)p->cells.size())
+    return fail(IGN_ERR_INVALID, "ign_plan_set_cell_options: cell %d outside 0..%d", cell, (int)p->cells.size() - 1);
+  for (int a : {o->activation, o->recurrent_activation})
+    if (!act_ok(a, ACT_AT_PREDICT))
+      return fail(IGN_ERR_INVALID, "ign_plan_set_cell_options: activation code %d", a);
+  CellP& cp = p->cells[cell];
+  cp.act = o->activation;
+  cp.ract = o->recurrent_activation;
+  cp.use_bias = o->use_bias != 0;
+  cp.reset_after = o->reset_after != 0;
+  layout_params(p);   // the bias tensor's form, and both layouts after it
   layout_packed(p);
   return IGN_OK;
 }

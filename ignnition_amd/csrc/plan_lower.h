@@ -149,6 +149,7 @@ struct PlanModel : PlanSwitches {
   int n_adj = 0, n_il = 0;
   std::vector<MPP> mps;
   std::vector<CellP> cells;
+  bool any_cell_options = false;  // a cell is not a default cell (layout_packed sets it)
   std::vector<int> ro_in;         // predict inputs: readout tensor ids
   std::vector<DenseP> dense;
   std::vector<StackLayer> seq;    // predict's layers in order (dense: its Dense layers)
@@ -195,6 +196,11 @@ inline int site_order(const PlanModel* p, int stack, int kind, int idx) {
 // (the caller checks).
 int add_dropout(PlanModel* p, int stack, int before_layer, float rate, uint64_t layer_seed);
 int add_layernorm(PlanModel* p, int stack, int before_layer, float epsilon, int center, int scale);
+// ign_plan_set_cell_options on the model: the options enter CellP and both layouts run again (the bias
+// tensor [2][3H], [3H] or absent; a cell with options packs pack_gru's unscaled form and none of the
+// split pieces, which takes it off the resident, split and fused paths).  IGN_ERR_INVALID for a bad
+// cell index or activation code.  Only before the parameters exist on a device (the caller checks).
+int set_cell_options(PlanModel* p, int cell, const ign_cell_options* o);
 
 // d + sw -> *m (a fresh PlanModel); IGN_OK or the refusal's code, its text in ign_last_error
 int lower_plan(const ign_plan_desc* d, const PlanSwitches& sw, PlanModel* m);

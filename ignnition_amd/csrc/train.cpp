@@ -64,6 +64,8 @@ struct TrainState {
   float* gu = nullptr;
   float* dx = nullptr;
   float* dtab = nullptr;
+  float* gu2 = nullptr;       // a reset_after = false cell's backward: gu's second half and r * h_prev
+  float* rh = nullptr;        //   (CellBwdExtra), rows as gu's
   float* rsrc = nullptr;      // convolution plans: an ordered MP's source rows, the unread ones as zeros
   std::vector<float*> dS[2];
   std::vector<float*> act;                // readout activations of layers 0 .. L-2
@@ -509,7 +511,7 @@ int enable_mp(const ign_plan* p, const ign_batch* b, TrainState* t, size_t mi, b
 
 // floats of the scratch buffers the MP instances / readout layers of a backward share: the largest need of each
 struct TrainScratch {
-  int64_t ga = 0, gu = 0, dx = 0, dtab = 0, part = 0, rsrc = 0;
+  int64_t ga = 0, gu = 0, dx = 0, dtab = 0, part = 0, rsrc = 0, gu2 = 0, rh = 0;
   int64_t dmsg = 0, mz = 0, mdin = 0;            // message networks
   int64_t amsg = 0, arows = 0;                   // attention
   int64_t dz = 0, rz = 0, rcat = 0, ties = 0;    // readout
@@ -527,6 +529,10 @@ TrainScratch train_scratch(const ign_plan* p, const ign_batch* b) {
       const int64_t hs_rows = mb.n_steps + mb.n_dst;
       z.ga = std::max(z.ga, (mb.n_steps + 1) * 3 * H);   // + the pad slot row (seq_gru_bwd_kernel)
       z.gu = std::max(z.gu, hs_rows * 3 * H);
+      if (!p->cells[mp.cell].reset_after) {
+        z.gu2 = std::max(z.gu2, hs_rows * 3 * H);
+        z.rh = std::max(z.rh, hs_rows * H);
+      }
       need_part(hs_rows, H, 3 * H);
       if (p->bwd_fuse && seq_bwd_fused_supported(H)) z.part = std::max(z.part, seq_bwd_partial_floats(H));
       for (int s = 0; s < S; ++s) {
@@ -553,6 +559,10 @@ TrainScratch train_scratch(const ign_plan* p, const ign_batch* b) {
       }
       z.ga = std::max(z.ga, mb.n_dst * 3 * H);
       z.gu = std::max(z.gu, mb.n_dst * 3 * H);
+      if (!p->cells[mp.cell].reset_after) {
+        z.gu2 = std::max(z.gu2, mb.n_dst * 3 * H);
+        z.rh = std::max(z.rh, mb.n_dst * H);
+      }
       z.dx = std::max(z.dx, mb.n_dst * DIN);
       need_part(mb.n_dst, std::max(DIN, H), 3 * H);
     }
@@ -608,6 +618,7 @@ int alloc_mp_scratch(const ign_plan* p, TrainState* t, const TrainScratch& z) {
   if ((rc = talloc(t, &t->ga, z.ga)) || (rc = talloc(t, &t->gu, z.gu)) || (rc = talloc(t, &t->dx, z.dx)) ||
       (rc = talloc(t, &t->dtab, z.dtab)))
     return rc;
+  if (z.gu2 && ((rc = talloc(t, &t->gu2, z.gu2)) || (rc = talloc(t, &t->rh, z.rh)))) return rc;
   if (z.rsrc && (rc = talloc(t, &t->rsrc, z.rsrc))) return rc;
   if (z.amsg && ((rc = talloc(t, &t->adw, z.amsg)) || (rc = talloc(t, &t->adv, z.amsg)) ||
                  (rc = talloc(t, &t->ads_src, z.arows)) || (rc = talloc(t, &t->ads_dst, z.arows)) ||
@@ -692,7 +703,7 @@ int alloc_deferred(const ign_plan* p, const ign_batch* b, TrainState* t) {
     const int H = cp.H, H3 = 3 * cp.H, DIN = mp.din;
     if (mp.sorted) {
       for (size_t s2 = 0; s2 < mp.src.size(); ++s2) add(cp.off_k, -1, DIN, H3, t->mp[mi].trows[s2]);
-    } else if (mp.aggr == IGN_AGGR_SUM) {
+    } else if (mp.aggr == IGN_AGGR_SUM && cp.is_default()) {   // (a cell with options reduces per instance)
       const int64_t fw = sum_bwd_fused_waves(mb.n_dst, DIN, H);   // the fused sum backward's partials
       add(cp.off_k, cp.off_b, DIN, H3, mb.n_dst, fw);
       add(cp.off_rk, cp.off_b + H3, H, H3, mb.n_dst, fw);
@@ -701,7 +712,7 @@ int alloc_deferred(const ign_plan* p, const ign_batch* b, TrainState* t) {
   for (size_t mi = 0; mi < p->mps.size(); ++mi) {   // the fused ordered backward's partials
     const MPP& mp = p->mps[mi];
     const CellP& cp = p->cells[mp.cell];
-    if (!mp.sorted || !p->bwd_fuse || !seq_bwd_fused_supported(cp.H)) continue;
+    if (!mp.sorted || !p->bwd_fuse || !seq_bwd_fused_supported(cp.H) || !cp.is_default()) continue;
     const int64_t tiles = (b->mp[mi].n_dst + 15) / 16;
     const int64_t waves = std::min<int64_t>((tiles + 3) / 4 * 4, kBwdPartialWaves) * p->T;   // upper bound
     bool found = false;
@@ -982,6 +993,16 @@ int ign_backward_mp(ign_plan* p, ign_batch* b) {
     float* gk = grads + cp.off_k;
     float* grk = grads + cp.off_rk;
     float* gb = grads + cp.off_b;
+    // A cell with options (gru_cell.hip): the bias gradients in the [3H] layout or nowhere, and for
+    // reset_after = false the second pair of rows whose contraction completes dU
+    const bool dflt = cp.is_default();
+    float* gb_in = cp.use_bias ? gb : nullptr;
+    float* gb_rec = cp.use_bias && cp.reset_after ? gb + H3 : nullptr;
+    CellBwdExtra cx{};
+    if (!cp.reset_after) {
+      cx.gu2 = t->gu2;
+      cx.rh = t->rh;
+    }
     if (mp.sorted) {
       // the forward's table of this instance: saved by the resident training forward, else recomputed
       const bool saved = t->tab_saved && rec.mi == 0 && rec.it < (int)t->tsave.size();
@@ -991,7 +1012,13 @@ int ign_backward_mp(ign_plan* p, ign_batch* b) {
                    t->ga, t->gu, mb.n_dst};
       a.h_in = t->ver[dst][rec.v_in];
       a.hdr = mt.hdrb;
-      if (p->bwd_fuse && seq_bwd_fused_supported(H)) {
+      if (!dflt) {
+        HIP_TRY(launch_seq_gru_cell_bwd(a, H, cell_opt(cp), cx, st));
+        HIP_TRY(launch_tsgemm_add(mt.hs[rec.it], H, t->gu, H3, mt.hs_rows, H, H3, t->part, grk, gb_rec, st));
+        if (!cp.reset_after)   // dU_h = (r h)^T dc
+          HIP_TRY(launch_tsgemm_add(t->rh, H, t->gu2, H3, mt.hs_rows, H, H3, t->part, grk, nullptr, st));
+        if (gb_in) HIP_TRY(launch_colsum_add(t->ga, H3, mb.n_steps, H3, t->part, gb_in, st));
+      } else if (p->bwd_fuse && seq_bwd_fused_supported(H)) {
         // dU and both bias gradients (column sums of da and du) inside the kernel
         a.gu = nullptr;
         a.part = t->part;
@@ -1062,7 +1089,13 @@ int ign_backward_mp(ign_plan* p, ign_batch* b) {
         if (fw && d.off_c == cp.off_k && d.off_cb == cp.off_b && d.M == DIN && d.N == H3 && d.used + fw <= d.cap) dw = &d;
         if (fw && d.off_c == cp.off_rk && d.off_cb == cp.off_b + H3 && d.M == H && d.N == H3 && d.used + fw <= d.cap) du = &d;
       }
-      if (dw && du) {
+      if (!dflt) {
+        HIP_TRY(launch_sum_gru_cell_bwd(a, DIN, H, cell_opt(cp), cx, st));
+        if ((rc = tsgemm_deferred(t, mt.xs[rec.it], DIN, t->ga, H3, mb.n_dst, DIN, H3, gk, gb_in, st)) ||
+            (rc = tsgemm_deferred(t, hin, H, t->gu, H3, mb.n_dst, H, H3, grk, gb_rec, st)) ||
+            (!cp.reset_after && (rc = tsgemm_deferred(t, t->rh, H, t->gu2, H3, mb.n_dst, H, H3, grk, nullptr, st))))
+          return rc;
+      } else if (dw && du) {
         HIP_TRY(launch_sum_gru_bwd_fused(a, DIN, H, dw->part + dw->used * (int64_t)(DIN + 1) * H3,
                                          du->part + du->used * (int64_t)(H + 1) * H3, st));
         dw->used += fw;

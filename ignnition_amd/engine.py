@@ -25,6 +25,24 @@ from . import _lib
 from ._lib import check, lib
 
 SUPPORTED_GRU_KEYS = {"units", "name"}
+# the GRUCell keys lowered beside them (ign_plan_set_cell_options), with the Keras GRUCell v2 defaults
+GRU_OPTION_DEFAULTS = {"activation": "tanh", "recurrent_activation": "sigmoid", "use_bias": True, "reset_after": True}
+
+
+def _gru_options(parameters):
+    """(activation code, recurrent_activation code, use_bias, reset_after) of a GRU cell's parameters."""
+    extra = set(parameters) - SUPPORTED_GRU_KEYS - set(GRU_OPTION_DEFAULTS)
+    if extra:
+        raise UnsupportedModel("GRU options %s are not lowered (Keras defaults only)" % sorted(extra))
+    prm = dict(GRU_OPTION_DEFAULTS, **{k: v for k, v in parameters.items() if k in GRU_OPTION_DEFAULTS})
+    codes = []
+    for key in ("activation", "recurrent_activation"):
+        if prm[key] is not None and not isinstance(prm[key], str):   # (a list or dict: plan_json.cpp's text)
+            raise ValueError("GRU %s: expected a string" % key)
+        if prm[key] not in _lib.ACT:
+            raise UnsupportedModel("activation %r not supported" % prm[key])
+        codes.append(_lib.ACT[prm[key]])
+    return codes[0], codes[1], bool(prm["use_bias"]), bool(prm["reset_after"])
 
 # Live handles, released explicitly at interpreter exit (batches before plans) while the HIP
 # runtime is still up; relying on __del__ during module teardown can run after it is gone.
@@ -103,6 +121,7 @@ class MPPlan:
     il_slots: list = field(default_factory=list)       # indices_<src>_to_<dst> keys
     mps: list = field(default_factory=list)            # dicts
     cells: list = field(default_factory=list)          # [(dst_name, din, H)]
+    cell_options: list = field(default_factory=list)   # per cell: (activation, recurrent_activation, use_bias, reset_after)
     readout_inputs: list = field(default_factory=list)  # predict inputs: readout tensor ids
     readout_ops: list = field(default_factory=list)     # operations before predict (dicts)
     ro_widths: list = field(default_factory=list)       # readout tensor widths (entity states first)
@@ -140,9 +159,7 @@ class MPPlan:
                 if cell.type != "GRU":
                     raise UnsupportedModel("recurrent_type %s is not lowered (only GRU; LSTM passes one state, "
                                            "AUX:764)" % cell.type)
-                extra = set(cell.parameters) - SUPPORTED_GRU_KEYS
-                if extra:
-                    raise UnsupportedModel("GRU options %s are not lowered (Keras defaults only)" % sorted(extra))
+                options = _gru_options(cell.parameters)
                 aggr = mp.aggregation.type
                 if aggr not in ("sum", "ordered", "interleave", "concat", "attention", "convolution"):
                     raise UnsupportedModel("aggregation %r is not lowered yet" % aggr)
@@ -175,6 +192,7 @@ class MPPlan:
                 if dst not in cell_of:
                     cell_of[dst] = len(p.cells)
                     p.cells.append((dst, din, p.hidden[eidx[dst]]))
+                    p.cell_options.append(options)   # one cell per destination entity: its first MP's keys
                 p.mps.append({"dst": eidx[dst], "aggr": aggr, "axis": getattr(mp.aggregation, "concat_axis", 0),
                               "cell": cell_of[dst], "sources": srcs, "stage": stage_name, "act": act,
                               "nets": nets})
@@ -348,6 +366,7 @@ class MPPlan:
         h = C.c_void_p()
         check(lib.ign_plan_create(C.byref(desc), 0, C.byref(h)))
         try:
+            self.set_cell_options(h)
             dead = C.c_int32()
             out = []
             for mi in range(len(self.mps)):
@@ -356,6 +375,14 @@ class MPPlan:
             return out
         finally:
             lib.ign_plan_destroy(h)
+
+    def set_cell_options(self, handle):
+        """The cells' options on a plan just created from ``to_desc`` (ign_plan_set_cell_options; ign_cell_desc
+        has no room for them).  A cell of Keras defaults needs no call."""
+        for c, opt in enumerate(self.cell_options):
+            if opt != _gru_options({}):
+                o = _lib.CellOptions(*[int(v) for v in opt])
+                check(lib.ign_plan_set_cell_options(handle, c, C.byref(o)))
 
     # ------------------------------------------------------------------ C structures
     def to_desc(self):
@@ -399,9 +426,10 @@ class MPPlan:
     def param_specs(self):
         """[(name, shape)] in the engine's tensor order (ign_plan_param_tensor)."""
         specs = []
-        for dst, din, h in self.cells:
-            specs += [(dst + "_update/kernel", (din, 3 * h)), (dst + "_update/recurrent_kernel", (h, 3 * h)),
-                      (dst + "_update/bias", (2, 3 * h))]
+        for (dst, din, h), (_, _, use_bias, reset_after) in zip(self.cells, self.cell_options):
+            specs += [(dst + "_update/kernel", (din, 3 * h)), (dst + "_update/recurrent_kernel", (h, 3 * h))]
+            if use_bias:   # Keras' GRUCell: [2][3H]; reset_after false, [3H]; use_bias false, no variable
+                specs.append((dst + "_update/bias", (2, 3 * h) if reset_after else (3 * h,)))
         for m in self.mps:
             for net in m.get("nets", []):
                 if not net:
@@ -473,6 +501,7 @@ class Engine:
         h = C.c_void_p()
         check(lib.ign_plan_create(C.byref(desc), device, C.byref(h)))
         self.handle = h
+        plan.set_cell_options(h)
         for kind, *args in plan.stack_sites():   # ign_dense_desc has no room for them
             check((lib.ign_plan_add_dropout if kind == "dropout" else lib.ign_plan_add_layernorm)(h, *args))
         self.params_version = 0   # bumped by every parameter update (SplitBatch re-syncs its replicas)

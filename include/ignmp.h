@@ -413,6 +413,29 @@ int  ign_plan_add_dropout(ign_plan* plan, int32_t stack, int32_t before_layer, f
  * message-creation network the layer is IGN_ERR_UNSUPPORTED. */
 int  ign_plan_add_layernorm(ign_plan* plan, int32_t stack, int32_t before_layer, float epsilon, int32_t center,
                             int32_t scale);
+/* ---- GRU cell options (ABI 13 addition) ----------------------------------------------------------
+ * The keys of tf.keras.layers.GRUCell the engine lowers beside units: ign_cell_desc has no room for
+ * them, so they are set after ign_plan_create, before the plan's parameters are set or its first
+ * batch is created (else IGN_ERR_INVALID: parameter and training buffers are sized from them).
+ *   activation            the candidate's IGN_ACT_* code (Keras default: tanh)
+ *   recurrent_activation  the gates' IGN_ACT_* code (Keras default: sigmoid)
+ *   use_bias              0: the cell owns no bias tensor (kind 2) and its arithmetic has zeros there
+ *   reset_after           != 0: c = act(x.W_h + b_ih + r * (h.U_h + b_hh)), the Keras default.  0: the
+ *                         "v1" cell c = act(x.W_h + b_h + (r * h).U_h), whose bias tensor is [3H]
+ *                         instead of [2][3H]
+ * A bad cell index or activation code is IGN_ERR_INVALID.  The call lays the parameters out again
+ * (read ign_plan_param_tensor after the last one).  A cell whose four values are the Keras defaults
+ * is a default cell and runs on the kernels it ran on without the call; any other cell runs on the
+ * generalised f32-MFMA kernels (seq_gru_cell, sum_gru_cell and their backward forms): no resident
+ * forward, no split-bf16 / split-fp16 variant, no fused weight gradients, no fused projection.
+ * ign_plan_create_json sets the options of its description itself. */
+typedef struct {
+  int32_t activation;
+  int32_t recurrent_activation;
+  int32_t use_bias;
+  int32_t reset_after;
+} ign_cell_options;
+int  ign_plan_set_cell_options(ign_plan* plan, int32_t cell, const ign_cell_options* options);
 /* The mask stream of the batch's next ign_forward_train (and the backward that follows it): site s
  * draws the mask ign_dropout_keep(seed ^ layer_seed(s), s, step, rows, units, rate(s)).  A batch
  * on which this was never called uses (0, 0): the same mask every step.  A trainer passes its seed
