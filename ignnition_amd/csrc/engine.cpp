@@ -77,6 +77,18 @@ int check_pb(ign_plan* p, ign_batch* b, bool train) {
   return set_device(p->device);
 }
 
+// what ign_batch_set_features and ign_batch_feature_gradients refuse alike
+int check_feature_entity(const ign_plan* p, const ign_batch* b, int32_t e, const void* ptr) {
+  if (!ptr) return fail(IGN_ERR_INVALID, "null argument");
+  if (e < 0 || e >= (int)p->ents.size()) return fail(IGN_ERR_INVALID, "entity %d out of range", e);
+  if (p->ents[e].feature_total <= 0 || !b->d_feat[e]) return fail(IGN_ERR_INVALID, "entity %d has no features", e);
+  for (int64_t h : b->halo)
+    if (h)
+      return fail(IGN_ERR_UNSUPPORTED, "a batch with halo rows (an edge-cut partition): a halo row's features and "
+                  "their gradient belong to the partition that owns the row");
+  return IGN_OK;
+}
+
 int ensure_device(ign_plan* p) {
   int rc = set_device(p->device);
   if (rc) return rc;
@@ -1176,6 +1188,25 @@ int ign_batch_read_predictions(ign_plan* p, ign_batch* b, float* host_out) {
   if (rc) return rc;
   if (!host_out) return fail(IGN_ERR_INVALID, "null argument");
   return copy_out(p, b, host_out);
+}
+
+int ign_batch_set_features(ign_plan* p, ign_batch* b, int32_t e, const float* rows) {
+  int rc = check_pb(p, b);
+  if (rc || (rc = check_feature_entity(p, b, e, rows))) return rc;
+  if (b->train && train_step_open(b->train))
+    return fail(IGN_ERR_INVALID, "ign_batch_set_features between a training forward and the end of its backward "
+                "(the saved states belong to the old values)");
+  // Nothing else of the batch is derived from feature values: every forward builds h0 from this buffer
+  // (launch_init_state, the resident forward's path_feat / src_feat), the captured graph included, which
+  // holds the pointer.  One copy in the plan's stream order; a device source is not waited for
+  const size_t bytes = (size_t)b->rows[e] * p->ents[e].feature_total * sizeof(float);
+  hipPointerAttribute_t at{};
+  const bool dev = hipPointerGetAttributes(&at, rows) == hipSuccess &&
+                   (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged);
+  if (!dev) (void)hipGetLastError();   // (an unregistered host pointer is an error to the query)
+  HIP_TRY(hipMemcpyAsync(b->d_feat[e], rows, bytes, hipMemcpyDefault, p->stream));
+  if (!dev) HIP_TRY(hipStreamSynchronize(p->stream));   // the caller's host rows may die after the call
+  return IGN_OK;
 }
 
 int ign_batch_mp_split(const ign_batch* b, int32_t mi, int64_t* interior, int64_t* boundary) {

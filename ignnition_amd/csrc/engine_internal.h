@@ -23,6 +23,8 @@
 
 struct TrainState;                 // train.cpp
 void train_state_destroy(TrainState* t);
+// between ign_forward_train_begin and the end of that forward's backward (train.cpp)
+bool train_step_open(const TrainState* t);
 
 namespace ign {
 
@@ -263,6 +265,8 @@ int dev_alloc(ign_batch* b, float** out, int64_t n);
 int repack(ign_plan* p);                      // runs p->packs: fragments from d_params (set_params, optimizer)
 // what every forward / backward entry point checks first; train: the batch has its training state too
 int check_pb(ign_plan* p, ign_batch* b, bool train = false);
+// ign_batch_set_features / ign_batch_feature_gradients: ptr, the entity, its features, no halo rows
+int check_feature_entity(const ign_plan* p, const ign_batch* b, int32_t e, const void* ptr);
 // readout.cpp: the readout program (operations before predict, GM:611-655) and predict's head
 int readout_batch(ign_plan* p, ign_batch* b, const ign_batch_desc* d);
 // ent: entity-state tensors to read (training keeps every version); null = the batch's current states

@@ -98,6 +98,7 @@ struct TrainState {
   std::vector<float*> nbuf, nstats;
   NormRun norm;
   bool forward_done = false;
+  bool backward_done = false;   // ign_backward_end ran for the last forward: dS holds dLoss/d(initial states)
   // stepped forward / backward (ign_forward_train_begin .. _end, ign_backward_begin .. _end): the
   // edge-cut driver exchanges halo rows between the steps
   int f_it = 0, f_mi = 0;
@@ -129,6 +130,8 @@ struct TrainState {
   DevPool* pool = nullptr;                 // the batch's (outlives this state)
   hipStream_t stream = nullptr;            // the plan stream, for the release fence
 };
+
+bool train_step_open(const TrainState* t) { return t->f_open || t->forward_done || t->b_open; }
 
 void train_state_destroy(TrainState* t) {
   if (!t) return;
@@ -781,6 +784,8 @@ int ign_forward_train_begin(ign_plan* p, ign_batch* b) {
   t->f_it = t->f_mi = 0;
   t->f_open = true;
   t->forward_done = false;
+  t->b_open = false;   // (a backward left unfinished is abandoned with its forward)
+  t->backward_done = false;
   return IGN_OK;
 }
 
@@ -936,6 +941,7 @@ int ign_backward_begin(ign_plan* p, ign_batch* b, const float* dpred, float* gra
   // the readout backward below may write gradient rows over the saved activations (fuse_outer_bwd):
   // a second backward of the same forward would read them as activations
   t->forward_done = false;
+  t->backward_done = false;
   hipStream_t st = p->stream;
   const int E = (int)p->ents.size();
   set_tsgemm_bf(p->tsgemm_bf);
@@ -1172,6 +1178,24 @@ int ign_backward_end(ign_plan* p, ign_batch* b) {
     for (auto& nn : mp.nn)
       for (auto& d : nn.layers)
         if ((rc = add_l2_grad(p, d, grads, t->l2_scale, st))) return rc;
+  t->backward_done = true;
+  return IGN_OK;
+}
+
+// dLoss/d(feature values) of entity e after a completed backward.  Every MP instance of the backward
+// turns the gradient of its destination's output version into that of its input version (dh_out, all
+// H columns, whether or not a parameter gradient needs it) and adds its message gradients to its
+// sources' buffers, down to iteration 0: at ign_backward_end the entity's current gradient buffer
+// is dLoss/dh0, and h0 = [features | zeros] (launch_init_state), so its first F columns are the answer
+int ign_batch_feature_gradients(ign_plan* p, ign_batch* b, int32_t e, float* dev_out) {
+  int rc = check_train(p, b);
+  if (rc || (rc = check_feature_entity(p, b, e, dev_out))) return rc;
+  const TrainState* t = b->train;
+  if (!t->backward_done)
+    return fail(IGN_ERR_INVALID, "ign_batch_feature_gradients needs a completed backward of this batch (ign_backward "
+                "or ign_backward_end after its ign_forward_train)");
+  HIP_TRY(launch_slice_cols(t->dS[t->dcur[e]][e], b->rows[e], p->ents[e].hidden_dim, p->ents[e].feature_total, dev_out,
+                            p->stream));
   return IGN_OK;
 }
 

@@ -916,6 +916,20 @@ __global__ void split_cols_add_kernel(float* __restrict__ dst, int64_t n, int wi
   }
 }
 
+// out[r][:width] = in[r][:width], in's rows stride floats apart; V = 4: width, stride % 4 == 0, aligned
+template <int V>
+__global__ void slice_cols_kernel(const float* __restrict__ in, int64_t n, int stride, int width,
+                                  float* __restrict__ out) {
+  const int wv = width / V;
+  const int64_t total = n * wv;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i / wv;
+    const int c = (int)(i - r * wv) * V;
+    if (V == 4) st4(out + r * width + c, ld4(in + r * stride + c));
+    else out[r * width + c] = in[r * stride + c];
+  }
+}
+
 __global__ void act_bwd_kernel(const float* __restrict__ da, const float* __restrict__ a, int64_t n, int act,
                                float* __restrict__ dz) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
@@ -1604,6 +1618,17 @@ hipError_t launch_split_cols_add(float* dst, int64_t n, int width, const float* 
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(split_cols_add_kernel, dim3(blocks_for(n * width)), dim3(256), 0, st, dst, n, width, src,
                      src_stride, col0);
+  return hipGetLastError();
+}
+
+hipError_t launch_slice_cols(const float* in, int64_t n, int stride, int width, float* out, hipStream_t st) {
+  if (width <= 0 || width > stride) return hipErrorInvalidValue;
+  if (n == 0) return hipSuccess;
+  const bool v4 = width % 4 == 0 && stride % 4 == 0 && ((uintptr_t)in | (uintptr_t)out) % 16 == 0;
+  if (v4)
+    hipLaunchKernelGGL(slice_cols_kernel<4>, dim3(blocks_for(n * (width / 4))), dim3(256), 0, st, in, n, stride, width, out);
+  else
+    hipLaunchKernelGGL(slice_cols_kernel<1>, dim3(blocks_for(n * width)), dim3(256), 0, st, in, n, stride, width, out);
   return hipGetLastError();
 }
 

@@ -745,6 +745,53 @@ def batch_desc(p: "MPPlan", graphs, halo_rows: dict = None):
     return desc, keep, (G, E, num, cnt, halo)
 
 
+def feature_rows(features, rows: int, values) -> np.ndarray:
+    """The ``[rows, F]`` float32 array ``Batch.set_features`` hands to the engine, without a GPU.
+    ``features``: the entity's ``[(name, size)]`` of ``MPPlan.features`` (F = the sum of the sizes);
+    ``values``: a ``{feature name: array}`` dict, each array holding ``rows * size`` values (``[rows]``
+    for size 1, ``[rows, size]`` or flat), laid side by side in the plan's column order; or one array
+    of ``rows * F`` values, ``[rows, F]`` or flat.  A missing or unknown name, or an array of another
+    size, is a ``ValueError``."""
+    F = sum(size for _, size in features)
+    if F == 0:
+        raise ValueError("the entity has no features")
+    if isinstance(values, dict):
+        names = [name for name, _ in features]
+        missing = [n for n in names if n not in values]
+        unknown = sorted(set(values) - set(names))
+        if missing or unknown:
+            raise ValueError("set_features: missing feature(s) %s, unknown feature(s) %s (the entity has %s)"
+                             % (missing, unknown, names))
+        cols = []
+        for name, size in features:
+            v = np.asarray(values[name], np.float32)
+            if v.size != rows * size or (v.ndim == 2 and v.shape != (rows, size)) or v.ndim > 2:
+                raise ValueError("set_features: feature %s has shape %s, the batch needs %d rows of width %d"
+                                 % (name, tuple(v.shape), rows, size))
+            cols.append(v.reshape(rows, size))
+        return np.ascontiguousarray(np.concatenate(cols, 1))
+    v = np.asarray(values, np.float32)
+    if v.size != rows * F or (v.ndim == 2 and v.shape != (rows, F)) or v.ndim > 2:
+        raise ValueError("set_features: values have shape %s, the batch needs %d rows of width %d"
+                         % (tuple(v.shape), rows, F))
+    return np.ascontiguousarray(v.reshape(rows, F))
+
+
+def _is_device_tensor(x) -> bool:
+    return hasattr(x, "data_ptr") and getattr(x, "is_cuda", False)
+
+
+def _device_rows(x, rows: int, F: int, what: str):
+    """A CUDA tensor as [rows, F] contiguous float32 rows, or ValueError."""
+    import torch
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError("%s: a contiguous float32 CUDA tensor is needed" % what)
+    if x.numel() != rows * F or (x.dim() == 2 and tuple(x.shape) != (rows, F)) or x.dim() > 2:
+        raise ValueError("%s: tensor has shape %s, the batch needs %d rows of width %d"
+                         % (what, tuple(x.shape), rows, F))
+    return x
+
+
 class Batch:
     """A disjoint-union batch of graphs on the device (``ign_batch``).
 
@@ -810,6 +857,56 @@ class Batch:
         check(lib.ign_batch_bind_state(self.engine.handle, self.handle, e, C.c_void_p(buf0.data_ptr()),
                                        C.c_void_p(buf1.data_ptr()), cap))
         self._bound[entity] = (buf0, buf1)
+
+    # ---- what-if analysis: new feature values on the same graphs, and their gradient -----------
+    def _feature_entity(self, entity: str):
+        p = self.engine.plan
+        if entity not in p.entities:
+            raise ValueError("no entity %r (the model has %s)" % (entity, p.entities))
+        e = p.entities.index(entity)
+        return e, self.rows[e], sum(size for _, size in p.features[e])
+
+    def set_features(self, entity: str, values):
+        """Replace the entity's feature values in place (ign_batch_set_features): from the next forward
+        on, the batch computes what a fresh batch built with these values computes, bit for bit.
+        ``values``: a ``{feature name: array}`` dict or one ``[rows, F]`` array (``feature_rows``),
+        normalised as the values the batch was built from; or a contiguous float32 CUDA tensor of
+        ``[rows, F]``, read by its pointer in the engine's stream order with no host copy (make the
+        engine's stream wait for whatever wrote it).  Refused between a training forward and the end
+        of its backward, and on an edge-cut partition."""
+        e, rows, F = self._feature_entity(entity)
+        if F == 0:   # the engine's refusal and its text
+            values = np.zeros(1, np.float32)
+            check(lib.ign_batch_set_features(self.engine.handle, self.handle, e, values.ctypes.data_as(C.c_void_p)))
+        if _is_device_tensor(values):
+            src = _device_rows(values, rows, F, "set_features")
+        else:
+            src = feature_rows(self.engine.plan.features[e], rows, values)   # (the engine waits for a host copy)
+        ptr = C.c_void_p(src.data_ptr()) if _is_device_tensor(values) else src.ctypes.data_as(C.c_void_p)
+        check(lib.ign_batch_set_features(self.engine.handle, self.handle, e, ptr))
+
+    def feature_gradients(self, entity: str, out=None):
+        """dLoss/d(feature values) of the entity after a completed backward (ign_batch_feature_gradients),
+        for the loss whose ``dpred`` that backward was given: ``{feature name: ndarray [rows, size]}``.
+        With ``out`` a contiguous float32 CUDA tensor ``[rows, F]`` it is filled in the engine's stream
+        order, with no host copy or wait, and returned."""
+        import torch
+        e, rows, F = self._feature_entity(entity)
+        if out is not None:
+            if not _is_device_tensor(out):
+                raise ValueError("feature_gradients: out must be a CUDA tensor")
+            _device_rows(out, rows, F, "feature_gradients")
+            check(lib.ign_batch_feature_gradients(self.engine.handle, self.handle, e, C.c_void_p(out.data_ptr())))
+            return out
+        buf = torch.empty((rows, max(F, 1)), dtype=torch.float32, device="cuda:%d" % self.engine.device)
+        check(lib.ign_batch_feature_gradients(self.engine.handle, self.handle, e, C.c_void_p(buf.data_ptr())))
+        self.engine.synchronize()
+        g = buf.cpu().numpy()
+        res, col = {}, 0
+        for name, size in self.engine.plan.features[e]:
+            res[name] = g[:, col:col + size].copy()
+            col += size
+        return res
 
     # ---- training -------------------------------------------------------------------------
     def enable_training(self):
@@ -953,6 +1050,24 @@ class SplitBatch:
                                                  out[row:row + b.predictions].ctypes.data_as(C.c_void_p)))
             row += b.predictions
         return out
+
+    def set_features(self, entity: str, values):
+        """``Batch.set_features`` on every sub-batch with its graphs' rows of ``values`` (the rows of the
+        whole batch, in graph order; a dict, an array or a CUDA tensor as there).  Inference only."""
+        p = self.engine.plan
+        if entity not in p.entities:
+            raise ValueError("no entity %r (the model has %s)" % (entity, p.entities))
+        e = p.entities.index(entity)
+        rows = sum(b.rows[e] for b in self.parts)
+        F = sum(size for _, size in p.features[e])
+        if _is_device_tensor(values):
+            whole = _device_rows(values, rows, F, "set_features").reshape(rows, F)
+        else:
+            whole = feature_rows(p.features[e], rows, values)
+        row = 0
+        for b in self.parts:
+            b.set_features(entity, whole[row:row + b.rows[e]])
+            row += b.rows[e]
 
     def synchronize(self):
         for e in self.engines:

@@ -243,6 +243,36 @@ class ComnetModel:
         """Flattened predictions of every graph, concatenated in batch order (GM:716-724)."""
         return self.batch(graphs).forward().reshape(-1)
 
+    def sensitivities(self, graphs, dpred=None):
+        """``(predictions, {entity: {feature: gradient}})`` of a batch of graphs: the batch is built,
+        its training forward and one backward run, and the gradient of ``sum(dpred * predictions)`` with
+        respect to every input feature is read back (``Batch.feature_gradients``).  ``dpred``:
+        ``[predictions * units]`` values, default ones, i.e. the gradient of the sum of the predictions.
+        The gradients are with respect to the normalised feature values the engine is fed (the values
+        in ``graphs``), not the raw ones in front of a normalisation function; each is ``[rows, size]``
+        in batch row order.  Entities without features are left out.  The model's Dropout layers draw
+        the (0, 0) mask stream of a training forward."""
+        import torch
+        b = self.batch(graphs)
+        try:
+            b.enable_training()
+            pred = b.forward_train()
+            dev = "cuda:%d" % self.engine.device
+            if dpred is None:
+                d = torch.ones(pred.size, dtype=torch.float32, device=dev)
+            else:
+                d = np.ascontiguousarray(np.asarray(dpred, np.float32).reshape(-1))
+                if d.size != pred.size:
+                    raise ValueError("sensitivities: dpred has %d values, the batch has %d predictions" % (d.size, pred.size))
+                d = torch.from_numpy(d).to(dev)
+            grads = torch.zeros(self.engine.n_params, dtype=torch.float32, device=dev)
+            torch.cuda.synchronize(dev)   # torch filled them on its own stream, the engine reads on the plan's
+            b.backward(d, grads)
+            out = {name: b.feature_gradients(name) for name, f in zip(self.plan.entities, self.plan.features) if f}
+        finally:
+            b.close()
+        return pred, out
+
     def __call__(self, input: dict, training: bool = False) -> np.ndarray:
         """``ComnetModel.call`` (GM:384) for one graph: [P, units] predictions."""
         return self.batch([input]).forward()

@@ -449,6 +449,29 @@ int  ign_batch_set_dropout(ign_batch* batch, uint64_t seed, uint32_t step);
  * the masks of a partitioned graph are not those of the whole one. */
 int  ign_dropout_keep(uint64_t seed, int32_t site, uint32_t step, int64_t rows, int64_t units, float rate,
                       uint8_t* out);
+/* ---- Feature values of a live batch and their gradient (ABI 13 additions) ------------------------
+ * What-if analysis on fixed graphs: the batch's tables stay, its feature values change.
+ * ign_batch_set_features replaces the feature rows of one entity: rows is [rows of the entity][F],
+ * F the entity's feature_total with the columns in the plan's feature order, the values
+ * ign_batch_create would have been given (after the caller's normalisation).  rows may be host or
+ * device memory: one copy in the plan's stream order; a device source is not waited for on the host,
+ * a host source may be reused when the call returns.  From the next forward on (ign_forward with its
+ * captured graph, the graph-resident forward, the per-MP launches, ign_forward_train and its stepped
+ * form) the batch computes what a fresh batch created with these values computes, bit for bit:
+ * nothing but the feature buffer depends on feature values.
+ * IGN_ERR_INVALID: a null pointer, an entity out of range or without features, and a call between
+ * ign_forward_train(_begin) and the end of that forward's backward (the saved states belong to the
+ * old values).  IGN_ERR_UNSUPPORTED: a batch with halo rows (an edge-cut partition).
+ *
+ * ign_batch_feature_gradients writes [rows][F] = dLoss/d(feature values) of one entity to device
+ * memory, in the plan's stream order, for the loss whose dpred the last backward was given: the first
+ * F columns of the gradient with respect to the entity's initial states (h0 = [features | zeros]).
+ * Valid from the end of a backward (ign_backward, ign_backward_end) to the batch's next
+ * ign_forward_train(_begin) or ign_backward(_begin), else IGN_ERR_INVALID; the same argument and halo
+ * refusals as above.  It needs no opt-in and costs a default training step nothing: every backward
+ * path already carries the state gradients down to iteration 0. */
+int  ign_batch_set_features(ign_plan* plan, ign_batch* batch, int32_t entity, const float* rows);
+int  ign_batch_feature_gradients(ign_plan* plan, ign_batch* batch, int32_t entity, float* dev_out);
 /* MeanSquaredError: loss = mean((pred - labels)^2) (host, may be NULL), dpred = 2 (pred - labels) / n.
  * This is ign_loss with kind IGN_LOSS_MEAN_SQUARED_ERROR. */
 int  ign_mse_loss(ign_plan* plan, const float* pred, const float* labels, int64_t n, float* dpred, double* loss);
