@@ -89,6 +89,20 @@ int check_feature_entity(const ign_plan* p, const ign_batch* b, int32_t e, const
   return IGN_OK;
 }
 
+// what ign_batch_set_edge_params and ign_batch_edge_param_gradients refuse alike
+int check_edge_source(const ign_plan* p, const ign_batch* b, int32_t mi, int32_t s, const void* ptr) {
+  if (!ptr) return fail(IGN_ERR_INVALID, "null argument");
+  if (mi < 0 || mi >= (int)p->mps.size()) return fail(IGN_ERR_INVALID, "mp index %d out of range", mi);
+  const MPP& mp = p->mps[mi];
+  if (s < 0 || s >= (int)mp.src.size()) return fail(IGN_ERR_INVALID, "mp %d has no source %d", mi, s);
+  const MsgNN& nn = mp.nn[s];
+  if (nn.layers.empty()) return fail(IGN_ERR_INVALID, "source %d of mp %d has no message network", s, mi);
+  if (std::find(nn.inputs.begin(), nn.inputs.end(), (int)IGN_MSG_EDGE_PARAMS) == nn.inputs.end() ||
+      !b->mp[mi].d_edge_params[s])
+    return fail(IGN_ERR_INVALID, "the message network of source %d of mp %d does not read edge_params", s, mi);
+  return IGN_OK;
+}
+
 int ensure_device(ign_plan* p) {
   int rc = set_device(p->device);
   if (rc) return rc;
@@ -1205,6 +1219,28 @@ int ign_batch_set_features(ign_plan* p, ign_batch* b, int32_t e, const float* ro
                    (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged);
   if (!dev) (void)hipGetLastError();   // (an unregistered host pointer is an error to the query)
   HIP_TRY(hipMemcpyAsync(b->d_feat[e], rows, bytes, hipMemcpyDefault, p->stream));
+  if (!dev) HIP_TRY(hipStreamSynchronize(p->stream));   // the caller's host rows may die after the call
+  return IGN_OK;
+}
+
+int ign_batch_set_edge_params(ign_plan* p, ign_batch* b, int32_t mi, int32_t s, const float* rows) {
+  int rc = check_pb(p, b);
+  if (rc || (rc = check_edge_source(p, b, mi, s, rows))) return rc;
+  if (b->train && train_step_open(b->train))
+    return fail(IGN_ERR_INVALID, "ign_batch_set_edge_params between a training forward and the end of its backward "
+                "(the saved states belong to the old values)");
+  // Nothing else of the batch is derived from parameter values: every forward gathers the network's
+  // input rows from this buffer (mp_message_nets), the captured graph included, which holds the
+  // pointer.  A halo batch too: a partition owns its in-edges and their rows whole.  One copy in the
+  // plan's stream order; a device source is not waited for
+  const MPB& mb = b->mp[mi];
+  const size_t bytes = (size_t)mb.n_edges[s] * p->mps[mi].nn[s].param_dim * sizeof(float);
+  if (!bytes) return IGN_OK;
+  hipPointerAttribute_t at{};
+  const bool dev = hipPointerGetAttributes(&at, rows) == hipSuccess &&
+                   (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged);
+  if (!dev) (void)hipGetLastError();   // (an unregistered host pointer is an error to the query)
+  HIP_TRY(hipMemcpyAsync(mb.d_edge_params[s], rows, bytes, hipMemcpyDefault, p->stream));
   if (!dev) HIP_TRY(hipStreamSynchronize(p->stream));   // the caller's host rows may die after the call
   return IGN_OK;
 }

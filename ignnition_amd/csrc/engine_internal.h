@@ -267,6 +267,9 @@ int repack(ign_plan* p);                      // runs p->packs: fragments from d
 int check_pb(ign_plan* p, ign_batch* b, bool train = false);
 // ign_batch_set_features / ign_batch_feature_gradients: ptr, the entity, its features, no halo rows
 int check_feature_entity(const ign_plan* p, const ign_batch* b, int32_t e, const void* ptr);
+// ign_batch_set_edge_params / ign_batch_edge_param_gradients: ptr, the MP, its source, a message
+// network on it that reads edge_params
+int check_edge_source(const ign_plan* p, const ign_batch* b, int32_t mi, int32_t s, const void* ptr);
 // readout.cpp: the readout program (operations before predict, GM:611-655) and predict's head
 int readout_batch(ign_plan* p, ign_batch* b, const ign_batch_desc* d);
 // ent: entity-state tensors to read (training keeps every version); null = the batch's current states

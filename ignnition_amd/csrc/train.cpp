@@ -19,6 +19,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <memory>
@@ -47,6 +48,9 @@ struct MPTrain {
   int32_t* nsrc_idx[IGN_MAX_SLOTS] = {nullptr, nullptr, nullptr, nullptr};
   int32_t* ndst_ptr[IGN_MAX_SLOTS] = {nullptr, nullptr, nullptr, nullptr};
   int32_t* ndst_idx[IGN_MAX_SLOTS] = {nullptr, nullptr, nullptr, nullptr};
+  // ign_batch_enable_edge_param_gradients: per source slot whose network reads edge_params, the
+  // backward's sum over this MP's instances of d(network input)'s edge_params columns [edges][param_dim]
+  float* dprm[IGN_MAX_SLOTS] = {nullptr, nullptr, nullptr, nullptr};
 };
 
 struct MPRec {
@@ -99,6 +103,8 @@ struct TrainState {
   NormRun norm;
   bool forward_done = false;
   bool backward_done = false;   // ign_backward_end ran for the last forward: dS holds dLoss/d(initial states)
+  bool edge_grads = false;      // ign_batch_enable_edge_param_gradients: MPTrain::dprm are allocated
+  bool edge_grads_live = false; // ... and the backward that began last zeroed them and adds to them
   // stepped forward / backward (ign_forward_train_begin .. _end, ign_backward_begin .. _end): the
   // edge-cut driver exchanges halo rows between the steps
   int f_it = 0, f_mi = 0;
@@ -280,7 +286,9 @@ int msg_net_backward(ign_plan* p, ign_batch* b, TrainState* t, const MPP& mp, co
     else if (nn.inputs[q] == IGN_MSG_HS_DEST)
       HIP_TRY(launch_csr_gather_cols_add(ddst, b->rows[mp.dst], mt.ndst_ptr[s], mt.ndst_idx[s], t->mdin, nn.din,
                                          col, w, 1, st));
-    col += w;   // edge_params: input data, no gradient
+    else if (nn.inputs[q] == IGN_MSG_EDGE_PARAMS && t->edge_grads_live)   // input data: its gradient only on request
+      HIP_TRY(launch_slice_cols_add(t->mdin, mb.n_edges[s], nn.din, col, w, mt.dprm[s], st));
+    col += w;
   }
   return IGN_OK;
 }
@@ -956,6 +964,13 @@ int ign_backward_begin(ign_plan* p, ign_batch* b, const float* dpred, float* gra
   for (size_t id = 0; id < t->dT.size(); ++id)
     if (t->dT[id])
       HIP_TRY(hipMemsetAsync(t->dT[id], 0, space_rows(p, b, p->ro_t[id]) * p->ro_t[id].width * sizeof(float), st));
+  t->edge_grads_live = t->edge_grads;
+  if (t->edge_grads_live)
+    for (size_t mi = 0; mi < p->mps.size(); ++mi)
+      for (size_t s = 0; s < p->mps[mi].src.size(); ++s)
+        if (t->mp[mi].dprm[s] && b->mp[mi].n_edges[s])
+          HIP_TRY(hipMemsetAsync(t->mp[mi].dprm[s], 0,
+                                 b->mp[mi].n_edges[s] * p->mps[mi].nn[s].param_dim * sizeof(float), st));
 
   // ---- readout (GM:605-629) in reverse: predict, then the operations before it
   const float* x = p->ro_in.size() > 1 ? t->ro_x : readout_tensor(p, b, p->ro_in[0], t->ent.data());
@@ -1196,6 +1211,42 @@ int ign_batch_feature_gradients(ign_plan* p, ign_batch* b, int32_t e, float* dev
                 "or ign_backward_end after its ign_forward_train)");
   HIP_TRY(launch_slice_cols(t->dS[t->dcur[e]][e], b->rows[e], p->ents[e].hidden_dim, p->ents[e].feature_total, dev_out,
                             p->stream));
+  return IGN_OK;
+}
+
+int ign_batch_enable_edge_param_gradients(ign_plan* p, ign_batch* b) {
+  if (!p || !b) return fail(IGN_ERR_INVALID, "null argument");
+  if (b->plan != p) return fail(IGN_ERR_INVALID, "batch was created for another plan");
+  if (!b->train) return fail(IGN_ERR_INVALID, "training not enabled on this batch (ign_batch_enable_training)");
+  TrainState* t = b->train;
+  if (t->edge_grads) return IGN_OK;
+  int rc = set_device(p->device);
+  if (rc) return rc;
+  for (size_t mi = 0; mi < p->mps.size(); ++mi)
+    for (size_t s = 0; s < p->mps[mi].src.size(); ++s) {
+      const MsgNN& nn = p->mps[mi].nn[s];
+      if (nn.layers.empty() || std::find(nn.inputs.begin(), nn.inputs.end(), (int)IGN_MSG_EDGE_PARAMS) == nn.inputs.end())
+        continue;
+      if (!t->mp[mi].dprm[s] && (rc = talloc(t, &t->mp[mi].dprm[s], b->mp[mi].n_edges[s] * nn.param_dim))) return rc;
+    }
+  t->edge_grads = true;
+  return IGN_OK;
+}
+
+// dLoss/d(edge_params) of source s of MP mi after a completed backward: msg_net_backward added the
+// edge_params columns of every instance's d(network input) into MPTrain::dprm, in instance order
+int ign_batch_edge_param_gradients(ign_plan* p, ign_batch* b, int32_t mi, int32_t s, float* dev_out) {
+  int rc = check_train(p, b);
+  if (rc || (rc = check_edge_source(p, b, mi, s, dev_out))) return rc;
+  const TrainState* t = b->train;
+  if (!t->edge_grads)
+    return fail(IGN_ERR_INVALID, "ign_batch_edge_param_gradients needs ign_batch_enable_edge_param_gradients (a default "
+                "backward does not keep them)");
+  if (!t->backward_done || !t->edge_grads_live)
+    return fail(IGN_ERR_INVALID, "ign_batch_edge_param_gradients needs a completed backward of this batch that began after "
+                "the opt-in (ign_backward or ign_backward_end after its ign_forward_train)");
+  const size_t bytes = (size_t)b->mp[mi].n_edges[s] * p->mps[mi].nn[s].param_dim * sizeof(float);
+  if (bytes) HIP_TRY(hipMemcpyAsync(dev_out, t->mp[mi].dprm[s], bytes, hipMemcpyDeviceToDevice, p->stream));
   return IGN_OK;
 }
 

@@ -112,6 +112,11 @@ hipError_t launch_split_cols_add(float* dst, int64_t n, int width, const float* 
 // feature columns of dLoss/d(initial states).  Four columns per thread where width, stride and both
 // pointers allow 16-byte accesses, else one
 hipError_t launch_slice_cols(const float* in, int64_t n, int stride, int width, float* out, hipStream_t st);
+// acc[r][0:width] += in[r][col0 : col0 + width] for n rows of in, stride floats apart (col0 + width <=
+// stride), acc contiguous [n][width]: the edge_params columns of a message network's input gradient,
+// summed over an MP's instances.  Four columns per thread where width, col0, stride and both pointers
+// allow 16-byte accesses, else one
+hipError_t launch_slice_cols_add(const float* in, int64_t n, int stride, int col0, int width, float* acc, hipStream_t st);
 // dz[r][c] = da[r][c] * act'(a[r][c])
 hipError_t launch_act_bwd(const float* da, const float* a, int64_t n, int act, float* dz, hipStream_t st);
 // C[M][N] += sum_r A[r][:M]^T B[r][:N] and, if Cb, Cb[N] += sum_r B[r][:N] (a virtual ones column);

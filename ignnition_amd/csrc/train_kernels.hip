@@ -930,6 +930,21 @@ __global__ void slice_cols_kernel(const float* __restrict__ in, int64_t n, int s
   }
 }
 
+// acc[r][:width] += in[r][col0 : col0 + width], in's rows stride floats apart; V = 4: width, col0,
+// stride % 4 == 0, aligned.  One writer per element: no atomics, the sum over launches is in launch order
+template <int V>
+__global__ void slice_cols_add_kernel(const float* __restrict__ in, int64_t n, int stride, int col0, int width,
+                                      float* __restrict__ acc) {
+  const int wv = width / V;
+  const int64_t total = n * wv;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i / wv;
+    const int c = (int)(i - r * wv) * V;
+    if (V == 4) st4(acc + r * width + c, ld4(acc + r * width + c) + ld4(in + r * stride + col0 + c));
+    else acc[r * width + c] += in[r * stride + col0 + c];
+  }
+}
+
 __global__ void act_bwd_kernel(const float* __restrict__ da, const float* __restrict__ a, int64_t n, int act,
                                float* __restrict__ dz) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
@@ -1629,6 +1644,19 @@ hipError_t launch_slice_cols(const float* in, int64_t n, int stride, int width, 
     hipLaunchKernelGGL(slice_cols_kernel<4>, dim3(blocks_for(n * (width / 4))), dim3(256), 0, st, in, n, stride, width, out);
   else
     hipLaunchKernelGGL(slice_cols_kernel<1>, dim3(blocks_for(n * width)), dim3(256), 0, st, in, n, stride, width, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_slice_cols_add(const float* in, int64_t n, int stride, int col0, int width, float* acc, hipStream_t st) {
+  if (width <= 0 || col0 < 0 || col0 + width > stride) return hipErrorInvalidValue;
+  if (n == 0) return hipSuccess;
+  const bool v4 = width % 4 == 0 && col0 % 4 == 0 && stride % 4 == 0 && ((uintptr_t)in | (uintptr_t)acc) % 16 == 0;
+  if (v4)
+    hipLaunchKernelGGL(slice_cols_add_kernel<4>, dim3(blocks_for(n * (width / 4))), dim3(256), 0, st, in, n, stride, col0,
+                       width, acc);
+  else
+    hipLaunchKernelGGL(slice_cols_add_kernel<1>, dim3(blocks_for(n * width)), dim3(256), 0, st, in, n, stride, col0, width,
+                       acc);
   return hipGetLastError();
 }
 

@@ -777,6 +777,33 @@ def feature_rows(features, rows: int, values) -> np.ndarray:
     return np.ascontiguousarray(v.reshape(rows, F))
 
 
+def edge_param_sources(plan, adj: str):
+    """``(param_dim, [(mp, source, adjacency slot)])``: the MP sources whose message network reads the
+    per-edge parameters of adjacency ``adj`` (``params_<adj>``) as ``edge_params``, in plan order; each
+    owns one buffer in a batch.  ``ValueError`` when there is none.  No GPU is touched."""
+    found = []
+    for m, mp in enumerate(plan.mps):
+        for k, (src, net) in enumerate(zip(mp["sources"], mp.get("nets", []))):
+            if net and "edge_params" in net["inputs"] and plan.adj_slots[src[1]].adj == adj:
+                found.append((m, k, src[1], int(net["param_dim"])))
+    if not found:
+        reads = sorted({plan.adj_slots[src[1]].adj for mp in plan.mps
+                        for src, net in zip(mp["sources"], mp.get("nets", [])) if net and "edge_params" in net["inputs"]})
+        raise ValueError("no message network reads the edge parameters of adjacency %r (read: %s)" % (adj, reads))
+    return found[0][3], [f[:3] for f in found]
+
+
+def edge_param_rows(n_edges: int, param_dim: int, values, what: str = "set_edge_params") -> np.ndarray:
+    """The ``[n_edges, param_dim]`` float32 array ``Batch.set_edge_params`` hands to the engine, without
+    a GPU: ``values`` as ``[n_edges, param_dim]`` or flat (``[n_edges]`` for one parameter), in the
+    order of the ``params_<adj>`` the batch was built from.  Another size or shape is a ``ValueError``."""
+    v = np.asarray(values, np.float32)
+    if v.size != n_edges * param_dim or (v.ndim == 2 and v.shape != (n_edges, param_dim)) or v.ndim > 2:
+        raise ValueError("%s: values have shape %s, the batch needs %d rows of width %d"
+                         % (what, tuple(v.shape), n_edges, param_dim))
+    return np.ascontiguousarray(v.reshape(n_edges, param_dim))
+
+
 def _is_device_tensor(x) -> bool:
     return hasattr(x, "data_ptr") and getattr(x, "is_cuda", False)
 
@@ -821,6 +848,7 @@ class Batch:
         self.gru_steps_per_forward = info.gru_steps_per_forward
         self.rows = list(info.rows)[:E]
         self.graph_rows = num
+        self.graph_edges = cnt               # [graphs, adjacency slots]
         space = p.predict_space     # rows of the predict input space per graph (GM:716-724 splits)
         if space[0] == "entity":
             self.graph_predictions = num[:, space[1]].copy()
@@ -908,9 +936,80 @@ class Batch:
             col += size
         return res
 
+    # ---- what-if analysis: new per-edge parameters (params_<adj>) on the same graphs, their gradient
+    def _edge_sources(self, adj: str):
+        """(edges of the batch, param_dim, [(mp, source)]) of adjacency ``adj`` (edge_param_sources)."""
+        P, found = edge_param_sources(self.engine.plan, adj)
+        return int(self.graph_edges[:, found[0][2]].sum()), P, [(m, k) for m, k, _ in found]
+
+    def set_edge_params(self, adj: str, values):
+        """Replace the per-edge parameters of adjacency ``adj`` in place (ign_batch_set_edge_params, on
+        every MP source whose message network reads them): from the next forward on, the batch computes
+        what a fresh batch built with these ``params_<adj>`` computes, bit for bit.  ``values``:
+        ``[n_edges, param_dim]`` in the batch's edge order (the graphs' ``params_<adj>`` stacked), as an
+        array or as a contiguous float32 CUDA tensor, which is read by its pointer in the engine's
+        stream order with no host copy (make the engine's stream wait for whatever wrote it).  Refused
+        between a training forward and the end of its backward."""
+        ne, P, sources = self._edge_sources(adj)
+        if _is_device_tensor(values):
+            ptr = C.c_void_p(_device_rows(values, ne, P, "set_edge_params").data_ptr())
+        else:
+            src = edge_param_rows(ne, P, values)   # (the engine waits for a host copy)
+            ptr = src.ctypes.data_as(C.c_void_p)
+        if ne == 0:   # (an empty tensor has no address to hand over)
+            return
+        for m, k in sources:
+            check(lib.ign_batch_set_edge_params(self.engine.handle, self.handle, m, k, ptr))
+
+    def enable_edge_param_gradients(self):
+        """Keep dLoss/d(edge parameters) from the next backward on (ign_batch_enable_edge_param_gradients;
+        ``enable_training(edge_param_gradients=True)`` calls it).  A batch without it runs the default
+        training step, launch for launch."""
+        check(lib.ign_batch_enable_edge_param_gradients(self.engine.handle, self.handle))
+
+    def edge_param_source_gradients(self, mp: int, source: int, out):
+        """ign_batch_edge_param_gradients of one (mp, source) into the CUDA tensor ``out``."""
+        check(lib.ign_batch_edge_param_gradients(self.engine.handle, self.handle, int(mp), int(source),
+                                                 C.c_void_p(out.data_ptr())))
+        return out
+
+    def edge_param_gradients(self, adj: str, out=None):
+        """dLoss/d(``params_<adj>``) after a completed backward, ``[n_edges, param_dim]`` in the batch's
+        edge order, for the loss whose ``dpred`` that backward was given: the sum, in plan order, of
+        ign_batch_edge_param_gradients over the MP sources that read the adjacency's parameters (each
+        already summed over its MP's iterations).  The batch must have been opted in before that
+        backward began (``enable_training(edge_param_gradients=True)`` or
+        ``enable_edge_param_gradients``); nothing is enabled from here.  With ``out`` a contiguous
+        float32 CUDA tensor it is filled on the engine's stream (torch's current stream is made to
+        follow the plan's for the adds) and returned; else a float32 ndarray."""
+        import torch
+        ne, P, sources = self._edge_sources(adj)
+        dev = "cuda:%d" % self.engine.device
+        if out is not None:
+            if not _is_device_tensor(out):
+                raise ValueError("edge_param_gradients: out must be a CUDA tensor")
+            _device_rows(out, ne, P, "edge_param_gradients")
+        total = out if out is not None else torch.empty((ne, P), dtype=torch.float32, device=dev)
+        if out is not None:
+            torch.cuda.synchronize(dev)   # whatever torch queued on out, before the engine's stream writes it
+        self.edge_param_source_gradients(*sources[0], out=total)
+        if len(sources) > 1:
+            part = torch.empty((ne, P), dtype=torch.float32, device=dev)
+            for m, k in sources[1:]:
+                self.edge_param_source_gradients(m, k, out=part)
+                self.engine.synchronize()   # the adds run on torch's stream
+                total.view(ne, P).add_(part)
+                torch.cuda.synchronize(dev)
+        if out is not None:
+            return out
+        self.engine.synchronize()
+        return total.cpu().numpy()
+
     # ---- training -------------------------------------------------------------------------
-    def enable_training(self):
+    def enable_training(self, edge_param_gradients: bool = False):
         check(lib.ign_batch_enable_training(self.engine.handle, self.handle))
+        if edge_param_gradients:
+            self.enable_edge_param_gradients()
 
     def set_dropout(self, seed: int, step: int):
         """The Dropout mask stream of the next ``forward_train`` (ign_batch_set_dropout); never
@@ -1068,6 +1167,25 @@ class SplitBatch:
         for b in self.parts:
             b.set_features(entity, whole[row:row + b.rows[e]])
             row += b.rows[e]
+
+    def set_edge_params(self, adj: str, values):
+        """``Batch.set_edge_params`` on every sub-batch with its graphs' edges of ``values`` (the edges of
+        the whole batch, in graph order; an array or a CUDA tensor as there)."""
+        P, found = edge_param_sources(self.engine.plan, adj)
+        counts = [int(b.graph_edges[:, found[0][2]].sum()) for b in self.parts]
+        if _is_device_tensor(values):
+            whole = _device_rows(values, sum(counts), P, "set_edge_params").reshape(sum(counts), P)
+        else:
+            whole = edge_param_rows(sum(counts), P, values)
+        row = 0
+        for b, n in zip(self.parts, counts):
+            b.set_edge_params(adj, whole[row:row + n])
+            row += n
+
+    def edge_param_gradients(self, adj: str):
+        """``Batch.edge_param_gradients`` of every sub-batch, concatenated in graph order: for a caller
+        that runs training steps on ``parts`` itself (each opted in, each after its own backward)."""
+        return np.concatenate([b.edge_param_gradients(adj) for b in self.parts], 0)
 
     def synchronize(self):
         for e in self.engines:

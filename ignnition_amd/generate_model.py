@@ -243,7 +243,7 @@ class ComnetModel:
         """Flattened predictions of every graph, concatenated in batch order (GM:716-724)."""
         return self.batch(graphs).forward().reshape(-1)
 
-    def sensitivities(self, graphs, dpred=None):
+    def sensitivities(self, graphs, dpred=None, edge_params: bool = False):
         """``(predictions, {entity: {feature: gradient}})`` of a batch of graphs: the batch is built,
         its training forward and one backward run, and the gradient of ``sum(dpred * predictions)`` with
         respect to every input feature is read back (``Batch.feature_gradients``).  ``dpred``:
@@ -251,11 +251,13 @@ class ComnetModel:
         The gradients are with respect to the normalised feature values the engine is fed (the values
         in ``graphs``), not the raw ones in front of a normalisation function; each is ``[rows, size]``
         in batch row order.  Entities without features are left out.  The model's Dropout layers draw
-        the (0, 0) mask stream of a training forward."""
+        the (0, 0) mask stream of a training forward.  ``edge_params=True``: the result also carries
+        ``{"params_<adj>": gradient [edges, param_dim]}`` for every adjacency whose per-edge parameters
+        some message network reads (``Batch.edge_param_gradients``); the other entries are unchanged."""
         import torch
         b = self.batch(graphs)
         try:
-            b.enable_training()
+            b.enable_training(edge_param_gradients=edge_params)
             pred = b.forward_train()
             dev = "cuda:%d" % self.engine.device
             if dpred is None:
@@ -269,6 +271,12 @@ class ComnetModel:
             torch.cuda.synchronize(dev)   # torch filled them on its own stream, the engine reads on the plan's
             b.backward(d, grads)
             out = {name: b.feature_gradients(name) for name, f in zip(self.plan.entities, self.plan.features) if f}
+            if edge_params:
+                for mp in self.plan.mps:
+                    for src, net in zip(mp["sources"], mp.get("nets", [])):
+                        adj = self.plan.adj_slots[src[1]].adj
+                        if net and "edge_params" in net["inputs"] and "params_" + adj not in out:
+                            out["params_" + adj] = b.edge_param_gradients(adj)
         finally:
             b.close()
         return pred, out

@@ -472,6 +472,34 @@ int  ign_dropout_keep(uint64_t seed, int32_t site, uint32_t step, int64_t rows, 
  * path already carries the state gradients down to iteration 0. */
 int  ign_batch_set_features(ign_plan* plan, ign_batch* batch, int32_t entity, const float* rows);
 int  ign_batch_feature_gradients(ign_plan* plan, ign_batch* batch, int32_t entity, float* dev_out);
+/* ---- Edge parameters of a live batch and their gradient (ABI 13 additions) -----------------------
+ * The other input a what-if changes on fixed graphs: params_<adj>, which a message network of MP
+ * source (mp, source) reads as edge_params.  Each such source owns one buffer [n_edges][param_dim];
+ * two sources reading one adjacency own two (a caller that changes the adjacency's values writes both,
+ * and adds their gradients).
+ * ign_batch_set_edge_params replaces that buffer: rows is [n_edges][param_dim] in the order of the
+ * params_<adj> the batch was created from, host or device memory, copied as ign_batch_set_features
+ * copies.  From the next forward on (ign_forward with its captured graph, the per-MP launches,
+ * ign_forward_train and its stepped form, the backward's recompute) the batch computes what a fresh
+ * batch created with these values computes, bit for bit: every forward gathers the network's input
+ * from this buffer and nothing else depends on its values.  A batch with halo rows is served too: a
+ * partition owns the in-edges it keeps and their parameter rows.
+ * IGN_ERR_INVALID: a null pointer, mp or source out of range, a source without a message network or
+ * whose network does not read edge_params, and a call between ign_forward_train(_begin) and the end
+ * of that forward's backward.
+ *
+ * ign_batch_enable_edge_param_gradients (after ign_batch_enable_training) allocates one accumulator
+ * [n_edges][param_dim] per such source; from the next ign_backward(_begin) on, every MP instance of a
+ * backward adds its network-input gradient's edge_params columns to it, in instance order (no
+ * atomics: bitwise reproducible).  Without the call a training step launches and computes exactly
+ * what it did before.
+ * ign_batch_edge_param_gradients copies [n_edges][param_dim] = dLoss/d(edge_params) of one source,
+ * summed over the MP's T instances, to device memory in the plan's stream order.  Valid from the end
+ * of a backward that began after the opt-in to the batch's next ign_forward_train(_begin) or
+ * ign_backward(_begin), else IGN_ERR_INVALID; the argument refusals as above. */
+int  ign_batch_set_edge_params(ign_plan* plan, ign_batch* batch, int32_t mp, int32_t source, const float* rows);
+int  ign_batch_enable_edge_param_gradients(ign_plan* plan, ign_batch* batch);
+int  ign_batch_edge_param_gradients(ign_plan* plan, ign_batch* batch, int32_t mp, int32_t source, float* dev_out);
 /* MeanSquaredError: loss = mean((pred - labels)^2) (host, may be NULL), dpred = 2 (pred - labels) / n.
  * This is ign_loss with kind IGN_LOSS_MEAN_SQUARED_ERROR. */
 int  ign_mse_loss(ign_plan* plan, const float* pred, const float* labels, int64_t n, float* dpred, double* loss);
