@@ -16,7 +16,7 @@ OBJ = os.path.join(HERE, "build")
 OUT = os.path.join(HERE, "libignmp.so")
 # the resident kernel's phase-A instruction mix (tools/isa_mix.py), read by bench.py's roofline.issue
 ISA_MIX = os.path.join(HERE, "isa_mix.json")
-SOURCES = ["engine.cpp", "mp_step.cpp", "plan_lower.cpp", "batch_lower.cpp", "devpool.cpp", "train.cpp", "dense_stack.cpp", "train_lower.cpp", "learn.cpp", "readout.cpp", "dataset.cpp", "plan_json.cpp", "kernels.hip", "kernels_bf.hip",
+SOURCES = ["engine.cpp", "mp_step.cpp", "plan_lower.cpp", "batch_lower.cpp", "devpool.cpp", "train.cpp", "train_alloc.cpp", "mp_backward.cpp", "dense_stack.cpp", "train_lower.cpp", "learn.cpp", "readout.cpp", "dataset.cpp", "plan_json.cpp", "kernels.hip", "kernels_bf.hip",
            "train_kernels.hip", "learn_kernels.hip", "readout_kernels.hip", "resident.hip", "readout_h32.hip", "train_csr.hip",
            "dropout.cpp", "dropout_kernels.hip", "layernorm.cpp", "layernorm_kernels.hip", "cell_options.cpp", "gru_cell.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-Wno-unused-value"]

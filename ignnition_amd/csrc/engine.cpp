@@ -134,6 +134,11 @@ hipStream_t upload_stream() {
   return s;
 }
 
+bool env_flag(const char* name, bool dflt) {
+  const char* v = getenv(name);
+  return v && *v ? atoi(v) != 0 : dflt;
+}
+
 namespace {
 struct UploadState {   // per host thread and device
   char* stage = nullptr;
@@ -154,10 +159,6 @@ UploadState& upload_state() {
   if ((int)st.size() <= dev) st.resize(dev + 1);
   if (!st[dev]) st[dev] = std::make_unique<UploadState>();
   return *st[dev];
-}
-bool env_flag(const char* name, bool dflt) {
-  const char* v = getenv(name);
-  return v && *v ? atoi(v) != 0 : dflt;
 }
 double now_ms() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -507,7 +508,7 @@ static bool resident_plan_shape(const ign_plan* p, ResShape* sh) {
 
 // ---------------------------------------------------------------------------------------------
 // ign_batch_create's per-MP steps: batch_lower.cpp builds an MP's host tables, these upload them (in
-// a fixed order: the pool hands out its blocks by it) and keep the host copies train.cpp reads.
+// a fixed order: the pool hands out its blocks by it) and keep the host copies train_alloc.cpp reads.
 
 // message networks: per-edge rows and parameters (GM:440-475)
 static int upload_message_nets(ign_batch* b, const MPP& mp, size_t mi, const BatchShape& sh, MPB& mb) {

@@ -1,5 +1,5 @@
-// engine_internal.h — plan / batch structures shared by engine.cpp (inference) and train.cpp
-// (training).  Not part of the C ABI.
+// engine_internal.h — plan / batch structures shared by engine.cpp (inference) and the training
+// units (train.cpp, train_alloc.cpp, mp_backward.cpp).  Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -21,8 +21,8 @@
 #include "host_types.h"   // the host-only types (MPP, hvec, IdxArr, ...), shared with batch_lower.h
 #include "plan_lower.h"   // PlanModel: the lowered plan without the device
 
-struct TrainState;                 // train.cpp
-void train_state_destroy(TrainState* t);
+struct TrainState;                 // train_state.h
+void train_state_destroy(TrainState* t);   // train_alloc.cpp
 // between ign_forward_train_begin and the end of that forward's backward (train.cpp)
 bool train_step_open(const TrainState* t);
 
@@ -259,6 +259,7 @@ int resident_sum_mps(const ign_plan* p, int* sum_mp, int* n_src);   // 0: not a 
 inline bool skips_last(const ign_plan* p, const ign_batch* b, int mi) {
   return p->dead_last && p->mps[mi].dead_in_last_iter && !b->ext_state[p->mps[mi].dst];
 }
+bool env_flag(const char* name, bool dflt);   // a 0 / 1 environment switch (unset or empty: dflt)
 int set_device(int dev);
 int ensure_device(ign_plan* p);
 int dev_alloc(ign_batch* b, float** out, int64_t n);

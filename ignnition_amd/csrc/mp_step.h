@@ -1,6 +1,7 @@
 // mp_step.h — one message-passing (MP) instance forward, for ign_forward_mp (engine.cpp), for
-// ign_forward_train_mp and, its message networks and projected table, ign_backward_mp's recompute
-// (train.cpp).  What depends on the mode hangs on the save record.
+// ign_forward_train_mp (train.cpp) and, its message networks and projected table, the recompute of
+// the instance's backward (mp_backward.cpp).  What depends on the mode hangs on the save record
+// (DESIGN.md §2).
 #pragma once
 #include "engine_internal.h"
 #include "gru_cell.h"

@@ -382,7 +382,7 @@ void layout_packed(PlanModel* p) {
     // fragments and its bias form, and none of the split pieces below.  Their absence is what takes
     // the cell off the fast paths: the resident forward (resident_plan_shape needs pk_uh / pk_wbf /
     // pk_ubf), the split-bf16 / split-fp16 sequence and sum variants, and sum_gru_g32's fused projection
-    // (its own pieces, and the target cell's pk_wbf).  mp_step.cpp and train.cpp dispatch on is_default().
+    // (its own pieces, and the target cell's pk_wbf).  mp_step.cpp and mp_backward.cpp dispatch on is_default().
     const bool dflt = cp.is_default();
     const int mode = dflt ? 0 : kPackGruRaw | cp.bias_rows();
     cp.pk_w = slot(AT_CELL, c, 0, PK_GRU, pack_gru_w_floats(din, H), cp.off_k, cp.off_rk, cp.off_b, din, H, mode);

@@ -1,7 +1,7 @@
 // train_lower.h — the host-side lowering of a batch's training tables: the transposed CSRs the
 // backward walks, from the host copies of the index tables the batch keeps.  Pure host code (no HIP
 // header, no device or pool call), so it runs and is checked on a CPU (tests/cpp/train_lower_check.cpp);
-// train.cpp uploads what it returns.  The source row -> steps / destinations tables also have a GPU
+// train_alloc.cpp uploads what it returns.  The source row -> steps / destinations tables also have a GPU
 // builder (train_csr.hip, the default where no pre-summed row is involved); the others are built here only.
 #pragma once
 #include <utility>
