@@ -92,7 +92,7 @@ struct Readout3Args {
   const float* w3;  const float* b3;  // [N2] (output units == 1), [1]
   int act1, act2, act3;
   float* y;                // [n_rows]
-  float* save1 = nullptr;  // readout_h16 only: [n_rows][N1] layer-1 activations (training forward)
+  float* save1 = nullptr;  // readout_h16 / _h32 / readout3: [n_rows][N1] layer-1 activations (training forward)
   float* save2 = nullptr;  //   [n_rows][N2] layer-2 activations
 };
 

@@ -783,7 +783,9 @@ __global__ __launch_bounds__(64 * WAVES) void sum_gru_lds_kernel(SumGruArgs a) {
 // accumulator layout (N1/16 tiles x 2) and feed layer 2 as B operands; layer 2 is produced
 // 16 units at a time and immediately contracted with the 1-unit output layer, so the second
 // hidden layer is never materialised.  W1/W2 fragments stream from L2 as float4 per lane.
-template <int DIN, int N1, int N2, int ACT>
+// SAVE (the training forward of a plan whose inference readout is this kernel): both hidden layers'
+// activations are also written (a.save1 [n_rows][N1], a.save2 [n_rows][N2]); the arithmetic is the same.
+template <int DIN, int N1, int N2, int ACT, bool SAVE = false>
 __global__ __launch_bounds__(256) void readout3_kernel(Readout3Args a) {
   constexpr int C0 = DIN / 16, U1 = N1 / 16, U2 = N2 / 16;
   __shared__ f4 sw2[2][U1 * 64];
@@ -824,6 +826,11 @@ __global__ __launch_bounds__(256) void readout3_kernel(Readout3Args a) {
     }
     h1[u][0] = acc0;
     h1[u][1] = acc1;
+    if constexpr (SAVE) {
+      const int64_t r0 = base + j, r1 = base + 16 + j;
+      if (r0 < a.n_rows) st4(a.save1 + r0 * N1 + 16 * u + 4 * g, acc0);
+      if (r1 < a.n_rows) st4(a.save1 + r1 * N1 + 16 * u + 4 * g, acc1);
+    }
   }
 
   // Layer 2, 16 output units (one 16 KB chunk of packed W2 fragments) at a time.  The chunk is
@@ -865,8 +872,15 @@ __global__ __launch_bounds__(256) void readout3_kernel(Readout3Args a) {
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      y0 += w3[r] * act_t<ACT>(acc0[r]);
-      y1 += w3[r] * act_t<ACT>(acc1[r]);
+      acc0[r] = act_t<ACT>(acc0[r]);
+      acc1[r] = act_t<ACT>(acc1[r]);
+      y0 += w3[r] * acc0[r];
+      y1 += w3[r] * acc1[r];
+    }
+    if constexpr (SAVE) {
+      const int64_t r0 = base + j, r1 = base + 16 + j;
+      if (r0 < a.n_rows) st4(a.save2 + r0 * N2 + 16 * v + 4 * g, acc0);
+      if (r1 < a.n_rows) st4(a.save2 + r1 * N2 + 16 * v + 4 * g, acc1);
     }
 #pragma unroll
     for (int k = 0; k < PER; ++k) sw2[cur ^ 1][tid + 256 * k] = stage[k];
@@ -1080,26 +1094,32 @@ hipError_t launch_sum_gru(const SumGruArgs& args, int din, int h, int variant, h
   return hipErrorInvalidValue;
 }
 
-template <int DIN>
+template <int DIN, bool SAVE>
 static hipError_t readout3_din(const Readout3Args& args, int act, dim3 grid, hipStream_t st) {
   switch (act) {
-    case IGN_K_ACT_SELU: hipLaunchKernelGGL((readout3_kernel<DIN, 256, 256, IGN_K_ACT_SELU>), grid, dim3(256), 0, st, args); break;
-    case IGN_K_ACT_RELU: hipLaunchKernelGGL((readout3_kernel<DIN, 256, 256, IGN_K_ACT_RELU>), grid, dim3(256), 0, st, args); break;
-    case IGN_K_ACT_TANH: hipLaunchKernelGGL((readout3_kernel<DIN, 256, 256, IGN_K_ACT_TANH>), grid, dim3(256), 0, st, args); break;
-    case IGN_K_ACT_SIGMOID: hipLaunchKernelGGL((readout3_kernel<DIN, 256, 256, IGN_K_ACT_SIGMOID>), grid, dim3(256), 0, st, args); break;
-    case IGN_K_ACT_LINEAR: hipLaunchKernelGGL((readout3_kernel<DIN, 256, 256, IGN_K_ACT_LINEAR>), grid, dim3(256), 0, st, args); break;
+    case IGN_K_ACT_SELU: hipLaunchKernelGGL((readout3_kernel<DIN, 256, 256, IGN_K_ACT_SELU, SAVE>), grid, dim3(256), 0, st, args); break;
+    case IGN_K_ACT_RELU: hipLaunchKernelGGL((readout3_kernel<DIN, 256, 256, IGN_K_ACT_RELU, SAVE>), grid, dim3(256), 0, st, args); break;
+    case IGN_K_ACT_TANH: hipLaunchKernelGGL((readout3_kernel<DIN, 256, 256, IGN_K_ACT_TANH, SAVE>), grid, dim3(256), 0, st, args); break;
+    case IGN_K_ACT_SIGMOID: hipLaunchKernelGGL((readout3_kernel<DIN, 256, 256, IGN_K_ACT_SIGMOID, SAVE>), grid, dim3(256), 0, st, args); break;
+    case IGN_K_ACT_LINEAR: hipLaunchKernelGGL((readout3_kernel<DIN, 256, 256, IGN_K_ACT_LINEAR, SAVE>), grid, dim3(256), 0, st, args); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }
 
+template <bool SAVE>
+static hipError_t readout3_save(const Readout3Args& args, int din, dim3 grid, hipStream_t st) {
+  if (din == 32) return readout3_din<32, SAVE>(args, args.act1, grid, st);
+  if (din == 16) return readout3_din<16, SAVE>(args, args.act1, grid, st);
+  return readout3_din<64, SAVE>(args, args.act1, grid, st);
+}
+
 hipError_t launch_readout3(const Readout3Args& args, int din, int n1, int n2, hipStream_t st) {
   if (args.n_rows == 0) return hipSuccess;
   if (!readout3_supported(din, n1, n2, args.act1, args.act2, args.act3)) return hipErrorInvalidValue;
+  if (!args.save1 != !args.save2) return hipErrorInvalidValue;
   dim3 grid(grid_for(args.n_rows, 128));
-  if (din == 32) return readout3_din<32>(args, args.act1, grid, st);
-  if (din == 16) return readout3_din<16>(args, args.act1, grid, st);
-  return readout3_din<64>(args, args.act1, grid, st);
+  return args.save1 ? readout3_save<true>(args, din, grid, st) : readout3_save<false>(args, din, grid, st);
 }
 
 hipError_t launch_dense_generic(const float* x, int64_t n, int in, int x_stride, const float* W, const float* b,

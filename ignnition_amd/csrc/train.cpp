@@ -188,8 +188,13 @@ int ign_forward_train_end(ign_plan* p, ign_batch* b, float* pred_out) {
   // the inference readout kernel (readout_h16 / _h32, as readout_fused picks it) with its activations
   // written out: one launch, no re-read of layer 1's output; its two saving kernels, three Dense layers only
   // (a stack with a Dropout site runs layer by layer: the mask sits between two of its launches)
-  const bool fused = p->train_fused_readout && p->fused_readout && p->readout_variant >= 4 && p->dense.size() == 3 &&
-                     p->dense[1].pk_h >= 0 && p->dense[0].pk_bf >= 0 && p->dense[1].pk_bf >= 0 &&
+  // A plan with a cell with options keeps forward's bits in its training forward: where its
+  // inference readout is the f32 readout3 (no split pieces: a predict input of 16 columns, or
+  // IGN_READOUT_VARIANT=1), that kernel's saving form runs here too.  A plan of default cells keeps its
+  // layer-by-layer stack there.
+  const bool split = p->dense.size() == 3 && p->readout_variant >= 2 && p->dense[0].pk_bf >= 0 && p->dense[1].pk_bf >= 0;
+  const bool fused = p->train_fused_readout && p->fused_readout && p->dense.size() == 3 &&
+                     ((p->readout_variant >= 4 && p->dense[1].pk_h >= 0 && split) || (p->any_cell_options && !split)) &&
                      p->dense[0].use_bias && p->dense[1].use_bias && p->seq.size() == p->dense.size();
   Timer untimed{nullptr};
   if ((rc = fused ? readout_fused(p, b, x, t->act[0], t->act[1], untimed, st)
