@@ -128,7 +128,7 @@ SYMBOLS = ["ign_abi_version", "ign_last_error", "ign_device_count", "ign_plan_cr
            "ign_plan_add_dropout", "ign_batch_set_dropout", "ign_dropout_keep", "ign_plan_add_layernorm",
            "ign_plan_mp_dead_last", "ign_plan_set_cell_options", "ign_batch_set_features",
            "ign_batch_feature_gradients", "ign_batch_set_edge_params", "ign_batch_enable_edge_param_gradients",
-           "ign_batch_edge_param_gradients"]
+           "ign_batch_edge_param_gradients", "ign_nonfinite_count"]
 
 ABI_VERSION = 13
 PART = {"all": 0, "interior": 1, "boundary": 2}
@@ -220,6 +220,7 @@ def _load():
         "ign_batch_set_edge_params": (C.c_int, [VP, VP, i32, i32, VP]),
         "ign_batch_enable_edge_param_gradients": (C.c_int, [VP, VP]),
         "ign_batch_edge_param_gradients": (C.c_int, [VP, VP, i32, i32, VP]),
+        "ign_nonfinite_count": (C.c_int, [VP, VP, i64, VP]),
     }
     # an A/B build of an older tree may lack newer entry points: only the A/B tools, which set
     # IGN_AB_LIB=1 next to IGN_LIB_PATH, skip them; any other library must export every symbol

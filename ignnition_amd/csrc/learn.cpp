@@ -185,6 +185,18 @@ int ign_optimizer_step(ign_plan* p, const ign_optimizer_desc* d, const float* gr
   return repack(p);
 }
 
+int ign_nonfinite_count(ign_plan* p, const float* dev, int64_t n, uint32_t* dev_count) {
+  if (!p || !dev || !dev_count) return fail(IGN_ERR_INVALID, "null argument");
+  if (n < 0) return fail(IGN_ERR_INVALID, "negative element count");
+  if (((uintptr_t)dev & 3) || ((uintptr_t)dev_count & 3))
+    return fail(IGN_ERR_INVALID, "ign_nonfinite_count: pointers must be 4-byte aligned");
+  if (n == 0) return IGN_OK;
+  int rc = ensure_device(p);
+  if (rc) return rc;
+  HIP_TRY(launch_nonfinite_count(dev, n, dev_count, p->stream));
+  return IGN_OK;
+}
+
 int ign_adam_step(ign_plan* p, const float* grads, float* m, float* v, int64_t iteration, float lr, float beta1,
                   float beta2, float epsilon) {
   if (!p || !grads || !m || !v) return fail(IGN_ERR_INVALID, "null argument");

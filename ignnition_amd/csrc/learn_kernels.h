@@ -36,5 +36,7 @@ struct OptimizerLaunch {
   int nesterov, centered;
 };
 hipError_t launch_optimizer(const OptimizerLaunch& o, hipStream_t st);
+// *count += the number of NaN / +-Inf among x[0..n) (x 4-byte aligned, n == 0: no launch)
+hipError_t launch_nonfinite_count(const float* x, int64_t n, uint32_t* count, hipStream_t st);
 // part[b] = partial sums of x^2
 hipError_t launch_sumsq(const float* x, int64_t n, double* part, int nblk, hipStream_t st);

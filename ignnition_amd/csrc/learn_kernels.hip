@@ -191,7 +191,54 @@ __global__ void optimizer_kernel(OptArgs a) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The non-finite guard: *count += the number of NaN / +-Inf among x[0..n).  A value is non-finite
+// when its exponent field is all ones; the test is on the bit pattern, so no floating-point
+// option of the compiler can fold it.  x + head is 16-byte aligned: the nvec float4 of the body
+// are read as such (grid-stride), the head scalars before it and the tail (< 4) scalars after it
+// by the first head + tail threads of the grid.  Each wave sums its lanes' counts, the block its
+// four waves', and a block that found any adds its sum with one atomic: an integer sum, the same
+// in any order.
+__device__ __forceinline__ uint32_t nonfinite_bits(float v) {
+  return (__float_as_uint(v) & 0x7F800000u) == 0x7F800000u ? 1u : 0u;
+}
+
+__global__ void nonfinite_kernel(const float* __restrict__ x, int64_t head, int64_t nvec, int64_t tail,
+                                 uint32_t* __restrict__ count) {
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const float4* __restrict__ body = reinterpret_cast<const float4*>(x + head);
+  uint32_t c = 0;
+  for (int64_t i = tid; i < nvec; i += (int64_t)gridDim.x * blockDim.x) {
+    const float4 q = body[i];
+    c += nonfinite_bits(q.x) + nonfinite_bits(q.y) + nonfinite_bits(q.z) + nonfinite_bits(q.w);
+  }
+  if (tid < head)
+    c += nonfinite_bits(x[tid]);
+  else if (tid < head + tail)
+    c += nonfinite_bits(x[head + 4 * nvec + (tid - head)]);
+  for (int o = warpSize / 2; o > 0; o >>= 1) c += __shfl_down(c, o);
+  __shared__ uint32_t wave_sum[256 / 64];
+  if ((threadIdx.x & (warpSize - 1)) == 0) wave_sum[threadIdx.x / warpSize] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t s = 0;
+    for (int w = 0; w < (int)(blockDim.x / warpSize); ++w) s += wave_sum[w];
+    if (s) atomicAdd(count, s);
+  }
+}
+
 }  // namespace
+
+hipError_t launch_nonfinite_count(const float* x, int64_t n, uint32_t* count, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  // scalars up to the first 16-byte boundary (x is 4-byte aligned), then whole float4, then the rest
+  const int64_t head = std::min<int64_t>(n, (int64_t)(((16 - ((uintptr_t)x & 15)) & 15) / 4));
+  const int64_t nvec = (n - head) / 4;
+  const int64_t tail = n - head - 4 * nvec;
+  const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>((nvec + 255) / 256, 256)));
+  hipLaunchKernelGGL(nonfinite_kernel, grid, dim3(256), 0, st, x, head, nvec, tail, count);
+  return hipGetLastError();
+}
 
 hipError_t launch_loss(int kind, const float* pred, const float* label, int64_t n, float* dpred, double* part,
                        int nblk, hipStream_t st) {

@@ -596,6 +596,17 @@ class Engine:
         check(lib.ign_optimizer_step(self.handle, C.byref(desc), _ptr(grads), arr, len(slots), int(iteration), lr))
         self.params_version += 1
 
+    def nonfinite_count(self, tensor, counter):
+        """ign_nonfinite_count: enqueue, on the plan's stream, ``counter += the number of NaN / +-Inf
+        values of tensor`` (a contiguous float32 device tensor, any 4-byte-aligned view of one; counter:
+        one 4-byte integer on the device, read as unsigned).  No host wait; an empty tensor launches nothing."""
+        if str(tensor.dtype) != "torch.float32" or not tensor.is_contiguous():
+            raise ValueError("nonfinite_count: the tensor must be contiguous float32, not %s" % (tensor.dtype,))
+        if counter.element_size() != 4 or counter.numel() != 1 or counter.is_floating_point():
+            raise ValueError("nonfinite_count: the counter must be one 4-byte integer")
+        if tensor.numel():   # (an empty tensor may have no address)
+            check(lib.ign_nonfinite_count(self.handle, _ptr(tensor), tensor.numel(), _ptr(counter)))
+
     def adam_step(self, grads, m, v, iteration: int, lr: float, beta1=0.9, beta2=0.999, epsilon=1e-7):
         """ign_adam_step: ``optimizer_step`` for Adam with loose hyper-parameters."""
         check(lib.ign_adam_step(self.handle, _ptr(grads), _ptr(m), _ptr(v), int(iteration), lr, beta1, beta2, epsilon))

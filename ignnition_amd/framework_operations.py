@@ -188,13 +188,19 @@ def train_and_evaluate(model, dist=None, device: int = 0, log_every: int = 10):
     The same INI options drive it:
     - ``[PATHS]`` train_dataset, eval_dataset, model_dir (an ``experiment_<datetime>`` subdirectory
       is created, FO:124), warm_start_path (``kernel`` / ``recurrent_kernel`` / ``bias`` tensors,
-      FO:126-131);
+      FO:126-131), and ``resume_from`` (an ``experiment_*`` directory or a ``state-*.safetensors``
+      file: the run continues there, see below);
     - ``[TRAINING_OPTIONS]`` batch_size, train_steps, eval_samples, shuffle_train_samples,
-      shuffle_eval_samples, save_checkpoints_secs, keep_checkpoint_max, throttle_secs, and
-      ``native_reader`` (default True: the C++ dataset reader; False: the Python generator).
+      shuffle_eval_samples, save_checkpoints_secs, save_checkpoints_steps (RunConfig's other rule,
+      default off), keep_checkpoint_max, throttle_secs, ``native_reader`` (default True: the C++
+      dataset reader; False: the Python generator), ``input_seed`` (the training stream's shuffle
+      seed, default: from entropy) and ``check_finite`` (default True: the Estimator's NanTensorHook).
 
     The Estimator's checkpoint/evaluate cycle becomes:
-    - a safetensors checkpoint every ``save_checkpoints_secs`` and at the end;
+    - a safetensors checkpoint ``ckpt-<step>`` (the parameters) and beside it the training state
+      ``state-<step>`` (``Trainer.state()`` and the input stream's seed, world, batch_size and
+      shuffle_train_samples) every ``save_checkpoints_secs``, every ``save_checkpoints_steps`` steps
+      and at the end, written by rank 0, both pruned to ``keep_checkpoint_max``;
     - an evaluation of ``eval_samples`` one-graph batches after each checkpoint, at most every
       ``throttle_secs``;
     - metrics appended to ``<model_dir>/metrics.jsonl``.
@@ -202,11 +208,24 @@ def train_and_evaluate(model, dist=None, device: int = 0, log_every: int = 10):
     ``execute_gpu`` is ignored: in the reference, ``True`` *hides* the GPU (FO:134-145); here
     every step runs on the HIP engine. With ``dist`` (torch.distributed, initialised), each rank
     trains on its slice of every global batch (disjoint samples, one shuffle seed broadcast from
-    rank 0) and gradients are averaged by all-reduce."""
+    rank 0) and gradients are averaged by all-reduce.
+
+    ``resume_from`` restores what the Estimator restores from ``model_dir``: every rank loads the
+    newest state file that reads, takes the parameters, optimizer slots, step, dropout seed and input
+    seed from it, skips the batches the run has consumed and runs steps ``iterations + 1 ..
+    train_steps`` in the same directory, appending to its ``metrics.jsonl``; the result is bitwise the
+    uninterrupted run's.  ValueError: together with ``warm_start_path``, or with a
+    world, batch_size or shuffle_train_samples other than the stored ones (the ranks' slices of the
+    stream would differ).
+
+    With ``check_finite`` a NaN or Inf in the gradient or the loss raises
+    ``training.NonFiniteTraining`` at the next step the host waits on (a logged step or a
+    checkpoint); no checkpoint or state file is written from then on, the newest clean state file
+    is logged, and the exception is re-raised."""
     import time
 
-    from .checkpoint import load_params, save_params
-    from .training import Trainer
+    from .checkpoint import latest_state, load_params, load_training_state, save_params, save_training_state, state_files
+    from .training import NonFiniteTraining, Trainer
 
     log.warning("IGNNITION: Starting the training and evaluation process...")
     gm.set_model_info(model)
@@ -216,14 +235,44 @@ def train_and_evaluate(model, dist=None, device: int = 0, log_every: int = 10):
     train_steps = int(opts["train_steps"])
     eval_samples = int(opts.get("eval_samples", "100"))
     save_secs = float(opts.get("save_checkpoints_secs", "600"))
+    save_steps = int(opts.get("save_checkpoints_steps", "0"))
+    check_finite = str_to_bool(opts.get("check_finite", "True"))
+    shuffle_train = str_to_bool(opts.get("shuffle_train_samples", "False"))
     keep = int(opts.get("keep_checkpoint_max", "5"))
     throttle = float(opts.get("throttle_secs", "600"))
     rank = dist.get_rank() if dist is not None and dist.is_initialized() else 0
     world = dist.get_world_size() if dist is not None and dist.is_initialized() else 1
-    model_dir = os.path.join(paths["model_dir"], "experiment_" + str(datetime.datetime.now()).replace(" ", "_"))
+    stream = {"world": world, "batch_size": batch_size, "shuffle_train_samples": shuffle_train}
+    resumed = None
+    if paths.get("resume_from", None):
+        if paths.get("warm_start_path", None):
+            raise ValueError("resume_from and warm_start_path are both set: a resumed run takes every tensor from its "
+                             "state file")
+        src = paths["resume_from"]
+        if os.path.isdir(src):
+            found = latest_state(src)
+            if found is None:
+                raise ValueError("resume_from: no readable state-<step>.safetensors in %s" % src)
+            model_dir, resumed = src, found[1]
+            log.warning("IGNNITION: resuming from %s", found[0])
+        else:
+            model_dir, resumed = os.path.dirname(os.path.abspath(src)), load_training_state(src)
+        stored = resumed["meta"].get("input")
+        if stored is None:
+            raise ValueError("resume_from: the state file does not record an input stream (it was not written by "
+                             "train_and_evaluate)")
+        for k, v in stream.items():
+            if stored[k] != v:
+                raise ValueError("resume_from: the state was written with %s %r, this run has %r: the ranks' slices "
+                                 "of the input stream would differ" % (k, stored[k], v))
+    else:
+        model_dir = os.path.join(paths["model_dir"], "experiment_" + str(datetime.datetime.now()).replace(" ", "_"))
     if rank == 0:
         os.makedirs(model_dir, exist_ok=True)
-    trainer = Trainer(model, device=device, dist=dist)
+    trainer = Trainer(model, device=device, dist=dist, check_finite=check_finite)
+    if resumed is not None:
+        trainer.load_state(resumed)
+    start = trainer.iterations
     if paths.get("warm_start_path", None):
         trainer.set_params(warm_start(trainer.params(), load_params(paths["warm_start_path"]),
                                       match=opts.get("warm_start_match", "component")))
@@ -231,12 +280,16 @@ def train_and_evaluate(model, dist=None, device: int = 0, log_every: int = 10):
     make_input = gm.input_fn_native if native else gm.input_fn
     # data parallel: one shuffle seed for every rank (rank 0's), each rank reads its slice of
     # every global batch of world * batch_size samples
-    seed = int(np.random.SeedSequence().entropy % (2 ** 31))
+    if resumed is not None:
+        seed = int(resumed["meta"]["input"]["seed"])
+    elif opts.get("input_seed", None) is not None:
+        seed = int(opts["input_seed"])
+    else:
+        seed = int(np.random.SeedSequence().entropy % (2 ** 31))
     if world > 1:
         box = [seed]
         dist.broadcast_object_list(box, src=0)
         seed = int(box[0])
-    shuffle_train = str_to_bool(opts.get("shuffle_train_samples", "False"))
     # 8 builders keep a 512-sample synth50 batch stream ahead of the GPU step (bench --train
     # --fresh-batches: 22.2 ms/step fresh vs 22.5 resident)
     workers = int(opts.get("input_workers", str(min(8, len(os.sched_getaffinity(0))))))
@@ -244,12 +297,12 @@ def train_and_evaluate(model, dist=None, device: int = 0, log_every: int = 10):
     if native:   # the gathers, normalisation and host CSR builds of `workers` batches run in parallel
         source = gm.NativeInput(paths["train_dataset"], shuffle=shuffle_train, batch_size=batch_size, seed=seed,
                                 rank=rank, world=world)
-        prepared = trainer.prefetch(source.ids(), depth=depth, workers=workers, load=source.load)
+        prepared = trainer.prefetch(source.ids(skip=start), depth=depth, workers=workers, load=source.load)
     else:
         # the training stream shuffles with its own random.Random(seed): the same order on every
         # rank, whatever the eval generator (rank 0, main thread) draws from the global random
         prepared = trainer.prefetch(gm.input_fn(paths["train_dataset"], shuffle=shuffle_train, batch_size=batch_size,
-                                                rank=rank, world=world, seed=seed), depth=depth)
+                                                rank=rank, world=world, seed=seed, skip=start), depth=depth)
 
     def eval_batches():
         it = make_input(paths["eval_dataset"], shuffle=str_to_bool(opts.get("shuffle_eval_samples", "False")),
@@ -257,19 +310,33 @@ def train_and_evaluate(model, dist=None, device: int = 0, log_every: int = 10):
         for _ in range(eval_samples):
             yield next(it)
 
-    ckpts, history = [], []
+    ckpts, states, history = [], [], []
+    if resumed is not None:   # the files the run left take part in the pruning
+        states = [p for s, p in state_files(model_dir) if s <= start]
+        ckpts = [p for p in (os.path.join(model_dir, "ckpt-%d.safetensors" % s) for s, _ in state_files(model_dir)
+                             if s <= start) if os.path.exists(p)]
     last_save = last_eval = time.time()
     metrics = None
+
+    def keep_newest(files, path):
+        if path not in files:
+            files.append(path)
+        while len(files) > keep:
+            os.remove(files.pop(0))
 
     def checkpoint_and_eval(step, force=False):
         nonlocal last_save, last_eval, metrics
         if rank != 0:
+            trainer.check_now()   # every rank stops at the checkpoint that refuses a non-finite state
             return
+        st = trainer.state()      # raises NonFiniteTraining before anything is written
+        st["meta"]["input"] = dict(stream, seed=seed)
         path = os.path.join(model_dir, "ckpt-%d.safetensors" % step)
-        save_params(trainer.params(), path, {"step": str(step)})
-        ckpts.append(path)
-        while len(ckpts) > keep:
-            os.remove(ckpts.pop(0))
+        save_params({name: st["tensors"][name] for name, _, _ in trainer.engine.layout}, path, {"step": str(step)})
+        keep_newest(ckpts, path)
+        path = os.path.join(model_dir, "state-%d.safetensors" % step)
+        save_training_state(st, path)
+        keep_newest(states, path)
         last_save = time.time()
         if force or time.time() - last_eval >= throttle:
             metrics = dict(trainer.evaluate(eval_batches()), step=step)
@@ -281,18 +348,24 @@ def train_and_evaluate(model, dist=None, device: int = 0, log_every: int = 10):
 
     # the next batches are read and built on worker threads while the GPU runs the current step
     try:
-        for step in range(1, train_steps + 1):
-            logged = step % log_every == 0 or step == 1
+        for step in range(start + 1, train_steps + 1):
+            logged = step % log_every == 0 or step == start + 1
             # the loss reaches the host only on the logged steps: the others are enqueued without a
             # wait, so the next batch's host work overlaps this step on the GPU
             out = trainer.train_prepared(*next(prepared), want_loss=logged)
             if rank == 0 and logged:
                 log.warning("IGNNITION: step %d  Loss %.6g  Regularization loss %.6g  Total loss %.6g", step,
                             out["loss"], out["regularization_loss"], out["total_loss"])
-            if time.time() - last_save >= save_secs:
+            if time.time() - last_save >= save_secs or (save_steps > 0 and step % save_steps == 0 and step < train_steps):
                 checkpoint_and_eval(step)
+        prepared.close()
+        checkpoint_and_eval(max(train_steps, start), force=True)
+    except NonFiniteTraining:
+        clean = latest_state(model_dir) if rank == 0 else None
+        log.error("IGNNITION: training went non-finite; no checkpoint is written.  The newest clean state file: %s",
+                  clean[0] if clean else "none")
+        raise
     finally:
         prepared.close()
-    checkpoint_and_eval(train_steps, force=True)
     return {"model_dir": model_dir, "final_metrics": metrics, "history": history, "checkpoints": list(ckpts),
             "trainer": trainer}

@@ -83,12 +83,14 @@ def _global_batches(stream, batch_size: int, rank: int, world: int):
         yield mine
 
 
-def input_fn(data_dir, shuffle=False, training=True, batch_size=1, repeat=True, rank=0, world=1, seed=None):
+def input_fn(data_dir, shuffle=False, training=True, batch_size=1, repeat=True, rank=0, world=1, seed=None, skip=0):
     """GM:102-198: generator -> normalization -> repeat -> batches of ``batch_size`` graphs.
     ``rank`` / ``world``: data-parallel slice of every global batch (``_global_batches``); the
     ranks must draw the same stream: pass the same ``seed`` on every rank, which gives the stream
     its own ``random.Random`` (reshuffled every epoch from it, untouched by any other draw of the
-    process).  ``seed=None`` shuffles with the global ``random``, as the reference does."""
+    process).  ``seed=None`` shuffles with the global ``random``, as the reference does.
+    ``skip``: drop this rank's first ``skip`` batches (a resumed run's position in a seeded stream);
+    the generator has to read and discard them."""
     mi = model_info
     feature_list = mi.get_all_features()
     adjacency_info = mi.get_adjecency_info()
@@ -115,7 +117,8 @@ def input_fn(data_dir, shuffle=False, training=True, batch_size=1, repeat=True, 
             if not repeat or n == 0:
                 return
 
-    for batch in _global_batches(stream(), batch_size, rank, world):
+    import itertools
+    for batch in itertools.islice(_global_batches(stream(), batch_size, rank, world), int(skip), None):
         if training:
             yield [b[0] for b in batch], [b[1] for b in batch]
         else:
@@ -126,8 +129,9 @@ class NativeInput:
     """input_fn on the native reader (ignnition_amd.dataset), in two halves so that an input
     pipeline can run the second on worker threads:
 
-    * ``ids()``: the sample-id stream (one repeated stream, reshuffled every epoch with ``seed``,
-      the same on every data-parallel rank) cut into this rank's batches (``_global_batches``);
+    * ``ids(skip=0)``: the sample-id stream (one repeated stream, reshuffled every epoch with ``seed``,
+      the same on every data-parallel rank) cut into this rank's batches (``_global_batches``), from
+      its ``skip``-th batch on (a resumed run's position: only ids are drawn, nothing is read);
     * ``load(ids)``: the native reader's gather (thread safe) and the normalisation functions,
       applied by name to each feature's graph-concatenated array and to the labels (the same
       values as the per-sample call for elementwise functions, those of the examples).  Returns
@@ -147,7 +151,8 @@ class NativeInput:
         self.rng = np.random.default_rng(seed)
         self.rank, self.world = rank, world
 
-    def ids(self):
+    def ids(self, skip: int = 0):
+        import itertools
         n = len(self.ds)
         if n == 0:
             return
@@ -158,7 +163,7 @@ class NativeInput:
                 if not self.repeat:
                     return
 
-        yield from _global_batches(id_stream(), self.batch_size, self.rank, self.world)
+        yield from itertools.islice(_global_batches(id_stream(), self.batch_size, self.rank, self.world), int(skip), None)
 
     def load(self, ids):
         # integer keys as int32 (the batch build reads them at that width: half the gather's bytes)

@@ -17,6 +17,10 @@
   for what is not lowered.
 * data parallel: with torch.distributed initialised, every rank trains on its own batches and
   the gradient is averaged with one all-reduce (RCCL on GPUs) before the update.
+* resuming: ``Trainer.state()`` / ``load_state()`` carry the parameters, the optimizer's slots by
+  parameter name, ``iterations`` and the dropout seed, so a new Trainer continues a run bit for bit
+  (the Estimator restores the same from model_dir); ``check_finite`` counts NaN / Inf gradient values
+  on the GPU (``ign_nonfinite_count``) and raises NonFiniteTraining (the Estimator's NanTensorHook).
 * eval metrics (GM:755-785): label/prediction mean, MAE, MRE and the batch-mean r-squared
   (GM:201-216), after denormalisation, plus the mean loss.
 """
@@ -188,8 +192,106 @@ def host_loss(kind: int, p, y) -> float:
     return float(np.mean(t))
 
 
+class NonFiniteTraining(FloatingPointError):
+    """A NaN or Inf reached the gradient, the loss, the parameters or an optimizer slot (the
+    Estimator's NanTensorHook).  The device counter is read only where the host waits anyway, so the
+    first bad step lies in ``first_possible_step .. detected_step``: the step after the last clean
+    reading, and the step the host had reached when it read the counter."""
+
+    def __init__(self, what: str, first_possible_step: int, detected_step: int):
+        super().__init__("training went non-finite: %s (first possible step %d, detected at step %d)"
+                         % (what, first_possible_step, detected_step))
+        self.first_possible_step, self.detected_step = int(first_possible_step), int(detected_step)
+
+
+STATE_FORMAT = 1
+_GOLDEN = 0x9E3779B97F4A7C15
+
+
+def slot_names(optimizer: str, hyper: dict) -> list:
+    """Keras' slot names of ``optimizer``'s buffers, in ign_optimizer_num_slots' order."""
+    if optimizer in ("Adam", "Adamax"):
+        return ["m", "v"]
+    if optimizer == "SGD":
+        return ["momentum"] if hyper.get("momentum", 0.0) > 0 else []
+    if optimizer == "RMSprop":   # the engine's order: rms, then mg (centered), then momentum
+        return ["rms"] + (["mg"] if hyper.get("centered") else []) + (["momentum"] if hyper.get("momentum", 0.0) > 0 else [])
+    if optimizer == "Adagrad":
+        return ["accumulator"]
+    if optimizer == "Adadelta":
+        return ["accum_grad", "accum_var"]
+    raise UnsupportedModel("optimizer %r is not lowered" % (optimizer,))
+
+
+def cut_flat(flat, layout, suffix: str = "") -> dict:
+    """A flat buffer in the plan's parameter layout ([(name, shape, offset)], ``Engine.layout``) ->
+    {name + suffix: tensor}; the alignment gaps between the tensors are dropped."""
+    flat = np.asarray(flat)
+    return {name + suffix: flat[off:off + int(np.prod(shape))].reshape(shape).copy() for name, shape, off in layout}
+
+
+def fill_flat(tensors: dict, layout, n: int, fill: float = 0.0, suffix: str = "") -> np.ndarray:
+    """The inverse of ``cut_flat``: a flat float32 buffer of ``n`` values, the gaps holding ``fill``."""
+    flat = np.full(n, fill, np.float32)
+    for name, shape, off in layout:
+        flat[off:off + int(np.prod(shape))] = np.asarray(tensors[name + suffix], np.float32).reshape(-1)
+    return flat
+
+
+def state_meta(options: LearningOptions, iterations: int, dropout_seed: int) -> dict:
+    """The metadata of a training state: what ``unpack_state`` holds a loading run to."""
+    return {"format": STATE_FORMAT, "iterations": int(iterations), "dropout_seed": int(dropout_seed),
+            "optimizer": options.optimizer, "hyper": dict(options.hyper), "slot_init": float(options.slot_init),
+            "loss": options.loss}
+
+
+def pack_state(params: dict, slots: list, options: LearningOptions, layout, iterations: int, dropout_seed: int) -> dict:
+    """{"tensors", "meta"} from the named parameters and the optimizer's flat slot buffers (host arrays
+    in ``layout``): each slot is cut into ``<param name>/<Optimizer>/<slot>`` tensors."""
+    tensors = {name: np.asarray(params[name], np.float32) for name, _, _ in layout}
+    for slot, flat in zip(slot_names(options.optimizer, options.hyper), slots):
+        tensors.update(cut_flat(flat, layout, "/%s/%s" % (options.optimizer, slot)))
+    return {"tensors": tensors, "meta": state_meta(options, iterations, dropout_seed)}
+
+
+def unpack_state(state: dict, options: LearningOptions, layout, n: int):
+    """(parameters, flat slot buffers) of a training state for a run with ``options`` and the plan
+    ``layout`` of ``n`` values (gaps hold the optimizer's slot_init).  ValueError when the state is
+    another optimizer's or differs in a hyper-parameter, lacks a tensor or has one too many, or holds a
+    tensor of another shape (what the reference's Saver.restore refuses too)."""
+    meta, tensors = state["meta"], state["tensors"]
+    if meta.get("format") != STATE_FORMAT:
+        raise ValueError("load_state: state format %r, this version reads format %d" % (meta.get("format"), STATE_FORMAT))
+    if meta["optimizer"] != options.optimizer:
+        raise ValueError("load_state: the state was trained with optimizer %s, the model description names %s"
+                         % (meta["optimizer"], options.optimizer))
+    if meta["loss"] != options.loss:
+        raise ValueError("load_state: the state was trained with loss %s, the model description names %s"
+                         % (meta["loss"], options.loss))
+    for k in sorted(set(meta["hyper"]) | set(options.hyper)):
+        if k not in meta["hyper"] or k not in options.hyper or meta["hyper"][k] != options.hyper[k]:
+            raise ValueError("load_state: hyper-parameter %s is %r in the state and %r in the model description"
+                             % (k, meta["hyper"].get(k), options.hyper.get(k)))
+    suffixes = [""] + ["/%s/%s" % (options.optimizer, s) for s in slot_names(options.optimizer, options.hyper)]
+    want = {name + sfx: tuple(shape) for sfx in suffixes for name, shape, _ in layout}
+    missing = sorted(set(want) - set(tensors))
+    if missing:
+        raise ValueError("load_state: the state lacks tensor(s) %s" % ", ".join(missing))
+    extra = sorted(set(tensors) - set(want))
+    if extra:
+        raise ValueError("load_state: the state holds tensor(s) the model does not have: %s" % ", ".join(extra))
+    for name, shape in want.items():
+        if tuple(np.shape(tensors[name])) != shape:
+            raise ValueError("load_state: %s has shape %s in the state, the model needs %s"
+                             % (name, tuple(np.shape(tensors[name])), shape))
+    params = {name: np.asarray(tensors[name], np.float32) for name, _, _ in layout}
+    slots = [fill_flat(tensors, layout, n, meta["slot_init"], sfx) for sfx in suffixes[1:]]
+    return params, slots
+
+
 class Trainer:
-    def __init__(self, model_info, params: dict | None = None, device: int = 0, seed: int = 0, dist=None):
+    def __init__(self, model_info, params: dict | None = None, device: int = 0, seed: int = 0, dist=None,
+                 check_finite: bool = False):
         lo = learning_options(model_info)   # refuses what is not lowered before torch or the GPU are touched
         import torch
         self.torch = torch
@@ -212,9 +314,15 @@ class Trainer:
         self.dist = dist
         self.iterations = 0
         # the Dropout mask stream: the trainer's seed mixed with the data-parallel rank (ranks draw
-        # different masks); the step number is ``iterations``, so a run resumed at step k redraws step k's
-        rank = dist.get_rank() if dist is not None and dist.is_initialized() else 0
-        self.dropout_seed = (int(seed) + 0x9E3779B97F4A7C15 * rank) & 0xFFFFFFFFFFFFFFFF
+        # different masks); the step number is ``iterations``, so a run resumed at step k (load_state
+        # restores both) redraws step k's
+        self._rank = dist.get_rank() if dist is not None and dist.is_initialized() else 0
+        self._set_dropout_seed(seed)
+        # check_finite: every step adds its gradient's NaN / Inf count to one device counter
+        # (ign_nonfinite_count, enqueued, no wait); the host reads it where it waits anyway
+        self.check_finite = bool(check_finite)
+        self.nonfinite = torch.zeros(1, dtype=torch.int32, device=dev) if self.check_finite else None
+        self._clean_through = 0   # the counter read zero with this many steps enqueued
         # IGN_STEP_PROF=1: host seconds per phase of train_prepared (bench.py --fresh-batches reports them)
         self.step_prof = (dict.fromkeys(("forward_enqueue", "loss_wait", "backward_enqueue", "close", "l2_wait",
                                          "steps"), 0.0) if os.environ.get("IGN_STEP_PROF") == "1" else None)
@@ -223,6 +331,25 @@ class Trainer:
     @property
     def engine(self):
         return self.model.engine
+
+    def _set_dropout_seed(self, base: int):
+        """``base``: the seed every rank was given (what a state file stores); the rank is mixed in."""
+        self.base_dropout_seed = int(base) & 0xFFFFFFFFFFFFFFFF
+        self.dropout_seed = (int(base) + _GOLDEN * self._rank) & 0xFFFFFFFFFFFFFFFF
+
+    def _check_counter(self, detected_step: int):
+        """Read the gradient counter (a host wait: call it where the stream is waited for anyway)."""
+        if not self.check_finite:
+            return
+        bad = int(self.nonfinite.item()) & 0xFFFFFFFF
+        if bad:
+            raise NonFiniteTraining("%d NaN / Inf gradient value(s)" % bad, self._clean_through + 1, detected_step)
+        self._clean_through = self.iterations
+
+    def check_now(self):
+        """Wait for the enqueued steps and raise NonFiniteTraining if one of their gradients held a NaN
+        or Inf (nothing without ``check_finite``): for the ranks that do not call ``state()``."""
+        self._check_counter(self.iterations)
 
     def _labels(self, labels):
         y = np.concatenate([np.asarray(l, np.float32).reshape(-1) for l in labels])
@@ -277,6 +404,11 @@ class Trainer:
             if tick:
                 t2 = tick()
                 prof["loss_wait"] += t2 - t1
+            if self.check_finite and want_loss:
+                # the stream was just waited for: the counter holds every earlier step's gradient
+                self._check_counter(self.iterations + 1)
+                if not math.isfinite(loss):
+                    raise NonFiniteTraining("the loss is %r" % loss, self.iterations + 1, self.iterations + 1)
             # sum(model.losses) is part of this step's total loss (GM:749-753): read at the parameters the
             # step starts from, before the update below (the stream is idle here, the loss was just read)
             reg = self.engine.l2_loss() if want_loss else None
@@ -296,6 +428,8 @@ class Trainer:
                 else:                                   # RCCL over xGMI
                     self.dist.all_reduce(self.grads)
                 self.grads /= self.dist.get_world_size()
+            if self.check_finite:
+                self.engine.nonfinite_count(self.grads, self.nonfinite)
             lr = self.lr(self.iterations)
             self.engine.optimizer_step(self.options.desc, self.grads, self.slots, self.iterations, lr)
             self.iterations += 1
@@ -352,6 +486,39 @@ class Trainer:
 
     def set_params(self, params: dict):
         self.model.set_params(params)
+
+    def state(self) -> dict:
+        """Everything a new Trainer of the same description needs to continue this run bit for bit
+        (``load_state``): {"tensors": the parameters as ``params()`` gives them and every optimizer slot
+        cut by the plan's parameter layout into ``<param name>/<Optimizer>/<slot>`` tensors (no
+        alignment gaps), "meta": ``iterations``, the dropout seed before the rank is mixed in, the
+        optimizer with its hyper-parameters and slot_init, the loss}.  Waits for the enqueued steps; with
+        ``check_finite`` it raises NonFiniteTraining rather than return a state whose run saw a NaN or Inf
+        gradient or whose host copies hold one."""
+        params = self.params()                          # waits for the stream
+        slots = [s.cpu().numpy() for s in self.slots]
+        self._check_counter(self.iterations)
+        st = pack_state(params, slots, self.options, self.engine.layout, self.iterations, self.base_dropout_seed)
+        bad = [k for k, v in st["tensors"].items() if not np.isfinite(v).all()] if self.check_finite else []
+        if bad:
+            raise NonFiniteTraining("NaN / Inf in %s" % ", ".join(bad[:4]) + (" ..." if len(bad) > 4 else ""),
+                                    self._clean_through + 1, self.iterations)
+        return st
+
+    def load_state(self, state: dict):
+        """Continue the run ``state`` was taken from: the parameters, every slot tensor written back at
+        its offset of this plan's layout (gaps get slot_init), ``iterations`` and the dropout seed.
+        ValueError (``unpack_state``) for a state of another optimizer, hyper-parameter, tensor set or
+        shape; nothing is changed then."""
+        params, slots = unpack_state(state, self.options, self.engine.layout, self.engine.n_params)
+        self.set_params(params)
+        for dst, flat in zip(self.slots, slots):   # in place: m and v stay the Adam slots
+            dst.copy_(self.torch.from_numpy(flat))
+        self.iterations = int(state["meta"]["iterations"])
+        self._set_dropout_seed(state["meta"]["dropout_seed"])
+        if self.check_finite:
+            self.nonfinite.zero_()
+        self._clean_through = self.iterations
 
 
 def builder_cpus(workers: int) -> list:

@@ -563,6 +563,14 @@ int  ign_optimizer_num_slots(const ign_optimizer_desc* desc, int32_t* n, float* 
  * departs from Keras only where Keras would produce NaN. */
 int  ign_optimizer_step(ign_plan* plan, const ign_optimizer_desc* desc, const float* grads, float* const* slots,
                         int32_t n_slots, int64_t iteration, float lr);
+/* The non-finite guard of a training loop (the Estimator's NanTensorHook): enqueues, on the plan's
+ * stream, a kernel that adds to *dev_count the number of NaN and +-Inf values among dev[0..n), e.g.
+ * the gradient between ign_backward and ign_optimizer_step.  dev and dev_count are device memory, dev
+ * any 4-byte-aligned address; the caller zeroes the counter and reads it where it waits for the
+ * stream anyway, there is no host wait here.  Calls into one counter accumulate, and the count is an
+ * integer sum, the same whatever the order.  n == 0 returns IGN_OK without a launch; a null pointer,
+ * a negative n or a misaligned pointer is IGN_ERR_INVALID. */
+int  ign_nonfinite_count(ign_plan* plan, const float* dev, int64_t n, uint32_t* dev_count);
 /* Copy the current parameters (flat layout) to host. */
 int  ign_plan_get_params(ign_plan* plan, float* host_out);
 
