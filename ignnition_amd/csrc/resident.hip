@@ -10,6 +10,9 @@
 //   LDS: path states [P][36] (or, for graphs whose paths do not fit, the batch's state buffer in
 //        HBM / L2), union-row states [U][36], the projected table [U + 1][100] (the hole row last),
 //        the sum MPs' CSR by union row (or, when it does not fit, read from L2), U's fp16 pieces;
+//   set-up: the union rows' [features | zeros] as whole float4s, barrier, the index arrays as 16-byte
+//        vectors, the iteration-0 projection, the path states in chunks that the waves claim (those
+//        without a projection tile first), barrier;
 //   per iteration: phase A, the ordered update (seq_gru_h16's tile loop over the graph's paths
 //        sorted by length; projected rows and states from LDS), barrier, phase B, the sum updates
 //        over all 16 waves: B1 the message sums (high in-degree rows: sum_seg_kernel's wave per
@@ -77,6 +80,53 @@ template <bool G> __device__ __forceinline__ void stp4(float* p, f4 v) {
   else lds4w(p, v);
 }
 
+// float4 column c4 of a state row's [features | zeros]: only the lanes whose column overlaps [0, F) load,
+// each element on its own (F is any run-time width: a feature row has no alignment), as global_* loads
+__device__ __forceinline__ f4 feat4(const float* row, int F, int c4) {
+  const __attribute__((address_space(1))) float* f = (const __attribute__((address_space(1))) float*)row + 4 * c4;
+  f4 v = {0, 0, 0, 0};
+#pragma unroll
+  for (int e = 0; e < 4; ++e)
+    if (4 * c4 + e < F) v[e] = f[e];
+  return v;
+}
+
+// The set-up's copy of one contiguous index array (n elements of T) from global memory into LDS: the
+// elements from the source's first 16-byte boundary on as whole vectors (a graph's arrays start
+// wherever the graphs before it end), one per thread and trip, and the fewer than 2 * E elements in
+// front of and behind them one by one.  first() only issues the first trip's load, so that several
+// arrays' loads are in flight before finish() waits for one
+template <typename T> struct IdxCopy {
+  static constexpr int E = 16 / sizeof(T);
+  const __attribute__((address_space(1))) T* s;
+  T* d;
+  int n, h, nv;   // elements; those in front of the first whole vector; whole vectors
+  __device__ __forceinline__ IdxCopy(const T* src, T* dst, int64_t cnt)
+      : s((const __attribute__((address_space(1))) T*)src), d(dst), n((int)cnt) {
+    h = (int)((0 - reinterpret_cast<uintptr_t>(src) / sizeof(T)) & (E - 1));
+    h = h < n ? h : n;
+    nv = (n - h) / E;
+  }
+  __device__ __forceinline__ u4v load(int i) const {
+    return *reinterpret_cast<const __attribute__((address_space(1))) u4v*>(s + h + E * i);
+  }
+  __device__ __forceinline__ void store(int i, u4v v) const {
+    struct Vec { T e[E]; };
+    const Vec t = __builtin_bit_cast(Vec, v);
+#pragma unroll
+    for (int e = 0; e < E; ++e) d[h + E * i + e] = t.e[e];   // (the LDS side is only T-aligned)
+  }
+  __device__ __forceinline__ u4v first(int tid) const { return tid < nv ? load(tid) : u4v{0, 0, 0, 0}; }
+  __device__ __forceinline__ void finish(int tid, u4v v) const {
+    if (tid < nv) store(tid, v);
+    for (int i = tid + 64 * kW; i < nv; i += 64 * kW) store(i, load(i));
+    if (tid < n - E * nv) {   // the head's h elements, then the tail's
+      const int k = tid < h ? tid : tid + E * nv;
+      d[k] = s[k];
+    }
+  }
+};
+
 // the three exact bf16 pieces of a lane's 8 values in the chained B layout (kernels_bf.hip)
 __device__ __forceinline__ void split_frags1(const f4* v, bf8 (&f)[3][1]) {
   u4v w0, w1, w2;
@@ -123,12 +173,26 @@ __device__ __forceinline__ void project_row(const ResidentArgs& a, const f4 (&hn
 }
 
 // the iteration-0 projected row as project_kernel computes it (f32 MFMA, x.W' over k-steps of 1 on
-// the bias) so the resident forward reproduces the batched forward's bits
+// the bias) so the resident forward reproduces the batched forward's bits.  AHEAD (the set-up's call,
+// where registers are free): the tile's 48 fragments -- a lane's four k-steps of a fragment group are one
+// float4 -- are all loaded in front of the first MFMA, one exposed round trip instead of one per k-step
+// group; the MFMAs, their order and operands are the same
+template <bool AHEAD>
 __device__ __forceinline__ void project_row_f32(const ResidentArgs& a, const f4 (&xv)[2], float* tab, int ll,
                                                 bool valid, int lane, int g, float* gsave = nullptr) {
   int lofs = lane;
   asm volatile("" : "+v"(lofs));
   constexpr int H = 32, NT = 2, KX = 32 / 4;
+  f4 w[AHEAD ? KX / 4 : 1][3][NT];
+  if constexpr (AHEAD) {
+    const __attribute__((address_space(1))) f4* wf = (const __attribute__((address_space(1))) f4*)a.proj_Wf;
+#pragma unroll
+    for (int q = 0; q < KX / 4; ++q)
+#pragma unroll
+      for (int G = 0; G < 3; ++G)
+#pragma unroll
+        for (int t = 0; t < NT; ++t) w[q][G][t] = wf[frag_idx(G * NT + t, 4 * q, KX, lofs) >> 2];
+  }
   f4 acc[3][NT];
 #pragma unroll
   for (int G = 0; G < 3; ++G)
@@ -140,7 +204,12 @@ __device__ __forceinline__ void project_row_f32(const ResidentArgs& a, const f4 
 #pragma unroll
     for (int G = 0; G < 3; ++G)
 #pragma unroll
-      for (int t = 0; t < NT; ++t) acc[G][t] = MFMA(a.proj_Wf[frag_idx(G * NT + t, s, KX, lofs)], xb, acc[G][t]);
+      for (int t = 0; t < NT; ++t) {
+        float wv;
+        if constexpr (AHEAD) wv = w[s >> 2][G][t][s & 3];
+        else wv = a.proj_Wf[frag_idx(G * NT + t, s, KX, lofs)];
+        acc[G][t] = MFMA(wv, xb, acc[G][t]);
+      }
   }
   if (valid) {
 #pragma unroll
@@ -214,7 +283,10 @@ __global__ __launch_bounds__(64 * kW) void resident_forward_kernel(ResidentArgs 
   __shared__ h8 su[NF * 64];
   __shared__ float sbn[kW][H];
   __shared__ float sbias[H];
-  __shared__ int sctr[2];   // phase A's tile counters (alternate iterations)
+  __shared__ int sctr[2];   // phase A's tile counters (alternate iterations).  sctr[1] also counts the set-up's
+                            // path-state chunks: zeroed with sctr[0] in front of the set-up's first barrier,
+                            // last incremented in front of its second, and phase A's iteration 0 resets it
+                            // behind that barrier, as it resets the next iteration's counter anyway
   extern __shared__ float dyn[];
   const int gph = a.gorder ? a.gorder[blockIdx.x] : (int)blockIdx.x;   // longest graphs first (LPT)
   const int64_t p0 = a.path_off[gph], P = a.path_off[gph + 1] - p0;
@@ -249,32 +321,49 @@ __global__ __launch_bounds__(64 * kW) void resident_forward_kernel(ResidentArgs 
     for (int e = tid; e < NF * 64; e += 64 * kW) dst[e] = src[e];
   }
   const int es = __float_as_int(reinterpret_cast<const float*>(a.Uh)[(int64_t)NF * 64 * 4]);
-  // GM:396-400: state_0 = [features | zeros] (SAVE: path_ver[0] holds it already)
-  for (int64_t i = SAVE ? P * H : tid; i < P * H; i += 64 * kW) {
-    const int64_t r = i / H;
-    const int c = (int)(i - r * H);
-    hP[r * SPP + c] = c < a.path_F ? a.path_feat[(p0 + r) * a.path_F + c] : 0.f;
-  }
-  for (int64_t i = tid; i < U * H; i += 64 * kW) {
-    const int64_t r = i / H;
-    const int c = (int)(i - r * H);
-    const bool e1 = r >= L0;
-    const int F = e1 ? a.src_F[1] : a.src_F[0];
-    const float* f = e1 ? a.src_feat[1] + (s10 + r - L0) * F : a.src_feat[0] + (s00 + r) * F;
-    hL[r * SP + c] = c < F ? f[c] : 0.f;
+  // GM:396-400: state_0 = [features | zeros], one thread per (row, float4 column), a group of trips'
+  // loads in front of its stores.  The union rows first: the iteration-0 projection reads only them and
+  // the hole row, so the barrier in front of it waits for nothing else
+  const int nuit = (int)U * (H / 4);   // (local rows are 16-bit)
+  for (int i0 = tid; i0 < nuit; i0 += 2 * 64 * kW) {
+    f4 v[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int i = i0 + u * 64 * kW, r = i >> 3;
+      if (i < nuit) {
+        const bool e1 = r >= L0;
+        const int F = e1 ? a.src_F[1] : a.src_F[0];
+        v[u] = feat4(e1 ? a.src_feat[1] + (s10 + r - L0) * F : a.src_feat[0] + (s00 + r) * F, F, i & 7);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int i = i0 + u * 64 * kW;
+      if (i < nuit) lds4w(hL + (i >> 3) * SP + 4 * (i & 7), v[u]);
+    }
   }
   for (int i = tid; i < 3 * H; i += 64 * kW) tab[U * ST + i] = a.proj_b[i];   // the hole row: b' alone
+  __syncthreads();
+  // the sum MPs' CSR and the row order, then the message rows and the step codes: two arrays' first loads
+  // are issued before either is waited on (all four at once, or held across the projection, their
+  // descriptors spill scalar registers into vector ones: +2 VGPRs in the all-LDS form)
   {
     const int64_t u0 = a.urow_off[gph];
-    const int* gp = a.lmsg_ptr + u0 + gph;
-    for (int64_t i = tid; i <= U; i += 64 * kW) smp[i] = gp[i];
-    if constexpr (CL)
-      for (int64_t i = tid; i < M; i += 64 * kW) sms_l[i] = a.lmsg_src[ms0 + i];
-    for (int64_t i = tid; i < U; i += 64 * kW) slo[i] = a.lorder[u0 + i];
-    if constexpr (!PG)
-      for (int64_t i = tid; i < NC; i += 64 * kW) scd_l[i] = a.lcode[cd0 + i];
+    const IdxCopy<int> c_mp(a.lmsg_ptr + u0 + gph, smp, U + 1);
+    const IdxCopy<uint16_t> c_lo(a.lorder + u0, slo, U);
+    const u4v v_mp = c_mp.first(tid), v_lo = c_lo.first(tid);
+    c_mp.finish(tid, v_mp);
+    c_lo.finish(tid, v_lo);
   }
-  __syncthreads();
+  {
+    const IdxCopy<uint16_t> c_ms(a.lmsg_src + ms0, sms_l, CL ? M : 0);
+    const IdxCopy<uint16_t> c_cd(a.lcode + cd0, scd_l, PG ? 0 : NC);
+    u4v v_ms = {0, 0, 0, 0}, v_cd = {0, 0, 0, 0};
+    if constexpr (CL) v_ms = c_ms.first(tid);
+    if constexpr (!PG) v_cd = c_cd.first(tid);
+    if constexpr (CL) c_ms.finish(tid, v_ms);
+    if constexpr (!PG) c_cd.finish(tid, v_cd);
+  }
   const int64_t nut = (U + 15) / 16;   // union-row tiles of the projection
   // the first iteration's projected table
   for (int64_t k = wave; k < nut; k += kW) {
@@ -287,7 +376,30 @@ __global__ __launch_bounds__(64 * kW) void resident_forward_kernel(ResidentArgs 
     float* gs = nullptr;   // SAVE: the table of iteration 0, row of this union row
     if constexpr (SAVE)
       if (a.tab_save) gs = in_global(a.tab_save[0]) + tab_row(a, ll, L0, s00, s10) * 96;
-    project_row_f32(a, h, tab, ll, valid, lane, g, gs);
+    project_row_f32<true>(a, h, tab, ll, valid, lane, g, gs);
+  }
+  // the path states (SAVE: path_ver[0] holds them already), in chunks of 4 x 64 float4s that the waves
+  // claim from sctr[1] (see its declaration): a wave without a projection tile starts at once and takes
+  // the larger share, the others join when their tile is done
+  if constexpr (!SAVE) {
+    const int nitem = (int)P * (H / 4);
+    for (;;) {
+      int c = 0;
+      if (lane == 0) c = atomicAdd(&sctr[1], 1);
+      const int i0 = __builtin_amdgcn_readfirstlane(c) * (4 * 64) + lane;
+      if (i0 - lane >= nitem) break;
+      f4 v[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int i = i0 + 64 * u;
+        if (i < nitem) v[u] = feat4(a.path_feat + (p0 + (i >> 3)) * a.path_F, a.path_F, i & 7);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int i = i0 + 64 * u;
+        if (i < nitem) stp4<PG>(hP + (i >> 3) * SPP + 4 * (i & 7), v[u]);
+      }
+    }
   }
   if constexpr (SAVE)   // every saved table's hole row: the bias alone (one workgroup writes them)
     if (a.tab_save && gph == 0)
@@ -643,7 +755,7 @@ __global__ __launch_bounds__(64 * kW) void resident_forward_kernel(ResidentArgs 
         if constexpr (SAVE) {   // mp_project's projection (and the next iteration's saved table)
           float* gs = nullptr;
           if (a.tab_save && it + 1 < a.T) gs = in_global(a.tab_save[it + 1]) + tab_row(a, ll, L0, s00, s10) * 96;
-          project_row_f32(a, hn, tab, ll, valid, lane, g, gs);
+          project_row_f32<false>(a, hn, tab, ll, valid, lane, g, gs);
         }
         else project_row(a, hn, tab, ll, valid, lane, g);
       }
