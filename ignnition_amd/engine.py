@@ -947,6 +947,35 @@ class Batch:
             col += size
         return res
 
+    def forward_tangent(self, directions: dict):
+        """Forward-mode sensitivities (ign_forward_tangent): ``(pred, dpred)``, both ``[predictions,
+        units]``, where ``dpred = J . directions`` is the derivative of every prediction along one
+        direction of the input features, from one pass the shape of an inference forward.
+        ``directions``: ``{entity: values}``, the values as ``set_features`` takes them (a ``{feature
+        name: array}`` dict or one ``[rows, F]`` array), in terms of the normalised values the batch
+        was built from; an entity left out has a zero direction.  ``pred`` is an f32 evaluation of the
+        model that does not depend on the direction; the batch's own states and predictions are not
+        touched.  An unknown entity, an entity without features or a wrong shape is a ``ValueError``;
+        a model outside the tangent kernels' scope an ``EngineError`` that names the feature."""
+        p = self.engine.plan
+        ptrs = (C.c_void_p * len(p.entities))()
+        keep = []
+        for entity, values in directions.items():
+            e, rows, F = self._feature_entity(entity)
+            if F == 0:
+                raise ValueError("forward_tangent: entity %r has no features" % entity)
+            try:
+                v = feature_rows(p.features[e], rows, values)
+            except ValueError as err:
+                raise ValueError(str(err).replace("set_features:", "forward_tangent:", 1)) from None
+            keep.append(v)
+            ptrs[e] = v.ctypes.data_as(C.c_void_p)
+        pred = np.empty((self.predictions, self.output_units), np.float32)
+        dpred = np.empty_like(pred)
+        check(lib.ign_forward_tangent(self.handle, ptrs, len(p.entities), pred.ctypes.data_as(C.c_void_p),
+                                      dpred.ctypes.data_as(C.c_void_p)))
+        return pred, dpred
+
     # ---- what-if analysis: new per-edge parameters (params_<adj>) on the same graphs, their gradient
     def _edge_sources(self, adj: str):
         """(edges of the batch, param_dim, [(mp, source)]) of adjacency ``adj`` (edge_param_sources)."""

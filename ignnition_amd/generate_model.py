@@ -286,6 +286,28 @@ class ComnetModel:
             b.close()
         return pred, out
 
+    def directional_sensitivities(self, graphs, directions: dict):
+        """``(predictions, dpred)`` of a batch of graphs, the forward-mode counterpart of
+        ``sensitivities``: ``dpred[i]`` is the derivative of prediction ``i`` along ``directions``, one
+        ``{feature name: array [rows, size]}`` entry per input feature that moves (in batch row order,
+        as ``sensitivities`` returns its gradients; a feature left out does not move), in terms of the
+        normalised values the engine is fed.  One pass of ``Batch.forward_tangent``: no training
+        tables and no backward, whatever the number of predictions."""
+        names = {f: (ent, rows) for ent, feats in zip(self.plan.entities, self.plan.features) for f, rows in feats}
+        unknown = sorted(set(directions) - set(names))
+        if unknown:
+            raise ValueError("directional_sensitivities: unknown feature(s) %s (the model has %s)" % (unknown, sorted(names)))
+        b = self.batch(graphs)
+        try:
+            per_entity = {}
+            for ent, feats, rows in zip(self.plan.entities, self.plan.features, b.rows):
+                if any(f in directions for f, _ in feats):
+                    per_entity[ent] = {f: directions[f] if f in directions else np.zeros((rows, size), np.float32)
+                                       for f, size in feats}
+            return b.forward_tangent(per_entity)
+        finally:
+            b.close()
+
     def __call__(self, input: dict, training: bool = False) -> np.ndarray:
         """``ComnetModel.call`` (GM:384) for one graph: [P, units] predictions."""
         return self.batch([input]).forward()

@@ -472,6 +472,26 @@ int  ign_dropout_keep(uint64_t seed, int32_t site, uint32_t step, int64_t rows, 
  * path already carries the state gradients down to iteration 0. */
 int  ign_batch_set_features(ign_plan* plan, ign_batch* batch, int32_t entity, const float* rows);
 int  ign_batch_feature_gradients(ign_plan* plan, ign_batch* batch, int32_t entity, float* dev_out);
+/* ---- Forward-mode sensitivities (ABI 13 addition) -------------------------------------------------
+ * The other direction of the same what-if: one input direction, every output.  ign_forward_tangent
+ * runs the forward on dual numbers: every state row carries its derivative along the feature direction
+ * dfeat, through the MP loop and predict, and the call returns the predictions and dpred = J . dfeat in
+ * one pass the shape of an inference forward -- no training tables, nothing saved, no backward.
+ * dfeat[e] is [rows of entity e][F_e] floats (the columns in the plan's feature order, in terms of the
+ * values ign_batch_create was given), host or device memory, or NULL for a zero direction on that
+ * entity; n_ents must equal the plan's entity count.  pred and dpred are [predictions][units], host or
+ * device memory, either may be NULL; the call returns when both are written.  The primal runs on the
+ * f32-MFMA kernels (an f32 evaluation of the model, not ign_forward's bits); it does not depend on the
+ * direction, a zero direction gives dpred = 0 exactly, and a direction scaled by a power of two the
+ * scaled dpred bit for bit.  The batch is not written: its states, predictions and captured graph
+ * stay as the last forward left them, and the parameters are read as they are at the call.
+ * Covered: ordered / interleave / concat-axis-1 and plain sum MPs with direct_assignation messages,
+ * GRU cells at 16/16, 16/32, 32/16, 32/32 and 64/64 with or without ign_plan_set_cell_options, predict
+ * Dense stacks with every activation (a Dropout layer is the identity).  IGN_ERR_UNSUPPORTED, with a
+ * message that begins "forward tangent:" and names the feature: attention, convolution, concat on
+ * axis 2, message networks, readout operations before predict, LayerNormalization, a batch with halo
+ * rows, and a call between ign_forward_train(_begin) and the end of that forward's backward. */
+int  ign_forward_tangent(ign_batch* batch, const float* const* dfeat, int n_ents, float* pred, float* dpred);
 /* ---- Edge parameters of a live batch and their gradient (ABI 13 additions) -----------------------
  * The other input a what-if changes on fixed graphs: params_<adj>, which a message network of MP
  * source (mp, source) reads as edge_params.  Each such source owns one buffer [n_edges][param_dim];
