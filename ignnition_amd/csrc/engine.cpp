@@ -330,6 +330,10 @@ int ign::repack(ign_plan* p) {
       case PK_READOUT_H16: HIP_TRY(launch_pack_readout_h16(s[0], s[1], s[2], dst, j->a, j->b, j->c, st)); break;
       case PK_READOUT_H32: HIP_TRY(launch_pack_readout_h32(s[0], s[1], s[2], dst, j->a, j->b, j->c, st)); break;
       case PK_ATTN_VECTORS: HIP_TRY(launch_attn_vectors(s[0], s[1], s[2], j->a, dst, st)); break;
+      case PK_WIDE_U: HIP_TRY(launch_pack_wide(s[0], nullptr, dst, IGN_PACK_WIDE_U, st)); break;
+      case PK_WIDE_W: HIP_TRY(launch_pack_wide(s[0], nullptr, dst, IGN_PACK_WIDE_W, st)); break;
+      case PK_WIDE_WU: HIP_TRY(launch_pack_wide(s[0], s[1], dst, IGN_PACK_WIDE_WU, st)); break;
+      case PK_WIDE_B: HIP_TRY(launch_pack_wide(s[0], nullptr, dst, IGN_PACK_WIDE_B, st)); break;
     }
   }
   return IGN_OK;
@@ -633,6 +637,15 @@ int ign_batch_create(ign_plan* p, const ign_batch_desc* d, ign_batch** out) {
   b->plan = p;
   b->pool = p->pool;
   b->G = G;
+  for (const CellP& cp : p->cells) {   // a 128-wide plan: whole batches only, and the LDS limit before any capture
+    if (!cp.wide()) continue;
+    for (int e = 0; e < E && d->halo_rows; ++e)
+      if (d->halo_rows[e] > 0)
+        return fail(IGN_ERR_UNSUPPORTED, "a batch with halo rows (an edge-cut partition) on a plan with a 128-wide GRU "
+                    "cell: the 128-wide updates run over whole batches only");
+    HIP_TRY(gru_wide_prepare_device());
+    break;
+  }
   BatchShape sh;
   if ((rc = lower_batch_shape(E, p->n_adj, p->n_il, p->mps, d, &sh))) return rc;
   b->rows = sh.rows;

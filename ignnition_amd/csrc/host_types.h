@@ -71,6 +71,9 @@ struct CellP {
   int64_t pk_wh = -1;             // split-fp16 input-kernel fragments + scale (sum variant 8, DIN = H = 64)
   int64_t pk_uh = -1;             // split-fp16 recurrent-kernel fragments + scale (seq variants 6/7)
   int64_t pk_uth = -1;            // backward: split-fp16 U fragments for dh = du . U^T (H = 32)
+  int64_t pk_wu = -1;             // a wide cell (128 / 128): [W ; U] in K chunks; its pk_w / pk_u / pk_b hold
+                                  // gru_wide.hip's W chunks, U slices and the biases [4][H]
+  bool wide() const { return pk_wu >= 0; }
   bool used = false;
   // ign_plan_set_cell_options (Keras GRUCell defaults).  A cell with any other value is a non-default
   // cell: unscaled pack_gru fragments, none of the split pieces above, the generalised kernels

@@ -8,6 +8,9 @@
 inline bool gru_shape_supported(int din, int h) {
   return ((din == 16 || din == 32) && (h == 16 || h == 32)) || (din == 64 && h == 64);
 }
+// DIN = H = 128 on gru_wide.hip's workgroup-split kernels: default cells, ordered-family and plain sum
+// MPs, inference only.  The lowering admits a shape that either predicate admits.
+inline bool gru_wide_supported(int din, int h) { return din == 128 && h == 128; }
 // the activation codes (ignmp.h's IGN_ACT_*, kernels.h's IGN_K_ACT_*): a launcher refuses any other
 inline bool act_code_ok(int a) { return a >= 0 && a <= 9; }
 // linear, relu, selu, sigmoid, tanh: the codes every templated kernel is instantiated for.  elu ..
@@ -63,6 +66,10 @@ inline bool dense_fwd_supported(int K, int M) {
 inline int64_t pack_gru_w_floats(int din, int H) { return 3LL * din * H; }   // pack_gru's W / pack_a of W, U
 inline int64_t pack_gru_u_floats(int H) { return 3LL * H * H; }
 inline int64_t pack_gru_b_floats(int H) { return 4LL * H; }                  // the combined biases [4][H]
+// gru_wide.hip's fragments (0: not a wide shape): U as eight per-wave slices, W and [W ; U] as 16-row K chunks
+inline int64_t pack_wide_u_floats(int H) { return H == 128 ? 3LL * H * H : 0; }
+inline int64_t pack_wide_w_floats(int din, int H) { return gru_wide_supported(din, H) ? 3LL * din * H : 0; }
+inline int64_t pack_wide_wu_floats(int din, int H) { return gru_wide_supported(din, H) ? 3LL * (din + H) * H : 0; }
 inline int64_t pack_u_bf16_floats(int H) { return (H == 32 || H == 64) ? 9LL * H * H / 2 : 0; }
 inline int64_t pack_u_f16_floats(int H) { return (H == 32 || H == 64) ? 3LL * H * H + 64 : 0; }
 inline int64_t pack_ut_f16_floats(int H) { return H == 32 ? 3LL * H * H + 64 : 0; }

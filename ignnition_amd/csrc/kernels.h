@@ -167,6 +167,24 @@ struct SumSegArgs {
 };
 hipError_t launch_sum_seg(const SumSegArgs& args, int din, hipStream_t st);
 
+// DIN = H = 128, default cells (gru_wide.hip; gru_wide_supported): the row tile's work split over the
+// waves of a workgroup by unit tile, f32 MFMA.
+enum { IGN_PACK_WIDE_U = 0, IGN_PACK_WIDE_W = 1, IGN_PACK_WIDE_WU = 2, IGN_PACK_WIDE_B = 3 };
+// U in the per-wave slice order (M = U), W or [W ; U] (M = W, M2 = U) in the K-chunk order, the combined
+// pre-scaled biases [4][128] (M = the bias tensor [2][384]); floats: pack_wide_*_floats
+hipError_t launch_pack_wide(const float* M, const float* M2, float* out, int what, hipStream_t st);
+// the kernels' dynamic-LDS limit, once per device: call before any launch or stream capture
+hipError_t gru_wide_prepare_device();
+// seq_gru_w128: the ordered update; args.Up from IGN_PACK_WIDE_U (order / len / step_ptr / step_code form)
+hipError_t launch_seq_gru_w128(const SeqGruArgs& args, hipStream_t st);
+// gemm_w128 PROJECT: launch_project's table rows at 128 / 128; Wk from IGN_PACK_WIDE_W
+hipError_t launch_project_w128(const float* x, int64_t n, const float* Wk, const float* bp, float* out, float* bias_row,
+                               hipStream_t st);
+// gemm_w128 SUM_GRU: aggregation (the destination's CSR order) and the GRU step in one launch; args.Wp
+// from IGN_PACK_WIDE_WU, args.Up unused.  A plain sum only: hipErrorInvalidValue with message weights,
+// a convolution kernel, a save or a projection target
+hipError_t launch_sum_gru_w128(const SumGruArgs& args, hipStream_t st);
+
 // Graph-resident forward (resident.hip): one workgroup per graph runs the T iterations of one ordered
 // MP into the "path" entity from S <= 2 source entities ("links"; Q-size: links and nodes, the
 // interleave) and, for each source entity, one sum MP from the paths back to it (RouteNet: S = 1),

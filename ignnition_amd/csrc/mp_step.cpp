@@ -75,6 +75,10 @@ int mp_project(ign_plan* p, const MPP& mp, const MPB& mb, const float* const* sr
     const float* wp = p->d_packed + (mp.feature_concat ? mp.pk_slice[s] : cp.pk_w);
     tm.begin(K_PROJECT, 2.0 * rs * mp.din * W3, (double)rs * (4.0 * mp.din + 4.0 * W3), 0,
              (double)((rs + 15) / 16) * 3 * (cp.H / 16) * (sdin / 4) * kMfmaF32Flops);
+    if (cp.wide())   // 128 / 128: gemm_w128 PROJECT on the W chunks
+      HIP_TRY(launch_project_w128(src[s], rs, wp, p->d_packed + cp.pk_b, mb.d_table + mb.src_off[s] * W3,
+                                  s == 0 ? mb.d_table + mb.zero_row * W3 : nullptr, p->stream));
+    else
     HIP_TRY(launch_project(src[s], rs, wp, p->d_packed + cp.pk_b, mb.d_table + mb.src_off[s] * W3,
                            s == 0 ? mb.d_table + mb.zero_row * W3 : nullptr, sdin, cp.H, p->stream));
     tm.end();
@@ -172,6 +176,13 @@ int mp_forward(ign_plan* p, ign_batch* b, int mi, int part, MpStates s, const Mp
     if (cp.pk_ubf >= 0) a.Ubf = p->d_packed + cp.pk_ubf;
     if (cp.pk_uh >= 0) a.Uh = p->d_packed + cp.pk_uh;
     a.hdr = mb.d_seq_hdr;
+    if (cp.wide()) {   // 128 / 128: seq_gru_w128, U in the workgroup's registers (3 gates x 8 unit tiles x 32 k-steps)
+      if (saving) return fail(IGN_ERR_UNSUPPORTED, "the 128-wide ordered update saves no states (inference only)");
+      tm.begin(K_SEQ, mb.flops, mb.bytes, 0, (double)mb.wave_steps * 3 * (cp.H / 16) * (cp.H / 4) * kMfmaF32Flops);
+      HIP_TRY(launch_seq_gru_w128(a, st));
+      tm.end();
+      return IGN_OK;
+    }
     if (!cp.is_default()) {   // a cell with options: seq_gru_cell (f32 MFMA; reset_after false: a second K = H sweep)
       tm.begin(K_SEQ, mb.flops, mb.bytes, 0,
                (double)mb.wave_steps * 3 * (cp.H / 16) * (cp.H / 4) * kMfmaF32Flops);
@@ -205,6 +216,18 @@ int mp_forward(ign_plan* p, ign_batch* b, int mi, int part, MpStates s, const Mp
     tm.end();
   }
   if (count <= 0) return IGN_OK;
+  if (cp.wide()) {   // 128 / 128: gemm_w128 SUM_GRU sums in the kernel (the CSR order; batch_lower builds neither
+                     // windowed nor segmented tables at this width) and contracts [x | h] with [W ; U]
+    if (mp.aggr != IGN_AGGR_SUM || saving || part != IGN_PART_ALL)
+      return fail(IGN_ERR_UNSUPPORTED, "the 128-wide sum update is a plain sum over the whole batch (inference only)");
+    SumGruArgs w{s.hin, s.hout, s.src, mb.d_order, mb.d_msg_ptr, mb.d_msg_src, p->d_packed + cp.pk_wu,
+                 p->d_packed + cp.pk_u, p->d_packed + cp.pk_b, count, p->xcd_remap};
+    tm.begin(K_SUM, mb.flops, mb.bytes, 0,
+             (double)((count + 15) / 16) * 3 * (cp.H / 16) * ((mp.din + cp.H) / 4) * kMfmaF32Flops);
+    HIP_TRY(launch_sum_gru_w128(w, st));
+    tm.end();
+    return IGN_OK;
+  }
   // windowed or segmented aggregation (sum MPs over all destinations): the sum kernel writes x,
   // then the GRU step reads it through an identity CSR (one message per destination: x itself)
   // (the training forward of a plan of default cells sums in the lane walk; a plan with a cell with

@@ -128,11 +128,18 @@ int lower_mps(const ign_plan_desc* d, PlanModel* p) {
     if (cp.din != din)
       return fail(IGN_ERR_INVALID, "mp %d: cell input_dim %d != message dim %d", m, cp.din, din);
     if (mp.feature_concat) {   // x.W is hoisted per source slice: the shapes that matter are (slice, H)
+      for (auto& s : mp.src)   // the 128-wide kernels (gru_wide.hip) take one 128-wide input, no slices
+        if (cp.H == 128 || p->ents[s.entity].hidden_dim == 128)
+          return fail(IGN_ERR_UNSUPPORTED, "mp %d: concat on axis 2 is not lowered at 128 units (slice %d, units %d)", m,
+                      p->ents[s.entity].hidden_dim, cp.H);
       for (auto& s : mp.src)
         if (!gru_shape_supported(p->ents[s.entity].hidden_dim, cp.H))
           return fail(IGN_ERR_UNSUPPORTED, "mp %d: concat slice (input %d, units %d) not instantiated", m,
                       p->ents[s.entity].hidden_dim, cp.H);
-    } else if (!gru_shape_supported(din, cp.H)) {
+    } else if ((din == 128) != (cp.H == 128)) {
+      return fail(IGN_ERR_UNSUPPORTED, "mp %d: a 128-wide GRU cell takes 128-wide messages only (input %d, units %d)", m,
+                  din, cp.H);
+    } else if (!gru_shape_supported(din, cp.H) && !gru_wide_supported(din, cp.H)) {
       return fail(IGN_ERR_UNSUPPORTED, "mp %d: GRU shape (input %d, units %d) not instantiated (16/32, 64/64)", m,
                   din, cp.H);
     }
@@ -384,6 +391,13 @@ void layout_packed(PlanModel* p) {
     // pk_ubf), the split-bf16 / split-fp16 sequence and sum variants, and sum_gru_g32's fused projection
     // (its own pieces, and the target cell's pk_wbf).  mp_step.cpp and mp_backward.cpp dispatch on is_default().
     const bool dflt = cp.is_default();
+    if (gru_wide_supported(din, H)) {   // gru_wide.hip's fragments and nothing else (set_cell_options keeps it default)
+      cp.pk_w = slot(AT_CELL, c, 0, PK_WIDE_W, pack_wide_w_floats(din, H), cp.off_k, -1, -1, din, H);
+      cp.pk_u = slot(AT_CELL, c, 1, PK_WIDE_U, pack_wide_u_floats(H), cp.off_rk, -1, -1, din, H);
+      cp.pk_b = slot(AT_CELL, c, 2, PK_WIDE_B, pack_gru_b_floats(H), cp.off_b, -1, -1, din, H);
+      cp.pk_wu = slot(AT_CELL, c, 3, PK_WIDE_WU, pack_wide_wu_floats(din, H), cp.off_k, cp.off_rk, -1, din, H);
+      continue;
+    }
     const int mode = dflt ? 0 : kPackGruRaw | cp.bias_rows();
     cp.pk_w = slot(AT_CELL, c, 0, PK_GRU, pack_gru_w_floats(din, H), cp.off_k, cp.off_rk, cp.off_b, din, H, mode);
     cp.pk_u = slot(AT_CELL, c, 1, PK_GRU_U, pack_gru_u_floats(H), -1, cp.off_rk, -1, din, H);
@@ -572,6 +586,10 @@ int set_cell_options(PlanModel* p, int cell, const ign_cell_options* o) {
     if (!act_ok(a, ACT_AT_PREDICT))
       return fail(IGN_ERR_INVALID, "ign_plan_set_cell_options: activation code %d", a);
   CellP& cp = p->cells[cell];
+  if (gru_wide_supported(cp.din, cp.H) &&
+      !(o->activation == IGN_ACT_TANH && o->recurrent_activation == IGN_ACT_SIGMOID && o->use_bias && o->reset_after))
+    return fail(IGN_ERR_UNSUPPORTED, "ign_plan_set_cell_options: cell %d is 128 units wide: a GRU cell with options "
+                "is lowered at 16, 32 and 64 units", cell);
   cp.act = o->activation;
   cp.ract = o->recurrent_activation;
   cp.use_bias = o->use_bias != 0;

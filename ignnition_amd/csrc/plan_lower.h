@@ -105,6 +105,7 @@ struct PlanSwitches {
   bool resident_save_table = true;   // ... which also saves the ordered MP's tables (IGN_RESIDENT_SAVE_TABLE=0: recompute)
   int sum_window = -1;            // IGN_SUM_WINDOW: 1 windowed sum aggregation where eligible; -1 (default)
                                   // segmented for destinations of >= 64 messages, 0 of >= 128, 2 for all.
+                                  // No effect on a 128-wide sum MP, which sums in its own kernel (gru_wide.hip).
                                   // (The windowed form:)
                                   // Measured 0.120 vs 0.112 ms (RouteNet link update, 37 messages per link);
                                   // Q-size x512 7.33 -> 6.44 ms/step with both sum MPs windowed
@@ -134,6 +135,10 @@ enum {
   PK_READOUT_H16,   // pack_readout_h16(W1, b1, W2; in1 a, n1 b, n2 c)
   PK_READOUT_H32,   // pack_readout_h32(the same)
   PK_ATTN_VECTORS,  // attn_vectors(K1, K2, a; F a)
+  PK_WIDE_U,        // a 128 / 128 cell (gru_wide.hip): pack_wide(U): the per-wave slices
+  PK_WIDE_W,        //   pack_wide(W): K chunks
+  PK_WIDE_WU,       //   pack_wide(W, U): K chunks of [W ; U]
+  PK_WIDE_B,        //   pack_wide(bias): the combined biases [4][H]
 };
 struct PackJob {
   int kind;

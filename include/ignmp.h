@@ -486,7 +486,8 @@ int  ign_batch_feature_gradients(ign_plan* plan, ign_batch* batch, int32_t entit
  * scaled dpred bit for bit.  The batch is not written: its states, predictions and captured graph
  * stay as the last forward left them, and the parameters are read as they are at the call.
  * Covered: ordered / interleave / concat-axis-1 and plain sum MPs with direct_assignation messages,
- * GRU cells at 16/16, 16/32, 32/16, 32/32 and 64/64 with or without ign_plan_set_cell_options, predict
+ * GRU cells at 16/16, 16/32, 32/16, 32/32 and 64/64 with or without ign_plan_set_cell_options, (not the
+ * 128/128 shape of the inference forward), predict
  * Dense stacks with every activation (a Dropout layer is the identity).  IGN_ERR_UNSUPPORTED, with a
  * message that begins "forward tangent:" and names the feature: attention, convolution, concat on
  * axis 2, message networks, readout operations before predict, LayerNormalization, a batch with halo
