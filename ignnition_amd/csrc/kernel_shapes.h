@@ -51,6 +51,10 @@ inline bool gru_cell_sum_supported(int din, int h, int mode) {
   if (din == 64 && h == 64) return mode == 0;
   return (din == 16 || din == 32) && (h == 16 || h == 32) && mode >= 0 && mode <= 2 && (mode != 2 || din == h);
 }
+// the scenario-major kernels (scenario.hip, ign_forward_scenarios): default cells, the ordered update at
+// H 16 / 32 / 64 and the plain sum update at the four 16 / 32 shapes and 64 / 64
+inline bool scen_seq_supported(int h) { return h == 16 || h == 32 || h == 64; }
+inline bool scen_sum_supported(int din, int h) { return gru_shape_supported(din, h); }
 // pack_gru's mode: 0 the default cell (scaled fragments, bias [2][3H]); else kPackGruRaw | the raw
 // bias tensor's rows (2: [2][3H], 1: [3H], 0: none, a block of zeros)
 constexpr int kPackGruRaw = 4;

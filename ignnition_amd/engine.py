@@ -976,6 +976,50 @@ class Batch:
                                       dpred.ctypes.data_as(C.c_void_p)))
         return pred, dpred
 
+    def forward_scenarios(self, features: dict, scenarios: int = None) -> np.ndarray:
+        """Predictions ``[S, predictions, units]`` for S sets of feature values on this batch's graphs, in
+        one pass (ign_forward_scenarios): scenario s is what a batch built from the same graphs with
+        scenario s's values predicts.  ``features``: ``{entity: values}``, the values one ``[S, rows, F]``
+        array or a ``{feature name: [S, rows(, size)]}`` dict, normalised as the values the batch was
+        built from; an entity left out keeps the batch's values in every scenario.  S is taken from the
+        arrays; with no array, ``scenarios`` gives it.  An f32 evaluation of the model like
+        ``forward_tangent``'s; a scenario's bits depend neither on S nor on its index.  The batch's
+        own states and predictions are not touched.  Arrays that disagree on S, an unknown entity, an
+        entity without features or a wrong shape is a ``ValueError``; a model outside the scenario
+        kernels' scope an ``EngineError`` that names the feature."""
+        p = self.engine.plan
+        per, counts = {}, set() if scenarios is None else {int(scenarios)}
+        for entity, values in features.items():
+            e, rows, F = self._feature_entity(entity)
+            if F == 0:
+                raise ValueError("forward_scenarios: entity %r has no features" % entity)
+            parts = {k: np.asarray(v, np.float32) for k, v in values.items()} if isinstance(values, dict) \
+                else np.asarray(values, np.float32)
+            for v in (parts.values() if isinstance(parts, dict) else [parts]):
+                if v.ndim < 2:
+                    raise ValueError("forward_scenarios: %r values have shape %s, [S, rows, ...] is needed"
+                                     % (entity, tuple(v.shape)))
+                counts.add(int(v.shape[0]))
+            per[e] = parts
+        if len(counts) != 1 or min(counts) < 1:
+            raise ValueError("forward_scenarios: the arrays give %s scenarios (one count >= 1 is needed; "
+                             "pass scenarios= when features is empty)" % sorted(counts))
+        S = counts.pop()
+        ptrs = (C.c_void_p * len(p.entities))()
+        keep = []
+        for e, parts in per.items():
+            try:
+                v = np.stack([feature_rows(p.features[e], self.rows[e],
+                                           {k: a[s] for k, a in parts.items()} if isinstance(parts, dict) else parts[s])
+                              for s in range(S)])
+            except ValueError as err:
+                raise ValueError(str(err).replace("set_features:", "forward_scenarios:", 1)) from None
+            keep.append(v)
+            ptrs[e] = v.ctypes.data_as(C.c_void_p)
+        pred = np.empty((S, self.predictions, self.output_units), np.float32)
+        check(lib.ign_forward_scenarios(self.handle, S, ptrs, len(p.entities), pred.ctypes.data_as(C.c_void_p)))
+        return pred
+
     # ---- what-if analysis: new per-edge parameters (params_<adj>) on the same graphs, their gradient
     def _edge_sources(self, adj: str):
         """(edges of the batch, param_dim, [(mp, source)]) of adjacency ``adj`` (edge_param_sources)."""

@@ -308,6 +308,40 @@ class ComnetModel:
         finally:
             b.close()
 
+    def predict_scenarios(self, graphs, features: dict) -> np.ndarray:
+        """Predictions ``[S, predictions, units]`` of a batch of graphs under S sets of feature values:
+        ``features`` is ``{feature name: array [S, rows(, size)]}`` in batch row order, raw values, to
+        which the model's normalisation functions are applied by name exactly as when a batch is built
+        (``normalization``); an entity none of whose features is named keeps the graphs' values in every
+        scenario, an entity with several features needs all of them.  One pass
+        of ``Batch.forward_scenarios`` on one batch: the index tables are lowered and uploaded once."""
+        names = {f: ent for ent, feats in zip(self.plan.entities, self.plan.features) for f, _ in feats}
+        unknown = sorted(set(features) - set(names))
+        if unknown:
+            raise ValueError("predict_scenarios: unknown feature(s) %s (the model has %s)" % (unknown, sorted(names)))
+        given = {f.name: np.asarray(v, np.float32) for f in self.model_info.get_all_features()
+                 for v in [features.get(f.name)] if v is not None}
+        counts = {int(v.shape[0]) for v in given.values() if v.ndim >= 2}
+        if len(counts) != 1 or any(v.ndim < 2 for v in given.values()):
+            raise ValueError("predict_scenarios: the arrays must be [S, rows, ...] with one S (got %s)"
+                             % sorted(tuple(v.shape) for v in given.values()))
+        S = counts.pop()
+        for f in self.model_info.get_all_features():
+            if f.name in given and str(f.normalization) != "None":
+                given[f.name] = np.asarray(_resolve(f.normalization)(given[f.name], f.name), np.float32)
+        per_entity = {}
+        for ent, feats in zip(self.plan.entities, self.plan.features):
+            if any(f in given for f, _ in feats):
+                missing = [f for f, _ in feats if f not in given]
+                if missing:   # an entity's columns travel together (ign_forward_scenarios' feat[e])
+                    raise ValueError("predict_scenarios: entity %r needs all of its features, %s missing" % (ent, missing))
+                per_entity[ent] = {f: given[f] for f, _ in feats}
+        b = self.batch(graphs)
+        try:
+            return b.forward_scenarios(per_entity, scenarios=S)
+        finally:
+            b.close()
+
     def __call__(self, input: dict, training: bool = False) -> np.ndarray:
         """``ComnetModel.call`` (GM:384) for one graph: [P, units] predictions."""
         return self.batch([input]).forward()

@@ -493,6 +493,31 @@ int  ign_batch_feature_gradients(ign_plan* plan, ign_batch* batch, int32_t entit
  * axis 2, message networks, readout operations before predict, LayerNormalization, a batch with halo
  * rows, and a call between ign_forward_train(_begin) and the end of that forward's backward. */
 int  ign_forward_tangent(ign_batch* batch, const float* const* dfeat, int n_ents, float* pred, float* dpred);
+/* ---- Scenario forward (ABI 13 addition) ------------------------------------------------------------
+ * The what-if asked most often: one topology and routing, n_scen sets of feature values (traffic
+ * matrices, capacity plans), every prediction of every set in one pass.  ign_forward_scenarios shares
+ * the batch's index tables among the scenarios and puts the 16 rows of every MFMA tile on the scenario
+ * axis, so a tile is 16 scenarios of one row: one length, one step code, contiguous blocks (DESIGN.md
+ * §3m).  feat[e] is [n_scen][rows of entity e][F_e] floats (the columns in the plan's feature order,
+ * the values ign_batch_create would be given, after the caller's normalisation), host or device
+ * memory; NULL: every scenario uses the batch's current feature values of that entity.  n_ents must be
+ * the plan's entity count.  pred is [n_scen][predictions][units], host or device memory: scenario s is
+ * what a batch created from the same graphs with scenario s's feature values predicts, evaluated in
+ * f32 on the f32-MFMA class like ign_forward_tangent's primal (not ign_forward's bits); its bits do
+ * not depend on n_scen or on s.  The call returns when pred is written.  The batch is not written:
+ * its states, predictions, feature buffer and captured graph stay as the last forward left them;
+ * parameters are read as they are at the call.  Device memory: about 2 n_scen' (rows_e H_e) floats per
+ * entity and n_scen' table rows of 3H per ordered MP, n_scen' = n_scen rounded up to 16, scratch of the
+ * batch's pool.  IGN_ERR_INVALID: n_scen < 1, a null batch or pred, a wrong n_ents, a non-NULL feat[e]
+ * on an entity without features.
+ * Covered: ordered / interleave / concat-axis-1 and plain sum MPs with direct_assignation messages,
+ * default GRU cells at 16/16, 16/32, 32/16, 32/32 and 64/64, predict Dense stacks with every
+ * activation (a Dropout layer is the identity).  IGN_ERR_UNSUPPORTED, with a message that begins
+ * "forward scenarios:" and names the feature: attention, convolution, concat on axis 2, message
+ * networks, readout operations before predict, LayerNormalization, a GRU cell with options, the
+ * 128/128 shape, a batch with halo rows, and a call between ign_forward_train(_begin) and the end of
+ * that forward's backward. */
+int  ign_forward_scenarios(ign_batch* batch, int32_t n_scen, const float* const* feat, int n_ents, float* pred);
 /* ---- Edge parameters of a live batch and their gradient (ABI 13 additions) -----------------------
  * The other input a what-if changes on fixed graphs: params_<adj>, which a message network of MP
  * source (mp, source) reads as edge_params.  Each such source owns one buffer [n_edges][param_dim];
