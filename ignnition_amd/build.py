@@ -18,13 +18,16 @@ OUT = os.path.join(HERE, "libignmp.so")
 ISA_MIX = os.path.join(HERE, "isa_mix.json")
 SOURCES = ["engine.cpp", "mp_step.cpp", "plan_lower.cpp", "batch_lower.cpp", "devpool.cpp", "train.cpp", "train_alloc.cpp", "mp_backward.cpp", "dense_stack.cpp", "train_lower.cpp", "learn.cpp", "readout.cpp", "dataset.cpp", "plan_json.cpp", "kernels.hip", "kernels_bf.hip",
            "train_kernels.hip", "learn_kernels.hip", "readout_kernels.hip", "resident.hip", "readout_h32.hip", "train_csr.hip",
-           "dropout.cpp", "dropout_kernels.hip", "layernorm.cpp", "layernorm_kernels.hip", "cell_options.cpp", "gru_cell.hip", "tangent.cpp", "tangent.hip", "gru_wide.hip", "scenario.cpp", "scenario.hip"]
+           "dropout.cpp", "dropout_kernels.hip", "layernorm.cpp", "layernorm_kernels.hip", "cell_options.cpp", "gru_cell.hip", "tangent.cpp", "tangent.hip", "gru_wide.hip", "scenario.cpp", "scenario.hip",
+           "jacobian.cpp", "jacobian.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-Wno-unused-value"]
 EXTRA = {"kernels_bf.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "resident.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
          "readout_h32.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
          # no packed-fp32 VALU forms in the dual step's elementwise code
          "tangent.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
-         "gru_wide.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+         "gru_wide.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+         # tangent.hip's flags: the linearising primal must give its primal's bits
+         "jacobian.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def needs_build() -> bool:

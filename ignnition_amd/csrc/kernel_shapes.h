@@ -55,6 +55,10 @@ inline bool gru_cell_sum_supported(int din, int h, int mode) {
 // H 16 / 32 / 64 and the plain sum update at the four 16 / 32 shapes and 64 / 64
 inline bool scen_seq_supported(int h) { return h == 16 || h == 32 || h == 64; }
 inline bool scen_sum_supported(int din, int h) { return gru_shape_supported(din, h); }
+// the linearised forward (jacobian.hip, ign_forward_jacobian): reset_after cells with or without other
+// options; the ordered kernels at (h, h) for H 16 / 32 / 64, the plain sum kernels at the four 16 / 32
+// shapes and 64 / 64
+inline bool jacobian_shape_supported(int din, int h) { return gru_shape_supported(din, h); }
 // pack_gru's mode: 0 the default cell (scaled fragments, bias [2][3H]); else kPackGruRaw | the raw
 // bias tensor's rows (2: [2][3H], 1: [3H], 0: none, a block of zeros)
 constexpr int kPackGruRaw = 4;

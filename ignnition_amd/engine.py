@@ -976,6 +976,40 @@ class Batch:
                                       dpred.ctypes.data_as(C.c_void_p)))
         return pred, dpred
 
+    def _stacked_feature_rows(self, what: str, unit: str, arg: str, kw: str, values_by_entity: dict, count: int = None):
+        """``(S, per-entity pointer array, the arrays it points into)`` for ``{entity: [S, rows, F] array or
+        {feature: [S, rows(, size)]}}``: the argument of ``forward_scenarios`` and ``forward_tangents``."""
+        p = self.engine.plan
+        per, counts = {}, set() if count is None else {int(count)}
+        for entity, values in values_by_entity.items():
+            e, rows, F = self._feature_entity(entity)
+            if F == 0:
+                raise ValueError("%s: entity %r has no features" % (what, entity))
+            parts = {k: np.asarray(v, np.float32) for k, v in values.items()} if isinstance(values, dict) \
+                else np.asarray(values, np.float32)
+            for v in (parts.values() if isinstance(parts, dict) else [parts]):
+                if v.ndim < 2:
+                    raise ValueError("%s: %r values have shape %s, [S, rows, ...] is needed"
+                                     % (what, entity, tuple(v.shape)))
+                counts.add(int(v.shape[0]))
+            per[e] = parts
+        if len(counts) != 1 or min(counts) < 1:
+            raise ValueError("%s: the arrays give %s %s (one count >= 1 is needed; "
+                             "pass %s= when %s is empty)" % (what, sorted(counts), unit, kw, arg))
+        S = counts.pop()
+        ptrs = (C.c_void_p * len(p.entities))()
+        keep = []
+        for e, parts in per.items():
+            try:
+                v = np.stack([feature_rows(p.features[e], self.rows[e],
+                                           {k: a[s] for k, a in parts.items()} if isinstance(parts, dict) else parts[s])
+                              for s in range(S)])
+            except ValueError as err:
+                raise ValueError(str(err).replace("set_features:", what + ":", 1)) from None
+            keep.append(v)
+            ptrs[e] = v.ctypes.data_as(C.c_void_p)
+        return S, ptrs, keep
+
     def forward_scenarios(self, features: dict, scenarios: int = None) -> np.ndarray:
         """Predictions ``[S, predictions, units]`` for S sets of feature values on this batch's graphs, in
         one pass (ign_forward_scenarios): scenario s is what a batch built from the same graphs with
@@ -987,38 +1021,29 @@ class Batch:
         own states and predictions are not touched.  Arrays that disagree on S, an unknown entity, an
         entity without features or a wrong shape is a ``ValueError``; a model outside the scenario
         kernels' scope an ``EngineError`` that names the feature."""
-        p = self.engine.plan
-        per, counts = {}, set() if scenarios is None else {int(scenarios)}
-        for entity, values in features.items():
-            e, rows, F = self._feature_entity(entity)
-            if F == 0:
-                raise ValueError("forward_scenarios: entity %r has no features" % entity)
-            parts = {k: np.asarray(v, np.float32) for k, v in values.items()} if isinstance(values, dict) \
-                else np.asarray(values, np.float32)
-            for v in (parts.values() if isinstance(parts, dict) else [parts]):
-                if v.ndim < 2:
-                    raise ValueError("forward_scenarios: %r values have shape %s, [S, rows, ...] is needed"
-                                     % (entity, tuple(v.shape)))
-                counts.add(int(v.shape[0]))
-            per[e] = parts
-        if len(counts) != 1 or min(counts) < 1:
-            raise ValueError("forward_scenarios: the arrays give %s scenarios (one count >= 1 is needed; "
-                             "pass scenarios= when features is empty)" % sorted(counts))
-        S = counts.pop()
-        ptrs = (C.c_void_p * len(p.entities))()
-        keep = []
-        for e, parts in per.items():
-            try:
-                v = np.stack([feature_rows(p.features[e], self.rows[e],
-                                           {k: a[s] for k, a in parts.items()} if isinstance(parts, dict) else parts[s])
-                              for s in range(S)])
-            except ValueError as err:
-                raise ValueError(str(err).replace("set_features:", "forward_scenarios:", 1)) from None
-            keep.append(v)
-            ptrs[e] = v.ctypes.data_as(C.c_void_p)
+        S, ptrs, keep = self._stacked_feature_rows("forward_scenarios", "scenarios", "features", "scenarios", features, scenarios)
         pred = np.empty((S, self.predictions, self.output_units), np.float32)
-        check(lib.ign_forward_scenarios(self.handle, S, ptrs, len(p.entities), pred.ctypes.data_as(C.c_void_p)))
+        check(lib.ign_forward_scenarios(self.handle, S, ptrs, len(self.engine.plan.entities), pred.ctypes.data_as(C.c_void_p)))
         return pred
+
+    def forward_tangents(self, directions: dict, directions_count: int = None):
+        """A block of the Jacobian (ign_forward_jacobian): ``(pred, dpred)`` with ``pred [predictions,
+        units]`` and ``dpred [K, predictions, units]``, ``dpred[k] = J . direction k``, from ONE
+        linearised forward instead of K calls of ``forward_tangent``.  ``directions``: ``{entity:
+        values}``, the values one ``[K, rows, F]`` array or a ``{feature name: [K, rows(, size)]}`` dict,
+        in terms of the normalised values the batch was built from; an entity left out does not move in
+        any direction.  K is taken from the arrays; with no array, ``directions_count`` gives it.
+        ``pred`` is ``forward_tangent``'s bit for bit; a direction's bits depend neither on K nor on its
+        index.  The batch's own states and predictions are not touched.  The ``ValueError``s are
+        ``forward_scenarios``'; a model outside the kernels' scope is an ``EngineError`` that names the
+        feature."""
+        K, ptrs, keep = self._stacked_feature_rows("forward_tangents", "directions", "directions", "directions_count", directions,
+                                                    directions_count)
+        pred = np.empty((self.predictions, self.output_units), np.float32)
+        dpred = np.empty((K,) + pred.shape, np.float32)
+        check(lib.ign_forward_jacobian(self.handle, K, ptrs, len(self.engine.plan.entities), pred.ctypes.data_as(C.c_void_p),
+                                       dpred.ctypes.data_as(C.c_void_p)))
+        return pred, dpred
 
     # ---- what-if analysis: new per-edge parameters (params_<adj>) on the same graphs, their gradient
     def _edge_sources(self, adj: str):

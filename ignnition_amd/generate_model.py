@@ -308,6 +308,32 @@ class ComnetModel:
         finally:
             b.close()
 
+    def jacobian(self, graphs, directions: dict):
+        """``(predictions, dpred [K, predictions, units])`` of a batch of graphs: K directional
+        sensitivities at once, ``dpred[k]`` what ``directional_sensitivities`` returns for direction k.
+        ``directions`` is ``{feature name: array [K, rows(, size)]}`` in batch row order, in terms of the
+        normalised values the engine is fed; a feature left out does not move.  One pass of
+        ``Batch.forward_tangents``: the primal forward runs once, whatever K."""
+        names = {f for feats in self.plan.features for f, _ in feats}
+        unknown = sorted(set(directions) - names)
+        if unknown:
+            raise ValueError("jacobian: unknown feature(s) %s (the model has %s)" % (unknown, sorted(names)))
+        given = {f: np.asarray(v, np.float32) for f, v in directions.items()}
+        counts = {int(v.shape[0]) for v in given.values() if v.ndim >= 2}
+        if len(counts) != 1 or any(v.ndim < 2 for v in given.values()):
+            raise ValueError("jacobian: the arrays must be [K, rows, ...] with one K (got %s)"
+                             % sorted(tuple(v.shape) for v in given.values()))
+        K = counts.pop()
+        b = self.batch(graphs)
+        try:
+            per_entity = {}
+            for ent, feats, rows in zip(self.plan.entities, self.plan.features, b.rows):
+                if any(f in given for f, _ in feats):
+                    per_entity[ent] = {f: given[f] if f in given else np.zeros((K, rows, size), np.float32) for f, size in feats}
+            return b.forward_tangents(per_entity, directions_count=K)
+        finally:
+            b.close()
+
     def predict_scenarios(self, graphs, features: dict) -> np.ndarray:
         """Predictions ``[S, predictions, units]`` of a batch of graphs under S sets of feature values:
         ``features`` is ``{feature name: array [S, rows(, size)]}`` in batch row order, raw values, to

@@ -518,6 +518,34 @@ int  ign_forward_tangent(ign_batch* batch, const float* const* dfeat, int n_ents
  * 128/128 shape, a batch with halo rows, and a call between ign_forward_train(_begin) and the end of
  * that forward's backward. */
 int  ign_forward_scenarios(ign_batch* batch, int32_t n_scen, const float* const* feat, int n_ents, float* pred);
+/* ---- Jacobian blocks (ABI 13 addition) --------------------------------------------------------------
+ * What a planner asks of the what-if family: how does every prediction move with each of n_dir feature
+ * directions (link capacities, traffic entries)?  ign_forward_jacobian runs the primal forward ONCE,
+ * keeps per GRU step the five coefficient rows of the tangent update, which do not depend on the
+ * direction, and then moves all n_dir tangents through a purely linear recurrence with the 16 rows of
+ * every MFMA tile on the direction axis -- instead of n_dir calls of
+ * ign_forward_tangent, each of which repeats the primal.  dfeat[e] is [n_dir][rows of entity e][F_e]
+ * floats (the columns in the plan's feature order, in terms of the values ign_batch_create was given),
+ * host or device memory; NULL: every direction is zero on that entity.  n_ents must be the plan's
+ * entity count.  pred is [predictions][units] and may be NULL; dpred is [n_dir][predictions][units],
+ * dpred[k] = J . direction k; host or device memory; the call returns when both are written.  pred is
+ * ign_forward_tangent's pred bit for bit.  dpred[k] agrees with ign_forward_tangent's dpred to rounding
+ * (its accumulation structure differs); its bits depend neither on n_dir nor on k, zero directions
+ * give zeros exactly and a direction scaled by a power of two the scaled dpred bit for bit.  The batch
+ * is not written: its states, predictions, feature buffer and captured graph stay as the last forward
+ * left them; parameters are read as they are at the call.  Device memory: about 2 n_dir' (rows_e H_e)
+ * floats per entity, n_dir' table rows of 3H per ordered MP and 5H per real step, n_dir' = n_dir
+ * rounded up to 16, scratch of the batch's pool.  IGN_ERR_INVALID: n_dir < 1, a null batch, both
+ * outputs null, a wrong n_ents, a non-NULL dfeat[e] on an entity without features.
+ * Covered: ordered / interleave / concat-axis-1 and plain sum MPs with direct_assignation messages,
+ * reset_after GRU cells at 16/16, 16/32, 32/16, 32/32 and 64/64 with or without the activation,
+ * recurrent_activation and use_bias options, predict Dense stacks with every activation (a Dropout
+ * layer is the identity).  IGN_ERR_UNSUPPORTED, with a message that begins "forward jacobian:" and
+ * names the feature: attention, convolution, concat on axis 2, message networks, readout operations
+ * before predict, LayerNormalization, a cell with reset_after = false, the 128/128 shape, a batch with
+ * halo rows, and a call between ign_forward_train(_begin) and the end of that forward's backward. */
+int  ign_forward_jacobian(ign_batch* batch, int32_t n_dir, const float* const* dfeat, int n_ents, float* pred,
+                          float* dpred);
 /* ---- Edge parameters of a live batch and their gradient (ABI 13 additions) -----------------------
  * The other input a what-if changes on fixed graphs: params_<adj>, which a message network of MP
  * source (mp, source) reads as edge_params.  Each such source owns one buffer [n_edges][param_dim];
