@@ -8,63 +8,15 @@
 // the plan's stream.  Nothing of the batch is written: its states, tables, feature buffer, predictions
 // and captured graph stay as the last forward left them.
 
-#include "jacobian.h"
-#include "mp_step.h"
+#include "jacobian_common.h"
 #include "train_kernels.h"
 
 namespace {
 
 using namespace ign;
 
-// scratch of one call (IGN_POOL_POISON=1 fills the blocks with NaN): no kernel here may read what no
-// kernel here wrote
-struct Scratch {
-  ign_batch* b;
-  hipStream_t st;
-  std::vector<void*> blocks;
-  ~Scratch() {
-    if (!blocks.empty()) pool_release(b->pool.get(), blocks, st);
-  }
-  // n floats (+ slack: a masked-off row 0 of an empty table may be read)
-  int get(float** out, int64_t n) {
-    void* q = nullptr;
-    const size_t bytes = (size_t)(std::max<int64_t>(n, 0) + 256) * sizeof(float);
-    const hipError_t e = pool_alloc(b->pool.get(), &q, bytes, true);
-    if (e != hipSuccess) return fail(IGN_ERR_OOM, "forward jacobian: device alloc (%zu bytes): %s", bytes, hipGetErrorString(e));
-    blocks.push_back(q);
-    *out = static_cast<float*>(q);
-    return IGN_OK;
-  }
-};
-
-int refuse(const char* what) { return fail(IGN_ERR_UNSUPPORTED, "forward jacobian: %s", what); }
-
-// what the linearised kernels do not cover, by name
-int check_scope(const ign_plan* p, const ign_batch* b) {
-  for (int64_t h : b->halo)
-    if (h) return refuse("a batch with halo rows (an edge-cut partition)");
-  if (b->train && train_step_open(b->train))
-    return refuse("a training step is open (between a training forward and the end of its backward)");
-  for (const MPP& mp : p->mps) {
-    if (mp.aggr == IGN_AGGR_ATTENTION) return refuse("attention aggregation");
-    if (mp.aggr == IGN_AGGR_CONVOLUTION) return refuse("convolution aggregation");
-    if (mp.feature_concat) return refuse("concat on axis 2");
-    for (const MsgNN& nn : mp.nn)
-      if (!nn.layers.empty()) return refuse("a message network (message-creation layers on an MP source)");
-    const CellP& cp = p->cells[mp.cell];
-    if (!cp.reset_after) return refuse("a GRU cell with reset_after = false (its candidate needs a second dependent sweep)");
-    if (gru_wide_supported(mp.din, cp.H)) return refuse("the 128/128 GRU shape");
-    if (mp.din != cp.din || !jacobian_shape_supported(mp.din, cp.H) || (mp.sorted && !jacobian_shape_supported(cp.H, cp.H)))
-      return fail(IGN_ERR_UNSUPPORTED, "forward jacobian: GRU shape %d / %d", mp.din, cp.H);
-  }
-  if (!p->ro_ops.empty()) return refuse("a readout operation before predict");
-  if (!p->norms.empty()) return refuse("LayerNormalization");
-  return IGN_OK;
-}
-
-struct RawCell {   // pack_gru's unscaled form of one cell, packed once per call from the live parameters
-  float *W = nullptr, *U = nullptr, *b = nullptr;
-};
+using Scratch = JacScratch;
+using RawCell = JacRawCell;
 
 struct MpScratch {
   float* tab = nullptr;    // ordered: the primal's projected table
@@ -140,7 +92,7 @@ int forward_jacobian(ign_plan* p, ign_batch* b, int64_t n_dir, const float* cons
   hipStream_t st = p->stream;
   const int E = (int)p->ents.size();
   const int64_t kp = scen_padded(n_dir), P = b->n_pred, rows_d = P * kp;
-  Scratch sc{b, st, {}};
+  Scratch sc{b, st, "forward jacobian", {}};
   int rc;
   // ---- every block of the call first: a poisoned pool fills them on the upload stream ----
   std::vector<RawCell> raw(p->cells.size());
@@ -270,6 +222,6 @@ extern "C" int ign_forward_jacobian(ign_batch* b, int32_t n_dir, const float* co
   for (int e = 0; e < n_ents; ++e)
     if (dfeat[e] && (p->ents[e].feature_total <= 0 || !b->d_feat[e]))
       return fail(IGN_ERR_INVALID, "forward jacobian: entity %d has no features", e);
-  if ((rc = check_scope(p, b))) return rc;
+  if ((rc = jac_check_scope(p, b, "forward jacobian"))) return rc;
   return forward_jacobian(p, b, n_dir, dfeat, pred, dpred);
 }

@@ -1045,6 +1045,44 @@ class Batch:
                                        dpred.ctypes.data_as(C.c_void_p)))
         return pred, dpred
 
+    def backward_cotangents(self, cotangents):
+        """Rows of the Jacobian (ign_backward_jacobian): ``(pred, {entity: {feature: ndarray [K, rows,
+        size]}})`` where entry k is the gradient of ``sum(cotangents[k] * pred)`` with respect to the
+        feature, i.e. ``J^T . cotangent k``, from ONE adjoint sweep of the linearised forward instead of K
+        rounds of ``forward_train`` / ``backward`` / ``feature_gradients``.  ``cotangents``: ``[K,
+        predictions, units]``, or ``[K, predictions]`` when units is 1; a one-hot cotangent gives the row
+        of one prediction.  The gradients are with respect to the normalised values the batch was built
+        from, split per feature as ``feature_gradients`` splits them; entities without features are left
+        out.  ``pred`` is ``forward_tangents``' bit for bit; a cotangent's bits depend neither on K nor on
+        its index.  No training tables are needed and the batch's own states and predictions are not
+        touched.  A wrong shape is a ``ValueError``; a model outside the kernels' scope an ``EngineError``
+        that names the feature."""
+        p = self.engine.plan
+        w = np.ascontiguousarray(cotangents, np.float32)
+        if w.ndim == 2 and self.output_units == 1:
+            w = w[:, :, None]
+        if w.ndim != 3 or w.shape[0] < 1 or w.shape[1:] != (self.predictions, self.output_units):
+            raise ValueError("backward_cotangents: cotangents have shape %s, [K >= 1, %d, %d] is needed"
+                             % (tuple(np.shape(cotangents)), self.predictions, self.output_units))
+        K = int(w.shape[0])
+        ptrs = (C.c_void_p * len(p.entities))()
+        outs = {}
+        for e, feats in enumerate(p.features):
+            F = sum(size for _, size in feats)
+            if F:
+                outs[e] = np.empty((K, self.rows[e], F), np.float32)
+                ptrs[e] = outs[e].ctypes.data_as(C.c_void_p)
+        pred = np.empty((self.predictions, self.output_units), np.float32)
+        check(lib.ign_backward_jacobian(self.handle, K, w.ctypes.data_as(C.c_void_p), len(p.entities),
+                                        pred.ctypes.data_as(C.c_void_p), ptrs))
+        res = {}
+        for e, g in outs.items():
+            res[p.entities[e]], col = {}, 0
+            for name, size in p.features[e]:
+                res[p.entities[e]][name] = g[:, :, col:col + size].copy()
+                col += size
+        return pred, res
+
     # ---- what-if analysis: new per-edge parameters (params_<adj>) on the same graphs, their gradient
     def _edge_sources(self, adj: str):
         """(edges of the batch, param_dim, [(mp, source)]) of adjacency ``adj`` (edge_param_sources)."""

@@ -334,6 +334,30 @@ class ComnetModel:
         finally:
             b.close()
 
+    def jacobian_rows(self, graphs, cotangents=None, predictions=None):
+        """``(predictions, {entity: {feature: gradient [K, rows, size]}})`` of a batch of graphs: K rows of
+        the Jacobian at once.  Entry k is what ``sensitivities(graphs, dpred=cotangents[k])`` returns, to
+        rounding, under the same conventions (gradients with respect to the normalised feature values the
+        engine is fed, in batch row order; entities without features left out).  ``cotangents``: ``[K,
+        predictions(, units)]``; or ``predictions=[i, ...]``, shorthand for the one-hot cotangents of those
+        (flattened) predictions: which inputs drive these K outputs.  One pass of
+        ``Batch.backward_cotangents``: no training tables, no parameter gradients, whatever K."""
+        if (cotangents is None) == (predictions is None):
+            raise ValueError("jacobian_rows: give either cotangents or predictions")
+        b = self.batch(graphs)
+        try:
+            if cotangents is None:
+                idx = np.asarray(predictions, np.int64).reshape(-1)
+                n = b.predictions * b.output_units
+                if idx.size < 1 or idx.min() < 0 or idx.max() >= n:
+                    raise ValueError("jacobian_rows: predictions must be indices in [0, %d)" % n)
+                cotangents = np.zeros((idx.size, n), np.float32)
+                cotangents[np.arange(idx.size), idx] = 1.0
+            w = np.asarray(cotangents, np.float32)
+            return b.backward_cotangents(w.reshape(w.shape[0], b.predictions, b.output_units) if w.ndim >= 2 else w)
+        finally:
+            b.close()
+
     def predict_scenarios(self, graphs, features: dict) -> np.ndarray:
         """Predictions ``[S, predictions, units]`` of a batch of graphs under S sets of feature values:
         ``features`` is ``{feature name: array [S, rows(, size)]}`` in batch row order, raw values, to

@@ -546,6 +546,29 @@ int  ign_forward_scenarios(ign_batch* batch, int32_t n_scen, const float* const*
  * halo rows, and a call between ign_forward_train(_begin) and the end of that forward's backward. */
 int  ign_forward_jacobian(ign_batch* batch, int32_t n_dir, const float* const* dfeat, int n_ents, float* pred,
                           float* dpred);
+/* ---- Jacobian rows (ABI 13 addition) ----------------------------------------------------------------
+ * The opposite question: which feature entries drive THESE n_cot predictions (or weighted sums of
+ * predictions)?  ign_backward_jacobian runs the same linearising primal once, keeping the coefficient
+ * rows of every MP instance of every iteration, and then one adjoint sweep moves all n_cot cotangents
+ * back through the transposed linear steps with the 16 rows of every MFMA tile on the cotangent axis
+ *  -- instead of n_cot rounds of ign_forward_train + ign_backward +
+ * ign_batch_feature_gradients.  It needs no training tables (ign_batch_enable_training) and forms no
+ * parameter gradient.  cot is [n_cot][predictions][units]; n_ents must be the plan's entity count;
+ * dfeat_out[e] is [n_cot][rows of entity e][F_e], dfeat_out[e][k] = d(sum cot[k] . pred)/d(features of
+ * e), i.e. J^T cot[k], in terms of the values ign_batch_create was given, or NULL (not wanted); pred is
+ * [predictions][units] or NULL.  Host or device memory; the call returns when they are written.  pred
+ * is ign_forward_jacobian's pred bit for bit.  A cotangent's result depends neither on n_cot nor on k
+ * bit for bit, zero cotangents give zeros exactly and a cotangent scaled by a power of two the scaled
+ * result bit for bit; source rows sum their readers in ascending step / message order.  The batch is
+ * not written.  Device memory, scratch of the batch's pool, n_cot' = n_cot rounded up to 16: 2 n_cot'
+ * (rows_e H_e) floats per entity, 5H floats per real step per iteration, 2 n_cot' predictions x the
+ * widest predict layer, and the step cotangents [steps][16 c][3H] for a chunk of c blocks of 16
+ * cotangents, c chosen so that they stay within 256 MiB (one block at least).
+ * IGN_ERR_INVALID: n_cot < 1, a null batch, cot or dfeat_out, a wrong n_ents, a non-NULL dfeat_out[e]
+ * on an entity without features.  Scope and refusals are ign_forward_jacobian's, the messages begin
+ * "backward jacobian:". */
+int  ign_backward_jacobian(ign_batch* batch, int32_t n_cot, const float* cot, int n_ents, float* pred,
+                           float* const* dfeat_out);
 /* ---- Edge parameters of a live batch and their gradient (ABI 13 additions) -----------------------
  * The other input a what-if changes on fixed graphs: params_<adj>, which a message network of MP
  * source (mp, source) reads as edge_params.  Each such source owns one buffer [n_edges][param_dim];
