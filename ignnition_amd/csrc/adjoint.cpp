@@ -33,14 +33,6 @@ struct TCell {   // launch_pack_a's fragments of the raw W [DIN][3H] / U [H][3H]
   float *Wt = nullptr, *Ut = nullptr;
 };
 
-int upload_i32(JacScratch& sc, const hvec<int32_t>& h, int32_t** out) {
-  float* f = nullptr;
-  if (int rc = sc.get(&f, (int64_t)h.size())) return rc;
-  *out = reinterpret_cast<int32_t*>(f);
-  if (!h.empty()) HIP_TRY(upload_bytes(f, h.data(), h.size() * sizeof(int32_t)));
-  return IGN_OK;
-}
-
 int backward_jacobian(ign_plan* p, ign_batch* b, int64_t n_cot, const float* cot, float* pred, float* const* dfeat_out) {
   hipStream_t st = p->stream;
   const int E = (int)p->ents.size();
@@ -103,7 +95,7 @@ int backward_jacobian(ign_plan* p, ign_batch* b, int64_t n_cot, const float* cot
     m.tptr.assign(S, nullptr);
     m.tidx.assign(S, nullptr);
     for (int s = 0; s < S; ++s)
-      if ((rc = upload_i32(sc, hp[s], &m.tptr[s])) || (rc = upload_i32(sc, hi[s], &m.tidx[s]))) return rc;
+      if ((rc = jac_upload_i32(sc, hp[s], &m.tptr[s])) || (rc = jac_upload_i32(sc, hi[s], &m.tidx[s]))) return rc;
   }
   const int32_t chunk = (int32_t)std::max<int64_t>(1, std::min<int64_t>(n_blk, kChunkBytes / (per_blk * (int64_t)sizeof(float))));
   float* blocks = nullptr;
@@ -263,16 +255,6 @@ extern "C" int ign_backward_jacobian(ign_batch* b, int32_t n_cot, const float* c
     if (dfeat_out[e] && (p->ents[e].feature_total <= 0 || !b->d_feat[e]))
       return fail(IGN_ERR_INVALID, "backward jacobian: entity %d has no features", e);
   if ((rc = jac_check_scope(p, b, kWhat))) return rc;
-  // what the flat layouts assume of a plan inside that scope
-  for (const MPP& mp : p->mps)
-    for (const auto& src : mp.src)
-      if (p->ents[src.entity].hidden_dim != mp.din)
-        return fail(IGN_ERR_UNSUPPORTED, "backward jacobian: a source %d wide on an MP input of %d", p->ents[src.entity].hidden_dim, mp.din);
-  for (int id : p->ro_in)
-    if (id < 0 || id >= n_ents || b->rows[id] != b->n_pred || p->ro_t[id].width != p->ents[id].hidden_dim)
-      return fail(IGN_ERR_UNSUPPORTED, "backward jacobian: predict does not read one row of entity states per prediction");
-  if (!p->dense.empty() && p->dense[0].in != p->ro_width)
-    return fail(IGN_ERR_UNSUPPORTED, "backward jacobian: predict's first layer reads %d of %d input columns", p->dense[0].in,
-                p->ro_width);
+  if ((rc = adj_check_layout(p, b, kWhat))) return rc;
   return backward_jacobian(p, b, n_cot, cot, pred, dfeat_out);
 }

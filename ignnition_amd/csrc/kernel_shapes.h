@@ -59,6 +59,9 @@ inline bool scen_sum_supported(int din, int h) { return gru_shape_supported(din,
 // options; the ordered kernels at (h, h) for H 16 / 32 / 64, the plain sum kernels at the four 16 / 32
 // shapes and 64 / 64
 inline bool jacobian_shape_supported(int din, int h) { return gru_shape_supported(din, h); }
+// the scenario adjoint (scenario_adjoint.hip, ign_backward_scenarios): the shapes both the scenario
+// kernels and §3o's source gather are instantiated for; the ordered kernel at (h, h)
+inline bool scen_adj_supported(int din, int h) { return scen_sum_supported(din, h) && jacobian_shape_supported(din, h); }
 // pack_gru's mode: 0 the default cell (scaled fragments, bias [2][3H]); else kPackGruRaw | the raw
 // bias tensor's rows (2: [2][3H], 1: [3H], 0: none, a block of zeros)
 constexpr int kPackGruRaw = 4;

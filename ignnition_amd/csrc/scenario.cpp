@@ -6,7 +6,7 @@
 // stack.  Nothing of the batch is written: its states, tables, feature buffer, predictions and
 // captured graph stay as the last forward left them.
 
-#include "mp_step.h"
+#include "jacobian_common.h"
 #include "scenario.h"
 #include "train_kernels.h"
 
@@ -35,31 +35,6 @@ struct Scratch {
     return IGN_OK;
   }
 };
-
-int refuse(const char* what) { return fail(IGN_ERR_UNSUPPORTED, "forward scenarios: %s", what); }
-
-// what the scenario kernels do not cover, by name
-int check_scope(const ign_plan* p, const ign_batch* b) {
-  for (int64_t h : b->halo)
-    if (h) return refuse("a batch with halo rows (an edge-cut partition)");
-  if (b->train && train_step_open(b->train))
-    return refuse("a training step is open (between a training forward and the end of its backward)");
-  for (const MPP& mp : p->mps) {
-    if (mp.aggr == IGN_AGGR_ATTENTION) return refuse("attention aggregation");
-    if (mp.aggr == IGN_AGGR_CONVOLUTION) return refuse("convolution aggregation");
-    if (mp.feature_concat) return refuse("concat on axis 2");
-    for (const MsgNN& nn : mp.nn)
-      if (!nn.layers.empty()) return refuse("a message network (message-creation layers on an MP source)");
-    const CellP& cp = p->cells[mp.cell];
-    if (!cp.is_default()) return refuse("a GRU cell with options (ign_plan_set_cell_options)");
-    if (gru_wide_supported(mp.din, cp.H)) return refuse("the 128/128 GRU shape");
-    if (mp.din != cp.din || !scen_sum_supported(mp.din, cp.H) || (mp.sorted && !scen_seq_supported(cp.H)))
-      return fail(IGN_ERR_UNSUPPORTED, "forward scenarios: GRU shape %d / %d", mp.din, cp.H);
-  }
-  if (!p->ro_ops.empty()) return refuse("a readout operation before predict");
-  if (!p->norms.empty()) return refuse("LayerNormalization");
-  return IGN_OK;
-}
 
 struct RawCell {   // pack_gru's unscaled form of one cell, packed per call from the live parameters
   float *W = nullptr, *U = nullptr, *b = nullptr;
@@ -203,6 +178,6 @@ extern "C" int ign_forward_scenarios(ign_batch* b, int32_t n_scen, const float* 
   for (int e = 0; feat && e < n_ents; ++e)
     if (feat[e] && (p->ents[e].feature_total <= 0 || !b->d_feat[e]))
       return fail(IGN_ERR_INVALID, "forward scenarios: entity %d has no features", e);
-  if ((rc = check_scope(p, b))) return rc;
+  if ((rc = scen_check_scope(p, b, "forward scenarios"))) return rc;
   return forward_scenarios(p, b, n_scen, feat, pred);
 }

@@ -46,9 +46,16 @@ hipError_t launch_init_state_scen(float* state, const float* scen, const float* 
 // listed projected rows carrying the bias once: multi_sum_kernel's arithmetic); W = 3H
 hipError_t launch_table_rows_scen(float* table, int64_t zero_row, int64_t n_multi, const int32_t* ptr,
                                   const uint32_t* rows, const float* bias, int W, int64_t sp, hipStream_t st);
+// With coef (16-byte aligned) the two updates also store the linearisation of every real step, PER
+// SCENARIO (ign_backward_scenarios): the rows (z, P, R, Q, S) of jacobian.h as tiles
+// [item][n_blk][kScenCoef][16][H], item = the step's index in step_code (ordered) or the order position
+// (sum), so the five [16][H] blocks of a tile-step are contiguous.  The states written are the same bits
+// with and without.
+constexpr int kScenCoef = 5;
+inline int64_t scen_coef_floats(int64_t items, int64_t n_blk, int H) { return items * n_blk * kScenCoef * 16 * H; }
 // scen_seq_supported(h)
-hipError_t launch_seq_gru_scen(const SeqScenArgs& a, int h, hipStream_t st);
+hipError_t launch_seq_gru_scen(const SeqScenArgs& a, int h, hipStream_t st, float* coef = nullptr);
 // scen_sum_supported(din, h)
-hipError_t launch_sum_gru_scen(const SumScenArgs& a, int din, int h, hipStream_t st);
+hipError_t launch_sum_gru_scen(const SumScenArgs& a, int din, int h, hipStream_t st, float* coef = nullptr);
 // out[s][p][u] = y[p][s][u] for s < n_scen: the padding scenarios stay behind
 hipError_t launch_gather_pred_scen(const float* y, int64_t n_pred, int64_t n_scen, int units, float* out, hipStream_t st);

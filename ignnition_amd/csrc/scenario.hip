@@ -52,20 +52,40 @@ __device__ __forceinline__ void sweep3(const f4* M4, int lane, const f4 (&v)[K /
 }
 
 // One step for the wave's 16 scenarios.  acc: a_z, a_r, b_hh on entry (used up); ah: a_h; h in, h' out.
-template <int H>
+// LIN (ign_backward_scenarios): the step's linearisation too, the rows (z, P, R, Q, S) of
+//   hd' = z hd + P (ad_z + hd.U_z) + R (ad_r + hd.U_r) + Q ad_h + S (hd.U_h)
+// of THIS lane's scenario, into the tile's five [16][H] blocks at cf (the lane's row and unit group of
+// block 0): a lane's four accumulator registers are four consecutive units, so every store is 16 bytes.
+// The primal's own expressions are the ones above the if: h' keeps forward_scenarios' bits.
+template <int H, bool LIN>
 __device__ __forceinline__ void scen_step(const f4* U4, int lane, f4 (&h)[H / 16], f4 (&acc)[3][H / 16],
-                                          const f4 (&ah)[H / 16]) {
+                                          const f4 (&ah)[H / 16], float* cf) {
   constexpr int NT = H / 16;
   sweep3<H, H>(U4, lane, h, acc);
 #pragma unroll
-  for (int t = 0; t < NT; ++t)
+  for (int t = 0; t < NT; ++t) {
+    f4 k[kScenCoef];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const float z = sigmoidf_(acc[0][t][r]);
       const float rr = sigmoidf_(acc[1][t][r]);
       const float c = tanhf_(ah[t][r] + rr * acc[2][t][r]);
+      const float h0 = h[t][r];
       h[t][r] = c + z * (h[t][r] - c);
+      if constexpr (LIN) {
+        const float Q = (1.f - z) * (1.f - c * c);
+        k[0][r] = z;
+        k[1][r] = (h0 - c) * (z * (1.f - z));
+        k[2][r] = Q * (rr * (1.f - rr)) * acc[2][t][r];
+        k[3][r] = Q;
+        k[4][r] = Q * rr;
+      }
     }
+    if constexpr (LIN) {
+#pragma unroll
+      for (int q = 0; q < kScenCoef; ++q) st4(cf + q * 16 * H + 16 * t, k[q]);
+    }
+  }
 }
 
 __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
@@ -122,8 +142,10 @@ __global__ void table_rows_scen_kernel(float* __restrict__ table, int64_t zero_r
 // ---------------------------------------------------------------------------------------------
 // Ordered update.  One wave per (order position, scenario block) for the whole sequence: h in
 // registers, U in LDS once per workgroup (48 KB at H = 64), the bias b_hh in registers.
-template <int H>
-__global__ __launch_bounds__(256) void seq_gru_scen_kernel(SeqScenArgs a) {
+// LIN: every real step's coefficient tile goes to coef [step][block][5][16][H], step counted over the
+// batch's step_code array (step_ptr[pos] + t).
+template <int H, bool LIN>
+__global__ __launch_bounds__(256) void seq_gru_scen_kernel(SeqScenArgs a, float* __restrict__ coef) {
   constexpr int NT = H / 16, W3 = 3 * H;
   __shared__ f4 su[3 * NT * NT * 64];
   {
@@ -145,7 +167,8 @@ __global__ __launch_bounds__(256) void seq_gru_scen_kernel(SeqScenArgs a) {
     const int64_t s = (w - pos * a.n_blk) * 16 + j;   // this lane's scenario
     const int row = uniform(a.order[pos]);
     const int L = uniform(a.len[pos]);
-    const uint32_t* codes = a.step_code + uniform(a.step_ptr[pos]);
+    const int s0 = uniform(a.step_ptr[pos]);
+    const uint32_t* codes = a.step_code + s0;
     const int64_t hofs = scen_offset(row, s, sp, H) + 4 * g;
     f4 h[NT];
 #pragma unroll
@@ -176,7 +199,9 @@ __global__ __launch_bounds__(256) void seq_gru_scen_kernel(SeqScenArgs a) {
           acc[1][i] = x[1][i];
           acc[2][i] = bhh[i];
         }
-        scen_step<H>(su, lane, h, acc, x[2]);
+        float* cf = nullptr;
+        if constexpr (LIN) cf = coef + (((int64_t)(s0 + t) * a.n_blk + (w - pos * a.n_blk)) * kScenCoef * 16 + j) * H + 4 * g;
+        scen_step<H, LIN>(su, lane, h, acc, x[2], cf);
 #pragma unroll
         for (int G = 0; G < 3; ++G)
 #pragma unroll
@@ -192,8 +217,9 @@ __global__ __launch_bounds__(256) void seq_gru_scen_kernel(SeqScenArgs a) {
 // Sum update.  One wave per (order position, scenario block); W and U in LDS once per workgroup, the
 // grid persistent.  x = the destination's messages added one by one in CSR order, four [16][DIN]
 // blocks in flight; without a message x = 0.
-template <int DIN, int H>
-__global__ __launch_bounds__(256) void sum_gru_scen_kernel(SumScenArgs a) {
+// LIN: the destination's coefficient tile goes to coef [order position][block][5][16][H].
+template <int DIN, int H, bool LIN>
+__global__ __launch_bounds__(256) void sum_gru_scen_kernel(SumScenArgs a, float* __restrict__ coef) {
   constexpr int NC = DIN / 16, NT = H / 16;
   constexpr int WF = 3 * NT * NC * 64, UF = 3 * NT * NT * 64;   // float4 fragments
   __shared__ f4 sW[WF];
@@ -269,7 +295,9 @@ __global__ __launch_bounds__(256) void sum_gru_scen_kernel(SumScenArgs a) {
       acc[1][t] = ax[1][t];
       acc[2][t] = *reinterpret_cast<const f4*>(sbias + 3 * H + 16 * t + 4 * g);
     }
-    scen_step<H>(sU, wofs, h, acc, ax[2]);
+    float* cf = nullptr;
+    if constexpr (LIN) cf = coef + ((w * kScenCoef * 16) + j) * H + 4 * g;
+    scen_step<H, LIN>(sU, wofs, h, acc, ax[2], cf);
 #pragma unroll
     for (int t = 0; t < NT; ++t) st4(a.h_out + hofs + 16 * t, h[t]);
   }
@@ -304,16 +332,26 @@ int persistent_grid(int64_t n_work) {
 }
 
 template <int H>
-hipError_t seq_scen_launch(const SeqScenArgs& a, hipStream_t st) {
-  hipLaunchKernelGGL((seq_gru_scen_kernel<H>), dim3(persistent_grid<seq_gru_scen_kernel<H>>(a.n_dst * a.n_blk)), dim3(256), 0,
-                     st, a);
+hipError_t seq_scen_launch(const SeqScenArgs& a, float* coef, hipStream_t st) {
+  const int64_t n_work = a.n_dst * a.n_blk;
+  if (coef)
+    hipLaunchKernelGGL((seq_gru_scen_kernel<H, true>), dim3(persistent_grid<seq_gru_scen_kernel<H, true>>(n_work)), dim3(256), 0,
+                       st, a, coef);
+  else
+    hipLaunchKernelGGL((seq_gru_scen_kernel<H, false>), dim3(persistent_grid<seq_gru_scen_kernel<H, false>>(n_work)), dim3(256),
+                       0, st, a, coef);
   return hipGetLastError();
 }
 
 template <int DIN, int H>
-hipError_t sum_scen_launch(const SumScenArgs& a, hipStream_t st) {
-  hipLaunchKernelGGL((sum_gru_scen_kernel<DIN, H>), dim3(persistent_grid<sum_gru_scen_kernel<DIN, H>>(a.n_dst * a.n_blk)),
-                     dim3(256), 0, st, a);
+hipError_t sum_scen_launch(const SumScenArgs& a, float* coef, hipStream_t st) {
+  const int64_t n_work = a.n_dst * a.n_blk;
+  if (coef)
+    hipLaunchKernelGGL((sum_gru_scen_kernel<DIN, H, true>), dim3(persistent_grid<sum_gru_scen_kernel<DIN, H, true>>(n_work)),
+                       dim3(256), 0, st, a, coef);
+  else
+    hipLaunchKernelGGL((sum_gru_scen_kernel<DIN, H, false>), dim3(persistent_grid<sum_gru_scen_kernel<DIN, H, false>>(n_work)),
+                       dim3(256), 0, st, a, coef);
   return hipGetLastError();
 }
 
@@ -341,27 +379,27 @@ hipError_t launch_table_rows_scen(float* table, int64_t zero_row, int64_t n_mult
   return hipGetLastError();
 }
 
-hipError_t launch_seq_gru_scen(const SeqScenArgs& a, int h, hipStream_t st) {
-  if (!scen_seq_supported(h) || a.n_blk < 1) return hipErrorInvalidValue;
+hipError_t launch_seq_gru_scen(const SeqScenArgs& a, int h, hipStream_t st, float* coef) {
+  if (!scen_seq_supported(h) || a.n_blk < 1 || (reinterpret_cast<uintptr_t>(coef) & 15)) return hipErrorInvalidValue;
   if (!a.h_in || !a.h_out || !a.table || !a.Up || !a.bias) return hipErrorInvalidValue;
   if (a.n_dst == 0) return hipSuccess;
   switch (h) {
-    case 16: return seq_scen_launch<16>(a, st);
-    case 32: return seq_scen_launch<32>(a, st);
-    case 64: return seq_scen_launch<64>(a, st);
+    case 16: return seq_scen_launch<16>(a, coef, st);
+    case 32: return seq_scen_launch<32>(a, coef, st);
+    case 64: return seq_scen_launch<64>(a, coef, st);
     default: return hipErrorInvalidValue;
   }
 }
 
-hipError_t launch_sum_gru_scen(const SumScenArgs& a, int din, int h, hipStream_t st) {
-  if (!scen_sum_supported(din, h) || a.n_blk < 1) return hipErrorInvalidValue;
+hipError_t launch_sum_gru_scen(const SumScenArgs& a, int din, int h, hipStream_t st, float* coef) {
+  if (!scen_sum_supported(din, h) || a.n_blk < 1 || (reinterpret_cast<uintptr_t>(coef) & 15)) return hipErrorInvalidValue;
   if (!a.h_in || !a.h_out || !a.Wp || !a.Up || !a.bias) return hipErrorInvalidValue;
   if (a.n_dst == 0) return hipSuccess;
-  if (din == 32 && h == 32) return sum_scen_launch<32, 32>(a, st);
-  if (din == 16 && h == 16) return sum_scen_launch<16, 16>(a, st);
-  if (din == 16 && h == 32) return sum_scen_launch<16, 32>(a, st);
-  if (din == 32 && h == 16) return sum_scen_launch<32, 16>(a, st);
-  return sum_scen_launch<64, 64>(a, st);
+  if (din == 32 && h == 32) return sum_scen_launch<32, 32>(a, coef, st);
+  if (din == 16 && h == 16) return sum_scen_launch<16, 16>(a, coef, st);
+  if (din == 16 && h == 32) return sum_scen_launch<16, 32>(a, coef, st);
+  if (din == 32 && h == 16) return sum_scen_launch<32, 16>(a, coef, st);
+  return sum_scen_launch<64, 64>(a, coef, st);
 }
 
 hipError_t launch_gather_pred_scen(const float* y, int64_t n_pred, int64_t n_scen, int units, float* out, hipStream_t st) {

@@ -1083,6 +1083,46 @@ class Batch:
                 col += size
         return pred, res
 
+    def scenario_gradients(self, features: dict, cotangents=None, scenarios: int = None):
+        """Input gradients at S feature sets on this batch's graphs, in one pass (ign_backward_scenarios):
+        ``(pred [S, predictions, units], {entity: {feature: ndarray [S, rows, size]}})`` where entry s is
+        the gradient of ``sum(cotangents[s] * pred[s])`` with respect to scenario s's own values of the
+        feature -- instead of S rounds of ``set_features`` / ``forward_train`` / ``backward`` /
+        ``feature_gradients``.  ``features`` and ``scenarios`` are ``forward_scenarios``' (an entity left
+        out keeps the batch's values in every scenario, and still gets its gradient); ``cotangents``:
+        ``[S, predictions, units]``, or ``[S, predictions]`` when units is 1, default ones.  The gradients
+        are with respect to the normalised values, split per feature as ``feature_gradients`` splits
+        them; entities without features are left out.  ``pred`` is ``forward_scenarios``' bit for bit; a
+        scenario's bits depend neither on S nor on its index.  No training tables are needed and the
+        batch's own states and predictions are not touched.  The ``ValueError``s are
+        ``forward_scenarios``' and, for ``cotangents``, a wrong shape; a model outside the kernels' scope
+        is an ``EngineError`` that names the feature."""
+        p = self.engine.plan
+        S, ptrs, keep = self._stacked_feature_rows("scenario_gradients", "scenarios", "features", "scenarios", features, scenarios)
+        shape = (S, self.predictions, self.output_units)
+        w = np.ones(shape, np.float32) if cotangents is None else np.ascontiguousarray(cotangents, np.float32)
+        if w.ndim == 2 and self.output_units == 1:
+            w = w[:, :, None]
+        if w.shape != shape:
+            raise ValueError("scenario_gradients: cotangents have shape %s, %s is needed" % (tuple(np.shape(cotangents)), list(shape)))
+        outs = (C.c_void_p * len(p.entities))()
+        grads = {}
+        for e, feats in enumerate(p.features):
+            F = sum(size for _, size in feats)
+            if F:
+                grads[e] = np.empty((S, self.rows[e], F), np.float32)
+                outs[e] = grads[e].ctypes.data_as(C.c_void_p)
+        pred = np.empty(shape, np.float32)
+        check(lib.ign_backward_scenarios(self.handle, S, ptrs, len(p.entities), w.ctypes.data_as(C.c_void_p),
+                                         pred.ctypes.data_as(C.c_void_p), outs))
+        res = {}
+        for e, g in grads.items():
+            res[p.entities[e]], col = {}, 0
+            for name, size in p.features[e]:
+                res[p.entities[e]][name] = g[:, :, col:col + size].copy()
+                col += size
+        return pred, res
+
     # ---- what-if analysis: new per-edge parameters (params_<adj>) on the same graphs, their gradient
     def _edge_sources(self, adj: str):
         """(edges of the batch, param_dim, [(mp, source)]) of adjacency ``adj`` (edge_param_sources)."""

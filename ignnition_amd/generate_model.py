@@ -358,23 +358,19 @@ class ComnetModel:
         finally:
             b.close()
 
-    def predict_scenarios(self, graphs, features: dict) -> np.ndarray:
-        """Predictions ``[S, predictions, units]`` of a batch of graphs under S sets of feature values:
-        ``features`` is ``{feature name: array [S, rows(, size)]}`` in batch row order, raw values, to
-        which the model's normalisation functions are applied by name exactly as when a batch is built
-        (``normalization``); an entity none of whose features is named keeps the graphs' values in every
-        scenario, an entity with several features needs all of them.  One pass
-        of ``Batch.forward_scenarios`` on one batch: the index tables are lowered and uploaded once."""
+    def _scenario_features(self, what: str, features: dict):
+        """``(S, {entity: {feature: normalised [S, rows(, size)]}})`` of raw ``{feature name: [S, rows(, size)]}``
+        arrays: the model's normalisation functions applied by name exactly as when a batch is built."""
         names = {f: ent for ent, feats in zip(self.plan.entities, self.plan.features) for f, _ in feats}
         unknown = sorted(set(features) - set(names))
         if unknown:
-            raise ValueError("predict_scenarios: unknown feature(s) %s (the model has %s)" % (unknown, sorted(names)))
+            raise ValueError("%s: unknown feature(s) %s (the model has %s)" % (what, unknown, sorted(names)))
         given = {f.name: np.asarray(v, np.float32) for f in self.model_info.get_all_features()
                  for v in [features.get(f.name)] if v is not None}
         counts = {int(v.shape[0]) for v in given.values() if v.ndim >= 2}
         if len(counts) != 1 or any(v.ndim < 2 for v in given.values()):
-            raise ValueError("predict_scenarios: the arrays must be [S, rows, ...] with one S (got %s)"
-                             % sorted(tuple(v.shape) for v in given.values()))
+            raise ValueError("%s: the arrays must be [S, rows, ...] with one S (got %s)"
+                             % (what, sorted(tuple(v.shape) for v in given.values())))
         S = counts.pop()
         for f in self.model_info.get_all_features():
             if f.name in given and str(f.normalization) != "None":
@@ -384,11 +380,39 @@ class ComnetModel:
             if any(f in given for f, _ in feats):
                 missing = [f for f, _ in feats if f not in given]
                 if missing:   # an entity's columns travel together (ign_forward_scenarios' feat[e])
-                    raise ValueError("predict_scenarios: entity %r needs all of its features, %s missing" % (ent, missing))
+                    raise ValueError("%s: entity %r needs all of its features, %s missing" % (what, ent, missing))
                 per_entity[ent] = {f: given[f] for f, _ in feats}
+        return S, per_entity
+
+    def predict_scenarios(self, graphs, features: dict) -> np.ndarray:
+        """Predictions ``[S, predictions, units]`` of a batch of graphs under S sets of feature values:
+        ``features`` is ``{feature name: array [S, rows(, size)]}`` in batch row order, raw values, to
+        which the model's normalisation functions are applied by name exactly as when a batch is built
+        (``normalization``); an entity none of whose features is named keeps the graphs' values in every
+        scenario, an entity with several features needs all of them.  One pass
+        of ``Batch.forward_scenarios`` on one batch: the index tables are lowered and uploaded once."""
+        S, per_entity = self._scenario_features("predict_scenarios", features)
         b = self.batch(graphs)
         try:
             return b.forward_scenarios(per_entity, scenarios=S)
+        finally:
+            b.close()
+
+    def scenario_sensitivities(self, graphs, features: dict, dpred=None):
+        """``(predictions [S, predictions, units], {entity: {feature: gradient [S, rows, size]}})`` of a batch
+        of graphs under S sets of feature values: entry s is what ``sensitivities(graphs_s, dpred=dpred[s])``
+        returns, to rounding, for the graphs with scenario s's values, under the same conventions
+        (gradients with respect to the normalised values the engine is fed, in batch row order; entities
+        without features left out).  ``features`` is ``predict_scenarios``': raw ``{feature name: array [S,
+        rows(, size)]}``, normalised by name.  ``dpred``: ``[S, predictions(, units)]``, default ones.  One
+        pass of ``Batch.scenario_gradients``: no training tables, no parameter gradients, whatever S."""
+        S, per_entity = self._scenario_features("scenario_sensitivities", features)
+        b = self.batch(graphs)
+        try:
+            w = None if dpred is None else np.asarray(dpred, np.float32)
+            if w is not None and w.ndim >= 2:
+                w = w.reshape(w.shape[0], b.predictions, b.output_units)
+            return b.scenario_gradients(per_entity, w, scenarios=S)
         finally:
             b.close()
 

@@ -569,6 +569,34 @@ int  ign_forward_jacobian(ign_batch* batch, int32_t n_dir, const float* const* d
  * "backward jacobian:". */
 int  ign_backward_jacobian(ign_batch* batch, int32_t n_cot, const float* cot, int n_ents, float* pred,
                            float* const* dfeat_out);
+/* ---- Scenario gradients (ABI 13 addition) -----------------------------------------------------------
+ * The gradient of an objective at n_scen DIFFERENT feature sets on one topology: descent on n_scen
+ * candidate capacity plans at once, multi-start traffic engineering, a robust objective over n_scen
+ * traffic matrices.  ign_backward_scenarios runs ign_forward_scenarios' primal with a gate epilogue that
+ * keeps, per scenario, the coefficient rows of every real GRU step, then predict's adjoint and one
+ * reverse sweep through the transposed linear steps, the 16 rows of every MFMA tile 16 scenarios of one
+ * destination throughout -- instead of n_scen rounds of ign_batch_set_features +
+ * ign_forward_train + ign_backward + ign_batch_feature_gradients.  It needs no training tables and
+ * forms no parameter gradient.  feat[e] is ign_forward_scenarios': [n_scen][rows of entity e][F_e], or
+ * NULL (every scenario uses the batch's current values of that entity); feat itself may be NULL.  cot is
+ * [n_scen][predictions][units]; n_ents must be the plan's entity count; dfeat_out[e] is [n_scen][rows of
+ * entity e][F_e], dfeat_out[e][s] = d(sum cot[s] . pred[s]) / d(features of e in scenario s), in terms of
+ * the values ign_batch_create would be given, or NULL (not wanted); pred is [n_scen][predictions][units]
+ * or NULL.  Host or device memory; the call returns when they are written.  pred is
+ * ign_forward_scenarios' pred bit for bit.  A scenario's results depend neither on n_scen, nor on s, nor
+ * on the chunk that covered it, bit for bit; zero cotangents give zeros exactly; source rows sum their
+ * readers in ascending step / message order.  The batch is not written; parameters are read as they are
+ * at the call.  The whole pass runs per chunk of c blocks of 16 scenarios.  Device memory, scratch of the
+ * batch's pool, per block: 5 * 16 H floats per real step (ordered) or destination (sum) per iteration,
+ * 4 * 16 (rows_e H_e) floats per entity, 16 table rows of 3H per table row of the largest ordered MP, the
+ * step cotangents [steps][16][3H] of the largest MP and 16 predictions x (every predict layer + twice the
+ * widest); c is the most blocks that stay within 2 GiB, or within IGN_SCEN_GRAD_CHUNK_MIB MiB when that
+ * environment variable is set at the call (one block at least).
+ * IGN_ERR_INVALID: n_scen < 1, a null batch, cot or dfeat_out, a wrong n_ents, a non-NULL feat[e] or
+ * dfeat_out[e] on an entity without features.  Scope and refusals are ign_forward_scenarios', the
+ * messages begin "backward scenarios:". */
+int  ign_backward_scenarios(ign_batch* batch, int32_t n_scen, const float* const* feat, int n_ents, const float* cot,
+                            float* pred, float* const* dfeat_out);
 /* ---- Edge parameters of a live batch and their gradient (ABI 13 additions) -----------------------
  * The other input a what-if changes on fixed graphs: params_<adj>, which a message network of MP
  * source (mp, source) reads as edge_params.  Each such source owns one buffer [n_edges][param_dim];
