@@ -129,7 +129,8 @@ SYMBOLS = ["ign_abi_version", "ign_last_error", "ign_device_count", "ign_plan_cr
            "ign_plan_mp_dead_last", "ign_plan_set_cell_options", "ign_batch_set_features",
            "ign_batch_feature_gradients", "ign_batch_set_edge_params", "ign_batch_enable_edge_param_gradients",
            "ign_batch_edge_param_gradients", "ign_nonfinite_count", "ign_forward_tangent",
-           "ign_forward_scenarios", "ign_forward_jacobian", "ign_backward_jacobian", "ign_backward_scenarios"]
+           "ign_forward_scenarios", "ign_forward_jacobian", "ign_backward_jacobian", "ign_backward_scenarios",
+           "ign_backward_scenarios_params"]
 
 ABI_VERSION = 13
 PART = {"all": 0, "interior": 1, "boundary": 2}
@@ -227,6 +228,7 @@ def _load():
         "ign_forward_jacobian": (C.c_int, [VP, i32, P(VP), C.c_int, VP, VP]),
         "ign_backward_jacobian": (C.c_int, [VP, i32, VP, C.c_int, VP, P(VP)]),
         "ign_backward_scenarios": (C.c_int, [VP, i32, P(VP), C.c_int, VP, VP, P(VP)]),
+        "ign_backward_scenarios_params": (C.c_int, [VP, i32, P(VP), C.c_int, VP, VP, VP]),
     }
     # an A/B build of an older tree may lack newer entry points: only the A/B tools, which set
     # IGN_AB_LIB=1 next to IGN_LIB_PATH, skip them; any other library must export every symbol

@@ -20,7 +20,7 @@ SOURCES = ["engine.cpp", "mp_step.cpp", "plan_lower.cpp", "batch_lower.cpp", "de
            "train_kernels.hip", "learn_kernels.hip", "readout_kernels.hip", "resident.hip", "readout_h32.hip", "train_csr.hip",
            "dropout.cpp", "dropout_kernels.hip", "layernorm.cpp", "layernorm_kernels.hip", "cell_options.cpp", "gru_cell.hip", "tangent.cpp", "tangent.hip", "gru_wide.hip", "scenario.cpp", "scenario.hip",
            "jacobian.cpp", "jacobian.hip", "adjoint.cpp", "adjoint.hip",
-           "scenario_adjoint.cpp", "scenario_adjoint.hip"]
+           "scenario_adjoint.cpp", "scenario_adjoint.hip", "scenario_wgrad.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-Wno-unused-value"]
 EXTRA = {"kernels_bf.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "resident.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
          "readout_h32.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],

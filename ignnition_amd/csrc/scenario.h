@@ -53,9 +53,15 @@ hipError_t launch_table_rows_scen(float* table, int64_t zero_row, int64_t n_mult
 // with and without.
 constexpr int kScenCoef = 5;
 inline int64_t scen_coef_floats(int64_t items, int64_t n_blk, int H) { return items * n_blk * kScenCoef * 16 * H; }
+// With keep (16-byte aligned, coef given) they also store what a weight gradient contracts the adjoint's
+// products with (ign_backward_scenarios_params): the ordered update the state in front of
+// every real step, one [16][H] tile per (step, block) -- row-major, i.e. the flat rows step * Sp + s, or with
+// keep_t transposed [H][16] --, the sum update its summed messages [order position][Sp][DIN].
 // scen_seq_supported(h)
-hipError_t launch_seq_gru_scen(const SeqScenArgs& a, int h, hipStream_t st, float* coef = nullptr);
+hipError_t launch_seq_gru_scen(const SeqScenArgs& a, int h, hipStream_t st, float* coef = nullptr, float* keep = nullptr,
+                               bool keep_t = false);
 // scen_sum_supported(din, h)
-hipError_t launch_sum_gru_scen(const SumScenArgs& a, int din, int h, hipStream_t st, float* coef = nullptr);
+hipError_t launch_sum_gru_scen(const SumScenArgs& a, int din, int h, hipStream_t st, float* coef = nullptr,
+                               float* keep = nullptr);
 // out[s][p][u] = y[p][s][u] for s < n_scen: the padding scenarios stay behind
 hipError_t launch_gather_pred_scen(const float* y, int64_t n_pred, int64_t n_scen, int units, float* out, hipStream_t st);

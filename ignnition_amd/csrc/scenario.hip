@@ -144,8 +144,11 @@ __global__ void table_rows_scen_kernel(float* __restrict__ table, int64_t zero_r
 // registers, U in LDS once per workgroup (48 KB at H = 64), the bias b_hh in registers.
 // LIN: every real step's coefficient tile goes to coef [step][block][5][16][H], step counted over the
 // batch's step_code array (step_ptr[pos] + t).
-template <int H, bool LIN>
-__global__ __launch_bounds__(256) void seq_gru_scen_kernel(SeqScenArgs a, float* __restrict__ coef) {
+// KEEP (ign_backward_scenarios_params): the state in front of every real step too, one
+// [16][H] tile per (step, block) at keep: 1 row-major, so the tiles are the flat rows step * Sp + s of a
+// row contraction; 2 transposed [H][16], the 16-byte A operand loads of the adjoint's fused h_prev^T . ubar.
+template <int H, bool LIN, int KEEP>
+__global__ __launch_bounds__(256) void seq_gru_scen_kernel(SeqScenArgs a, float* __restrict__ coef, float* __restrict__ keep) {
   constexpr int NT = H / 16, W3 = 3 * H;
   __shared__ f4 su[3 * NT * NT * 64];
   {
@@ -201,6 +204,16 @@ __global__ __launch_bounds__(256) void seq_gru_scen_kernel(SeqScenArgs a, float*
         }
         float* cf = nullptr;
         if constexpr (LIN) cf = coef + (((int64_t)(s0 + t) * a.n_blk + (w - pos * a.n_blk)) * kScenCoef * 16 + j) * H + 4 * g;
+        if constexpr (KEEP != 0) {
+          float* hp = keep + ((int64_t)(s0 + t) * a.n_blk + (w - pos * a.n_blk)) * 16 * H;
+#pragma unroll
+          for (int i = 0; i < NT; ++i) {
+            if constexpr (KEEP == 1) st4(hp + j * H + 16 * i + 4 * g, h[i]);
+            else
+#pragma unroll
+              for (int r = 0; r < 4; ++r) hp[(16 * i + 4 * g + r) * 16 + j] = h[i][r];
+          }
+        }
         scen_step<H, LIN>(su, lane, h, acc, x[2], cf);
 #pragma unroll
         for (int G = 0; G < 3; ++G)
@@ -218,8 +231,9 @@ __global__ __launch_bounds__(256) void seq_gru_scen_kernel(SeqScenArgs a, float*
 // grid persistent.  x = the destination's messages added one by one in CSR order, four [16][DIN]
 // blocks in flight; without a message x = 0.
 // LIN: the destination's coefficient tile goes to coef [order position][block][5][16][H].
-template <int DIN, int H, bool LIN>
-__global__ __launch_bounds__(256) void sum_gru_scen_kernel(SumScenArgs a, float* __restrict__ coef) {
+// KEEP: the summed messages x too, [order position][Sp][DIN] at keep.
+template <int DIN, int H, bool LIN, bool KEEP>
+__global__ __launch_bounds__(256) void sum_gru_scen_kernel(SumScenArgs a, float* __restrict__ coef, float* __restrict__ keep) {
   constexpr int NC = DIN / 16, NT = H / 16;
   constexpr int WF = 3 * NT * NC * 64, UF = 3 * NT * NT * 64;   // float4 fragments
   __shared__ f4 sW[WF];
@@ -276,6 +290,10 @@ __global__ __launch_bounds__(256) void sum_gru_scen_kernel(SumScenArgs a, float*
 #pragma unroll
       for (int c = 0; c < NC; ++c) x[c] += ld4(p + 16 * c);
     }
+    if constexpr (KEEP) {
+#pragma unroll
+      for (int c = 0; c < NC; ++c) st4(keep + (w * 16 + j) * DIN + 16 * c + 4 * g, x[c]);
+    }
     const int64_t hofs = scen_offset(row, s, sp, H) + 4 * g;
     f4 h[NT];
 #pragma unroll
@@ -331,28 +349,27 @@ int persistent_grid(int64_t n_work) {
   return (int)std::max<int64_t>(1, std::min<int64_t>(resident, (n_work + 3) / 4));
 }
 
-template <int H>
-hipError_t seq_scen_launch(const SeqScenArgs& a, float* coef, hipStream_t st) {
-  const int64_t n_work = a.n_dst * a.n_blk;
-  if (coef)
-    hipLaunchKernelGGL((seq_gru_scen_kernel<H, true>), dim3(persistent_grid<seq_gru_scen_kernel<H, true>>(n_work)), dim3(256), 0,
-                       st, a, coef);
-  else
-    hipLaunchKernelGGL((seq_gru_scen_kernel<H, false>), dim3(persistent_grid<seq_gru_scen_kernel<H, false>>(n_work)), dim3(256),
-                       0, st, a, coef);
+template <auto KERNEL, class Args>
+hipError_t scen_launch(const Args& a, int64_t n_work, float* coef, float* keep, hipStream_t st) {
+  hipLaunchKernelGGL(KERNEL, dim3(persistent_grid<KERNEL>(n_work)), dim3(256), 0, st, a, coef, keep);
   return hipGetLastError();
 }
 
-template <int DIN, int H>
-hipError_t sum_scen_launch(const SumScenArgs& a, float* coef, hipStream_t st) {
+template <int H>
+hipError_t seq_scen_launch(const SeqScenArgs& a, float* coef, float* keep, bool keep_t, hipStream_t st) {
   const int64_t n_work = a.n_dst * a.n_blk;
-  if (coef)
-    hipLaunchKernelGGL((sum_gru_scen_kernel<DIN, H, true>), dim3(persistent_grid<sum_gru_scen_kernel<DIN, H, true>>(n_work)),
-                       dim3(256), 0, st, a, coef);
-  else
-    hipLaunchKernelGGL((sum_gru_scen_kernel<DIN, H, false>), dim3(persistent_grid<sum_gru_scen_kernel<DIN, H, false>>(n_work)),
-                       dim3(256), 0, st, a, coef);
-  return hipGetLastError();
+  if (keep && keep_t) return scen_launch<seq_gru_scen_kernel<H, true, 2>>(a, n_work, coef, keep, st);
+  if (keep) return scen_launch<seq_gru_scen_kernel<H, true, 1>>(a, n_work, coef, keep, st);
+  if (coef) return scen_launch<seq_gru_scen_kernel<H, true, 0>>(a, n_work, coef, keep, st);
+  return scen_launch<seq_gru_scen_kernel<H, false, 0>>(a, n_work, coef, keep, st);
+}
+
+template <int DIN, int H>
+hipError_t sum_scen_launch(const SumScenArgs& a, float* coef, float* keep, hipStream_t st) {
+  const int64_t n_work = a.n_dst * a.n_blk;
+  if (keep) return scen_launch<sum_gru_scen_kernel<DIN, H, true, true>>(a, n_work, coef, keep, st);
+  if (coef) return scen_launch<sum_gru_scen_kernel<DIN, H, true, false>>(a, n_work, coef, keep, st);
+  return scen_launch<sum_gru_scen_kernel<DIN, H, false, false>>(a, n_work, coef, keep, st);
 }
 
 }  // namespace
@@ -379,27 +396,31 @@ hipError_t launch_table_rows_scen(float* table, int64_t zero_row, int64_t n_mult
   return hipGetLastError();
 }
 
-hipError_t launch_seq_gru_scen(const SeqScenArgs& a, int h, hipStream_t st, float* coef) {
-  if (!scen_seq_supported(h) || a.n_blk < 1 || (reinterpret_cast<uintptr_t>(coef) & 15)) return hipErrorInvalidValue;
+hipError_t launch_seq_gru_scen(const SeqScenArgs& a, int h, hipStream_t st, float* coef, float* keep, bool keep_t) {
+  if (!scen_seq_supported(h) || a.n_blk < 1 || ((reinterpret_cast<uintptr_t>(coef) | reinterpret_cast<uintptr_t>(keep)) & 15) ||
+      (keep && !coef))
+    return hipErrorInvalidValue;
   if (!a.h_in || !a.h_out || !a.table || !a.Up || !a.bias) return hipErrorInvalidValue;
   if (a.n_dst == 0) return hipSuccess;
   switch (h) {
-    case 16: return seq_scen_launch<16>(a, coef, st);
-    case 32: return seq_scen_launch<32>(a, coef, st);
-    case 64: return seq_scen_launch<64>(a, coef, st);
+    case 16: return seq_scen_launch<16>(a, coef, keep, keep_t, st);
+    case 32: return seq_scen_launch<32>(a, coef, keep, keep_t, st);
+    case 64: return seq_scen_launch<64>(a, coef, keep, keep_t, st);
     default: return hipErrorInvalidValue;
   }
 }
 
-hipError_t launch_sum_gru_scen(const SumScenArgs& a, int din, int h, hipStream_t st, float* coef) {
-  if (!scen_sum_supported(din, h) || a.n_blk < 1 || (reinterpret_cast<uintptr_t>(coef) & 15)) return hipErrorInvalidValue;
+hipError_t launch_sum_gru_scen(const SumScenArgs& a, int din, int h, hipStream_t st, float* coef, float* keep) {
+  if (!scen_sum_supported(din, h) || a.n_blk < 1 || ((reinterpret_cast<uintptr_t>(coef) | reinterpret_cast<uintptr_t>(keep)) & 15) ||
+      (keep && !coef))
+    return hipErrorInvalidValue;
   if (!a.h_in || !a.h_out || !a.Wp || !a.Up || !a.bias) return hipErrorInvalidValue;
   if (a.n_dst == 0) return hipSuccess;
-  if (din == 32 && h == 32) return sum_scen_launch<32, 32>(a, coef, st);
-  if (din == 16 && h == 16) return sum_scen_launch<16, 16>(a, coef, st);
-  if (din == 16 && h == 32) return sum_scen_launch<16, 32>(a, coef, st);
-  if (din == 32 && h == 16) return sum_scen_launch<32, 16>(a, coef, st);
-  return sum_scen_launch<64, 64>(a, coef, st);
+  if (din == 32 && h == 32) return sum_scen_launch<32, 32>(a, coef, keep, st);
+  if (din == 16 && h == 16) return sum_scen_launch<16, 16>(a, coef, keep, st);
+  if (din == 16 && h == 32) return sum_scen_launch<16, 32>(a, coef, keep, st);
+  if (din == 32 && h == 16) return sum_scen_launch<32, 16>(a, coef, keep, st);
+  return sum_scen_launch<64, 64>(a, coef, keep, st);
 }
 
 hipError_t launch_gather_pred_scen(const float* y, int64_t n_pred, int64_t n_scen, int units, float* out, hipStream_t st) {

@@ -1123,6 +1123,31 @@ class Batch:
                 col += size
         return pred, res
 
+    def scenario_parameter_gradients(self, features: dict, cotangents=None, scenarios: int = None):
+        """Parameter gradients over S feature sets on this batch's graphs, in one pass
+        (ign_backward_scenarios_params): ``(pred [S, predictions, units], {parameter name: ndarray of the
+        tensor's shape})`` where a tensor's entry is the gradient of ``sum over s of sum(cotangents[s] *
+        pred[s])`` with respect to it -- the gradient of S samples that share this topology, instead of S
+        rounds of ``set_features`` / ``forward_train`` / ``backward``.  The names and shapes are
+        ``Engine.layout``'s.  ``features``, ``scenarios``, ``cotangents`` and the ``ValueError``s are
+        ``scenario_gradients``'.  It is the derivative of the inference forward: no l2 term, Dropout the
+        identity.  ``pred`` is ``forward_scenarios``' bit for bit and a call repeats its bits.  No training
+        tables are needed and the batch's own states and predictions are not touched; a model outside the
+        kernels' scope is an ``EngineError`` that names the feature."""
+        eng = self.engine
+        S, ptrs, keep = self._stacked_feature_rows("scenario_gradients", "scenarios", "features", "scenarios", features, scenarios)
+        shape = (S, self.predictions, self.output_units)
+        w = np.ones(shape, np.float32) if cotangents is None else np.ascontiguousarray(cotangents, np.float32)
+        if w.ndim == 2 and self.output_units == 1:
+            w = w[:, :, None]
+        if w.shape != shape:
+            raise ValueError("scenario_gradients: cotangents have shape %s, %s is needed" % (tuple(np.shape(cotangents)), list(shape)))
+        pred = np.empty(shape, np.float32)
+        flat = np.empty(eng.n_params, np.float32)
+        check(lib.ign_backward_scenarios_params(self.handle, S, ptrs, len(eng.plan.entities), w.ctypes.data_as(C.c_void_p),
+                                                pred.ctypes.data_as(C.c_void_p), flat.ctypes.data_as(C.c_void_p)))
+        return pred, {name: flat[off:off + int(np.prod(shape))].reshape(shape).copy() for name, shape, off in eng.layout}
+
     # ---- what-if analysis: new per-edge parameters (params_<adj>) on the same graphs, their gradient
     def _edge_sources(self, adj: str):
         """(edges of the batch, param_dim, [(mp, source)]) of adjacency ``adj`` (edge_param_sources)."""

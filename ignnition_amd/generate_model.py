@@ -416,6 +416,23 @@ class ComnetModel:
         finally:
             b.close()
 
+    def scenario_parameter_gradients(self, graphs, features: dict, dpred=None):
+        """``(predictions [S, predictions, units], {parameter name: gradient of the tensor's shape})`` of a
+        batch of graphs under S sets of feature values: the gradient of ``sum(dpred * predictions)`` over all
+        S scenarios with respect to every parameter tensor, in one pass of
+        ``Batch.scenario_parameter_gradients``.  ``features`` and ``dpred`` are ``scenario_sensitivities``':
+        raw ``{feature name: array [S, rows(, size)]}``, normalised by name; ``[S, predictions(, units)]``,
+        default ones."""
+        S, per_entity = self._scenario_features("scenario_parameter_gradients", features)
+        b = self.batch(graphs)
+        try:
+            w = None if dpred is None else np.asarray(dpred, np.float32)
+            if w is not None and w.ndim >= 2:
+                w = w.reshape(w.shape[0], b.predictions, b.output_units)
+            return b.scenario_parameter_gradients(per_entity, w, scenarios=S)
+        finally:
+            b.close()
+
     def __call__(self, input: dict, training: bool = False) -> np.ndarray:
         """``ComnetModel.call`` (GM:384) for one graph: [P, units] predictions."""
         return self.batch([input]).forward()

@@ -597,6 +597,30 @@ int  ign_backward_jacobian(ign_batch* batch, int32_t n_cot, const float* cot, in
  * messages begin "backward scenarios:". */
 int  ign_backward_scenarios(ign_batch* batch, int32_t n_scen, const float* const* feat, int n_ents, const float* cot,
                             float* pred, float* const* dfeat_out);
+/* ---- Scenario parameter gradients (ABI 13 addition) -------------------------------------------------
+ * The same pass for the PARAMETERS: grads = d(sum_s cot[s] . pred[s]) / d(every parameter tensor), summed over
+ * the n_scen feature sets -- the gradient of a dataset of n_scen traffic matrices on one topology and routing,
+ * or the parameter sensitivities of an objective over n_scen scenarios, instead of n_scen rounds of
+ * ign_batch_set_features + ign_forward_train + ign_backward.  batch, n_scen, feat, n_ents,
+ * cot, pred, the stream and the error codes are ign_backward_scenarios'; grads is [ign_plan_num_params]
+ * floats in the plan's parameter layout (the offsets of ign_plan_param_tensor), host or device memory,
+ * WRITTEN, not accumulated into; the alignment padding between tensors is zero.  It is the derivative of the
+ * inference forward: no l2 term, Dropout is the identity.  No feature gradient is formed.  The primal also
+ * keeps the state in front of every real GRU step and every version of every entity's states; the ordered
+ * adjoint contracts them with its products inside the sweep (H 16 / 32: dU in registers, one partial tile
+ * per wave, reduced in slot order) or, at H 64 and with IGN_SCEN_WGRAD_FUSED=0 set at the call, afterwards
+ * over the stored rows.  Every sum has a fixed order: a call repeats its bits; zero cotangents give zeros
+ * exactly; the padding scenarios contribute exactly zero.  grads adds up the chunks in chunk order, so its
+ * bits may depend on IGN_SCEN_GRAD_CHUNK_MIB, and on nothing else.  Device memory per block of 16 scenarios, on
+ * top of ign_backward_scenarios': 16 H floats per real step (ordered) or 16 DIN per destination (sum) per
+ * iteration, 16 (rows_e H_e) per further update of an entity's states, and once the widest of 16 x 3H per
+ * step (unfused ordered form) or destination (sum), 16 x 4H per destination of the largest sum MP and
+ * 16 x 3H per source row of the largest ordered MP.
+ * IGN_ERR_INVALID: n_scen < 1, a null batch, cot or grads, a wrong n_ents, a non-NULL feat[e] on an entity
+ * without features.  Scope and refusals are ign_backward_scenarios', the messages begin
+ * "scenario parameter gradients:". */
+int  ign_backward_scenarios_params(ign_batch* batch, int32_t n_scen, const float* const* feat, int n_ents,
+                                   const float* cot, float* pred, float* grads);
 /* ---- Edge parameters of a live batch and their gradient (ABI 13 additions) -----------------------
  * The other input a what-if changes on fixed graphs: params_<adj>, which a message network of MP
  * source (mp, source) reads as edge_params.  Each such source owns one buffer [n_edges][param_dim];
